@@ -9,7 +9,11 @@ N > 1 : agent a lives on rank a % N (one process per GPU); the selected agent's 
         their public poses (X and the auxiliary Y sequence) with RCCL point-to-point in place of
         the PublicPoses ROS topic.  The synchronous schedule is sequential, so this is
         strong scaling of a fixed problem.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, runs W (--warmup) steps, times exactly K (--steps) steps as one run
+between two synchronisations (value = ms_per_step = that time / K) and prints the line.  --dump-outputs DIR writes the
+iterates after the last timed step (X, Y, V in agent order, and the global cost) as DIR/<name>.npy.  --full adds every
+other leg: the longer run and the spread of K-step runs, roofline, convergence, other configurations, CPU baselines and,
+at N > 1, the multi-rank extras.
 """
 import argparse
 import ctypes as C
@@ -62,13 +66,19 @@ def single_gpu(args):
     team.prepare(args.steps)
     team.synchronize()
     torch.cuda.synchronize()
-    # (1) the contract's region: exactly K steps between two synchronisations
+    # (1) the reported figure: exactly K steps as ONE run between two synchronisations
     t0 = time.perf_counter()
     team.run(args.steps)
     team.synchronize()
     torch.cuda.synchronize()
     dt_single = time.perf_counter() - t0
-    # (2) the reported figure: R x K steps enqueued as ONE run (graphs of up to 256 iterations), at least 50 ms of replays, one
+    ms_k = dt_single / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(team_outputs(team), cost=np.array([team.cost()])))
+    if not args.full:
+        team.close()
+        return ms_k, None
+    # (2) --full: R x K steps enqueued as ONE run (graphs of up to 256 iterations), at least 50 ms of replays, one
     # synchronisation at the end -- a 20-step region is 0.5 ms, of which the launch + synchronisation round trip, the
     # opening Nesterov launch and the closing statistics launch of the run are 10 %
     reps = max(1, min(100000, int(np.ceil(0.05 / max(dt_single, 1e-6)))))
@@ -89,8 +99,9 @@ def single_gpu(args):
         team.synchronize()
         torch.cuda.synchronize()
         singles.append((time.perf_counter() - a0) / args.steps * 1e3)
-    timing = {"timed_steps": reps * args.steps, "timed_region_ms": dt * 1e3,
-              "ms_per_step_single_run_of_K": dt_single / args.steps * 1e3,
+    timing = {"timed_steps": args.steps, "timed_region_ms": dt_single * 1e3,
+              "one_run_of_R_x_K": {"steps": reps * args.steps, "region_ms": dt * 1e3, "ms_per_step": ms},
+              "ms_per_step_single_run_of_K": ms_k,
               "ms_per_step_runs_of_K": {"runs": len(singles), "mean": float(np.mean(singles)), "p95": float(np.percentile(singles, 95)),
                                         "min": float(np.min(singles))}}
     counters = team.counters()
@@ -267,7 +278,22 @@ def single_gpu(args):
     conv["plain_rtr"] = cp
     conv["asapp_tunnels"] = asapp_leg(capi)
     conv["gnc_torus3D"] = gnc_leg(capi)
-    return ms, roof, conv, cpu, counters, timing
+    return ms_k, (roof, conv, cpu, counters, timing)
+
+
+def team_outputs(team, ids=None):
+    """what a caller of the timed path reads back after its last step: the iterate X and the auxiliary (Nesterov)
+    sequences Y and V of the given agents (default: all of the team's), in agent order"""
+    ags = [team.agents[i] for i in (team.ids if ids is None else ids)]
+    return {"X": np.concatenate([a.get_X() for a in ags]), "Y": np.concatenate([a.get_Y() for a in ags]),
+            "V": np.concatenate([a.get_V() for a in ags])}
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs DIR: one float64 .npy per array"""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def restart50_leg(capi, mp, n, T, Y, fstar):
@@ -833,14 +859,31 @@ def multi_gpu_impl(args):
     lib_path, lib_version = capi.comm_library()
     cost_main = comm.global_cost(be.team, stream=be.stream.cuda_stream)
     fstar_ = F_STAR[WORKLOAD["dataset"]]
-    arm_extras_watchdog(rank, {"value": ms_lib, "ms_per_step": ms_lib, "cpu_baseline": None, "roofline": None,
-                               "relcost_after_run": (cost_main - fstar_) / fstar_,
-                               "relcost_vs_iteration": [[0, (cost_start - fstar_) / fstar_],
-                                                        [args.warmup + args.steps, (cost_main - fstar_) / fstar_]],
-                               "exchange_timing": {"ms_per_step_rccl_in_library": ms_lib, "rccl_in_library_per_step_this_rank": lib_msgs,
-                                                   "rccl_library": lib_path, "rccl_version_code": lib_version,
-                                                   "rccl_world_size": dist.get_world_size(), "backend": dist.get_backend(),
-                                                   "ranks": devices, "value_is": "rccl_in_library (dpgo_team_run_ranks)"}})
+    main_line = {"value": ms_lib, "ms_per_step": ms_lib, "cpu_baseline": None, "roofline": None,
+                 "relcost_after_run": (cost_main - fstar_) / fstar_,
+                 "relcost_vs_iteration": [[0, (cost_start - fstar_) / fstar_],
+                                          [args.warmup + args.steps, (cost_main - fstar_) / fstar_]],
+                 "exchange_timing": {"ms_per_step_rccl_in_library": ms_lib, "rccl_in_library_per_step_this_rank": lib_msgs,
+                                     "rccl_library": lib_path, "rccl_version_code": lib_version,
+                                     "rccl_world_size": dist.get_world_size(), "backend": dist.get_backend(),
+                                     "ranks": devices, "value_is": "rccl_in_library (dpgo_team_run_ranks)"}}
+    if args.dump_outputs:
+        with be.stream_context():
+            local = {} if be.team is None else {a: team_outputs(be.team, [a]) for a in mine}
+        parts = [None] * world
+        dist.all_gather_object(parts, local)
+        if rank == 0:
+            by_agent = {a: o for p in parts for a, o in p.items()}
+            arrays = {k: np.concatenate([by_agent[a][k] for a in range(NA)]) for k in ("X", "Y", "V")}
+            arrays["cost"] = np.array([cost_main])
+            dump_outputs(args.dump_outputs, arrays)
+    if not args.full:
+        dist.barrier()
+        be.close()
+        comm.close()
+        dist.destroy_process_group()
+        return rank, main_line
+    arm_extras_watchdog(rank, main_line)
     # (1) the same messages driven from the host, one exchange per iteration (torch.distributed isend / irecv)
     m0 = drv.messages
     ms_rccl = timed(lambda k: [drv.step() for _ in range(k)])
@@ -961,10 +1004,12 @@ def multi_gpu_impl(args):
     exchange["config2_sphere2500_8_agents_rtr"] = config2_ranks_leg(args, capi, dist, torch, m, n, T, Y, rank, local_rank, world, comm)
     comm.close()
     dist.destroy_process_group()
-    return rank, ms, cost, roof, exchange, {"ms_per_block_update": cp_ms, "classes": len(drv2.groups),
-                            "relcost_after_45_sweeps": (cp_cost - F_STAR[WORKLOAD["dataset"]]) / F_STAR[WORKLOAD["dataset"]]}, \
-        {"workload": "data/tunnels, 8 robots on %d rank(s), RGD stepsize 0.2 + preconditioner, lockstep ticks" % world,
-         "ms_per_tick": tick_ms, "cost_initial": c0, "cost_after_220_ticks": c1, **free}
+    cp = {"ms_per_block_update": cp_ms, "classes": len(drv2.groups),
+          "relcost_after_45_sweeps": (cp_cost - F_STAR[WORKLOAD["dataset"]]) / F_STAR[WORKLOAD["dataset"]]}
+    asapp = {"workload": "data/tunnels, 8 robots on %d rank(s), RGD stepsize 0.2 + preconditioner, lockstep ticks" % world,
+             "ms_per_tick": tick_ms, "cost_initial": c0, "cost_after_220_ticks": c1, **free}
+    return rank, {"value": ms, "ms_per_step": ms, "roofline": roof, "cpu_baseline": None, "relcost_after_run": (cost - fstar_) / fstar_,
+                  "colour_parallel_plain_rtr": cp, "asapp_ticks_tunnels": asapp, "exchange_timing": exchange}
 
 
 def loopback_leg(capi, mp, T, Y, comm, args):
@@ -1054,6 +1099,10 @@ def spawn_ranks(args):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--steps", str(args.steps), "--warmup", str(args.warmup)]
         if args.spawn_check:
             cmd.append("--spawn-check")
+        if args.full:
+            cmd.append("--full")
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE if r == 0 else sys.stderr, text=True if r == 0 else None))
     t0, rc, out0 = time.time(), 0, ""
     try:
@@ -1101,7 +1150,14 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--spawn-check", action="store_true", help="rendezvous test of the built-in launcher, no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: longer runs, roofline, other configurations, convergence, "
+                         "CPU baselines, multi-rank extras")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # N > 1 without a launcher (no RANK in the environment): this process becomes the launcher
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -1120,11 +1176,17 @@ def main():
     _OUT = out
     force_dist = os.environ.get("DPGO_BENCH_FORCE_DIST") == "1"  # exercise the N > 1 driver with one rank
     if args.gpus <= 1 and int(os.environ.get("WORLD_SIZE", "1")) <= 1 and not force_dist:
-        ms, roof, conv, cpu, counters, timing = single_gpu(args)
-        out["config"]["value_is"] = ("ms per step of ONE run of R x K steps (R x K >= 2000: at least 50 ms of replays) between two "
-                                     "synchronisations; the single K-step region of the contract is ms_per_step_k_region")
+        ms, full = single_gpu(args)
+        out["config"]["value_is"] = ("ms per step of ONE run of exactly K (--steps) steps between two synchronisations, after W "
+                                     "(--warmup) steps and the capture of the run's hipGraphs")
+        out.update({"value": ms, "ms_per_step": ms})
+        if full is None:
+            print(json.dumps(out))
+            return
+        roof, conv, cpu, counters, timing = full
         out["config"]["ms_per_step_k_region"] = timing["ms_per_step_single_run_of_K"]
-        out.update({"value": ms, "ms_per_step": ms, "ms_per_step_k_region": timing["ms_per_step_single_run_of_K"],
+        out.update({"ms_per_step_k_region": timing["ms_per_step_single_run_of_K"],
+                    "ms_per_step_one_run_of_R_x_K": timing["one_run_of_R_x_K"]["ms_per_step"],
                     "ms_per_step_k_region_mean_of_15": timing["ms_per_step_runs_of_K"]["mean"],
                     "timing": timing, "roofline": roof, "cpu_baseline": cpu, "convergence": conv,
                     "iters_to_relcost_1e-6": conv["rgd_nesterov"]["iters_to_relcost_1e-6"],
@@ -1138,18 +1200,14 @@ def main():
                                          "formed; deep_carried: those that also found the private part of their product formed"}})
         print(json.dumps(out))
     else:
-        rank, ms, cost, roof, exchange, cp, asapp = multi_gpu(args)
+        rank, line = multi_gpu(args)
         if rank == 0:
-            fstar = F_STAR[WORKLOAD["dataset"]]
-            out.update({"value": ms, "ms_per_step": ms, "roofline": roof, "cpu_baseline": None,
-                        "relcost_after_run": (cost - fstar) / fstar, "colour_parallel_plain_rtr": cp,
-                        "asapp_ticks_tunnels": asapp,
-                        "launched_by": "bench.py (built-in launcher)" if os.environ.get("DPGO_BENCH_SPAWNED") else
+            out.update(line)
+            out.update({"launched_by": "bench.py (built-in launcher)" if os.environ.get("DPGO_BENCH_SPAWNED") else
                                        ("torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "environment"),
                         "exchange": "RCCL ncclSend / ncclRecv of packed public-pose slabs (X and Y) enqueued by libdpgo_hip.so on "
                                     "the team stream, K iterations per host call, pull-before-use with the staleness gate in "
-                                    "the library (csrc/rank_exchange.cpp)",
-                        "exchange_timing": exchange})
+                                    "the library (csrc/rank_exchange.cpp)"})
             print(json.dumps(out))
 
 

@@ -28,7 +28,7 @@ def test_bench_multi_rank_path_runs_under_rccl_at_world_size_one():
     env = dict(os.environ, DPGO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "60", "--warmup", "10"], env=env, capture_output=True, text=True, timeout=600)
+                          "--gpus", "1", "--steps", "60", "--warmup", "10", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -46,15 +46,21 @@ def test_bench_multi_rank_path_runs_under_rccl_at_world_size_one():
     assert 0 < c2["ms_per_iter"] < 5.0 and np.isfinite(c2["relcost_after_run"]) and c2["rccl_point_to_point_ops_per_iter_this_rank"] == 0
 
 
-def test_bench_multi_rank_path_starts_without_a_launcher():
-    """no torchrun, no RANK / MASTER_ADDR in the environment: `python bench.py` with the N > 1 driver forced at world size 1"""
+def test_bench_multi_rank_path_starts_without_a_launcher(tmp_path):
+    """no torchrun, no RANK / MASTER_ADDR in the environment: `python bench.py` with the N > 1 driver forced at world size 1;
+    a plain run prints the main measurement only, and --dump-outputs gathers every agent's iterates to rank 0"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DPGO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "10"], env=env,
-                         capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "10",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
-    assert d["exchange_timing"]["rccl_world_size"] == 1 and 0 < d["value"] < 1.0
+    assert d["exchange_timing"]["rccl_world_size"] == 1 and 0 < d["value"] == d["ms_per_step"] < 1.0
+    assert "colour_parallel_plain_rtr" not in d and "asapp_ticks_tunnels" not in d
+    X, cost = np.load(str(tmp_path / "X.npy")), np.load(str(tmp_path / "cost.npy"))
+    assert X.dtype == np.float64 and X.shape == (5 * 4 * 2500,) and np.isfinite(X).all()
+    fstar = 843.5029071410438
+    assert abs((cost[0] - fstar) / fstar - d["relcost_after_run"]) <= 1e-12
 
 
 def test_bench_multi_rank_line_survives_a_stuck_extra_leg():
@@ -62,7 +68,7 @@ def test_bench_multi_rank_line_survives_a_stuck_extra_leg():
     DPGO_BENCH_EXTRAS_TIMEOUT, rank 0 still prints ONE JSON line with the library-side RCCL value and exits 0"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DPGO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", DPGO_BENCH_EXTRAS_TIMEOUT="0.2")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "10"], env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "10", "--full"], env=env,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
