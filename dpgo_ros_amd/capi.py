@@ -62,10 +62,21 @@ class Status(C.Structure):
                 ("relative_change", C.c_double)]
 
 
+class Certificate(C.Structure):
+    _fields_ = [("lambda_min", C.c_double), ("residual", C.c_double), ("norm_bound", C.c_double),
+                ("certified", C.c_int), ("iterations", C.c_int), ("block", C.c_int), ("deflated", C.c_int)]
+
+    def __repr__(self):
+        return ("Certificate(lambda_min=%.6g, residual=%.3g, norm_bound=%.6g, certified=%d, iterations=%d, block=%d, "
+                "deflated=%d)" % (self.lambda_min, self.residual, self.norm_bound, self.certified, self.iterations,
+                                  self.block, self.deflated))
+
+
 METHOD_RTR, METHOD_RGD = 0, 1
 COST_L2, COST_L1, COST_HUBER, COST_TLS, COST_GM, COST_GNC_TLS = 0, 1, 2, 3, 4, 5
 WEIGHT_LIBRARY, WEIGHT_WRAPPER = 0, 1
 OK, NOT_READY, ERR = 0, 1, -1
+CERT_NO_DEFLATION, CERT_NO_PRECONDITIONER, CERT_ETA_RELATIVE = 1, 2, 4
 PRECOND_AUTO, PRECOND_DENSE, PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL = 0, 1, 2, 3
 
 # every symbol include/dpgo_hip.h declares (checked by tests/test_abi.py)
@@ -89,7 +100,8 @@ dpgo_agent_reset_acceleration dpgo_team_prepare dpgo_agent_read_partials dpgo_ag
 dpgo_comm_unique_id dpgo_comm_create dpgo_comm_destroy dpgo_comm_rank dpgo_comm_world dpgo_comm_library
 dpgo_comm_allreduce_sum dpgo_comm_allreduce_max dpgo_team_attach_comm dpgo_team_detach_comm dpgo_team_exchange_all_ranks
 dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_iteration_log dpgo_team_run_simultaneous_ranks
-dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule""".split()
+dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
+dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point""".split()
 
 
 class DpgoError(RuntimeError):
@@ -266,6 +278,17 @@ def lift(T, num_poses, YLift, r):
     X = np.zeros(r * 4 * num_poses)
     lib().dpgo_lift(_d(np.ascontiguousarray(T)), num_poses, _d(np.ascontiguousarray(YLift)), r, _d(X))
     return X
+
+
+def escape_point(X, r, num_poses, v, alpha):
+    """staircase step (host arithmetic): the rank r+1 point [X; 0] + alpha [0; v^T], rotation blocks projected back to the
+    Stiefel manifold.  X: r x 4n in the iterate layout, v: 4n"""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    assert X.size == r * 4 * num_poses and v.size == 4 * num_poses
+    out = np.zeros((r + 1) * 4 * num_poses)
+    _chk(lib().dpgo_escape_point(_d(X), int(r), int(num_poses), _d(v), C.c_double(alpha), _d(out)), "escape_point")
+    return out
 
 
 def error_threshold_at_quantile(q, dim):
@@ -711,3 +734,93 @@ class Team:
 
     def global_X(self):
         return np.concatenate([self.agents[i].get_X() for i in self.ids])
+
+    def certificate_apply(self, V):
+        """S(X) V for a K x 4N block (K in 3..8) in the iterate layout over the team's poses in team order:
+        element (b, column 4 g + c) at [(4 g + c) K + b]"""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        V = np.ascontiguousarray(V, dtype=np.float64).reshape(-1)
+        K = V.size // (4 * N)
+        assert V.size == K * 4 * N
+        out = np.zeros_like(V)
+        _chk(lib().dpgo_team_certificate_apply(self.h, int(K), _d(V), _d(out)), "certificate_apply")
+        return out
+
+    def certify(self, eta=1e-6, tol=1e-8, max_iters=1000, block=0, deflate=True, precondition=True, eta_relative=True):
+        """smallest eigenvalue of the certificate matrix S(X) at the current iterate (LOBPCG on the device).  Returns
+        (Certificate, v): certified 1 = converged with lambda_min >= -eta, 0 = lambda_min < -eta (v, 4N doubles in team
+        order, is a direction of negative curvature), -1 = not converged.  eta is relative to the bound s on |S| unless
+        eta_relative is False; tol always is.  Changes no solver state."""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        flags = (0 if deflate else CERT_NO_DEFLATION) | (0 if precondition else CERT_NO_PRECONDITIONER) | \
+            (CERT_ETA_RELATIVE if eta_relative else 0)
+        res, v = Certificate(), np.zeros(4 * N)
+        _chk(lib().dpgo_team_certify(self.h, C.c_double(eta), C.c_double(tol), int(max_iters), int(block), flags,
+                                     C.byref(res), _d(v)), "certify")
+        return res, v
+
+
+def _params_at_rank(params, r):
+    p = Params.from_buffer_copy(params)
+    p.r = r
+    return p
+
+
+def riemannian_staircase(meas, params, r0, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None, alpha0=None,
+                         max_backtracks=30, certify_kw=None, device=0):
+    """Riemannian staircase over the team solver: run the team at rank r (`iters` iterations of dpgo_team_run, or
+    `first_iters` at r0), certify; when the point is not certified, start rank r + 1 from the escape point
+    [X; 0] + alpha [0; v^T] along the certificate's direction v, alpha halved until the cost decreases.  Stops when
+    certified or at r_max.  The start is T lifted with the fixed Stiefel matrix (dpgo_team_set_initial), or X0 (rank r0,
+    team order).  Returns dict(X=per-agent iterates, r=final rank, ranks=rank path, certificate=last Certificate,
+    costs=cost at the end of every rank, escape_costs=[(cost before, cost after)] of every escape)."""
+    certify_kw = dict(certify_kw or {})
+    r = r0
+    team = Team.from_measurements(meas, _params_at_rank(params, r), device=device)
+    try:
+        if X0 is not None:
+            X0 = np.asarray(X0, dtype=np.float64).reshape(-1)
+            ofs = 0
+            for i in team.ids:
+                n = team.agents[i].n
+                team.agents[i].set_X(X0[ofs:ofs + r * 4 * n])
+                ofs += r * 4 * n
+            team.exchange_all()
+        else:
+            team.set_initial(T, fixed_stiefel(r))
+        ranks, costs, escapes = [r], [], []
+        n_it = iters if first_iters is None else first_iters
+        while True:
+            if n_it > 0:
+                team.run(n_it)
+            n_it = iters
+            f = team.cost()
+            costs.append(f)
+            cert, v = team.certify(eta=eta, **certify_kw)
+            if cert.certified != 0 or r >= r_max:
+                Xs = [team.agents[i].get_X() for i in team.ids]
+                return dict(X=Xs, r=r, ranks=ranks, certificate=cert, costs=costs, escape_costs=escapes)
+            Xs = [team.agents[i].get_X() for i in team.ids]
+            ns = [team.agents[i].n for i in team.ids]
+            team.close()
+            team = Team.from_measurements(meas, _params_at_rank(params, r + 1), device=device)
+            offs = np.concatenate([[0], np.cumsum(ns)])
+            alpha = float(alpha0) if alpha0 is not None else np.sqrt(float(offs[-1]))
+            taken = None
+            for _ in range(max_backtracks):
+                for k, i in enumerate(team.ids):
+                    vk = v[4 * offs[k]:4 * offs[k + 1]]
+                    team.agents[i].set_X(escape_point(Xs[k], r, ns[k], vk, alpha))
+                team.exchange_all()
+                f2 = team.cost()
+                if f2 < f:
+                    taken = f2
+                    break
+                alpha *= 0.5
+            if taken is None:
+                raise DpgoError("riemannian_staircase: no step along the escape direction decreased the cost")
+            escapes.append((f, taken))
+            r += 1
+            ranks.append(r)
+    finally:
+        team.close()

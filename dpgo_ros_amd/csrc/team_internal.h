@@ -254,6 +254,10 @@ struct dpgo_team {
   size_t h_block_bytes = 0;
   dpgo::RtrState *h_states = nullptr;          // pinned, one per local agent
   dpgo_host::DevBuf<double> d_tmp;  // scratch for raw manifold ops / dense factorisation
+  // certificate workspace (certify.hip): blocks of the eigensolver, Lambda, Gram partials; never one of the solver vectors
+  dpgo_host::DevBuf<double> d_cert;
+  dpgo_host::DevBuf<int> d_cert_int;       // pose offsets of the agents, Cholesky failure word
+  dpgo_host::PinnedBuf<double> h_cert;     // the Gram matrices of one eigensolver iteration, read back with one copy
   std::vector<int> sched;
   int iter = 0;
   bool descs_dirty = true;

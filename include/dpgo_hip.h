@@ -269,6 +269,30 @@ int dpgo_team_update_weights(dpgo_team_t *t);
 /* PGOAgent::shouldTerminate() as the leader (robot 0) evaluates it from the team's statuses
  * (src/PGOAgentROS.cpp:208): 1 terminate, 0 continue, <0 error.  All robots must live in this team. */
 int dpgo_team_should_terminate(dpgo_team_t *t);
+/* global-optimality certificate (Rosen et al. 2019; the "certifiably correct" of Tian et al.): S(X) = Q - Lambda(X),
+ * Lambda = blockdiag_i [[Sym(Y_i^T (X Q)_i,rot), 0], [0, 0]]; X is a global optimum when S(X) is positive semidefinite.
+ * The smallest eigenvalue is found by LOBPCG on the device (csrc/certify.hip).  All robots must live in this team and be
+ * INITIALIZED (else DPGO_ERR with a message).  Changes no solver state. */
+typedef struct {
+  double lambda_min;   /* smallest Ritz value found (deflated: min(0, .) on Z-perp) */
+  double residual;     /* |S v - lambda v| / |v| of its Ritz vector */
+  double norm_bound;   /* the Gershgorin bound s on |S| */
+  int certified;       /* 1: converged and lambda_min >= -eta; 0: lambda_min < -eta (v: negative curvature); -1: not converged */
+  int iterations, block, deflated;
+} dpgo_certificate_t;
+/* flags of dpgo_team_certify.  Deflation (default) projects out Z = [rows of X; e_t], e_t = 1 on every translation
+ * coordinate (S Z^T = 0 at a critical point); the preconditioner is the block-Jacobi (Q_a + shift I)^-1 by agent (off when
+ * an agent has the two-level form); ETA_RELATIVE: eta is taken relative to s */
+enum { DPGO_CERT_NO_DEFLATION = 1, DPGO_CERT_NO_PRECONDITIONER = 2, DPGO_CERT_ETA_RELATIVE = 4 };
+/* S(X) V for a K x 4N block in team order (agents by offsets), K in 3..8: the operator itself, for tests */
+int dpgo_team_certificate_apply(dpgo_team_t *t, int K, const double *V, double *out);
+/* verify the current iterate; v (4N doubles, team order) or NULL.  Converged: |S v - lambda v| <= tol * s; block 0 = r.
+ * Changes no solver state. */
+int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int block, int flags,
+                      dpgo_certificate_t *out, double *v);
+/* staircase step, host arithmetic: X (r x 4n) and v (4n) -> the rank r+1 point [X; 0] + alpha [0; v^T],
+ * rotation blocks projected back to the Stiefel manifold */
+int dpgo_escape_point(const double *X, int r, int num_poses, const double *v, double alpha, double *X_out);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
