@@ -72,11 +72,22 @@ class Certificate(C.Structure):
                                   self.block, self.deflated))
 
 
+class Rounding(C.Structure):
+    _fields_ = [("f_relaxed", C.c_double), ("f_rounded", C.c_double), ("sigma", C.c_double * 8),
+                ("r", C.c_int), ("reflected", C.c_int), ("refined", C.c_int), ("num_degenerate", C.c_int)]
+
+    def __repr__(self):
+        return ("Rounding(f_relaxed=%.12g, f_rounded=%.12g, sigma=[%s], r=%d, reflected=%d, refined=%d, num_degenerate=%d)"
+                % (self.f_relaxed, self.f_rounded, ", ".join("%.6g" % x for x in self.sigma[:self.r]), self.r,
+                   self.reflected, self.refined, self.num_degenerate))
+
+
 METHOD_RTR, METHOD_RGD = 0, 1
 COST_L2, COST_L1, COST_HUBER, COST_TLS, COST_GM, COST_GNC_TLS = 0, 1, 2, 3, 4, 5
 WEIGHT_LIBRARY, WEIGHT_WRAPPER = 0, 1
 OK, NOT_READY, ERR = 0, 1, -1
 CERT_NO_DEFLATION, CERT_NO_PRECONDITIONER, CERT_ETA_RELATIVE = 1, 2, 4
+ROUND_REFINE_TRANSLATIONS = 1
 PRECOND_AUTO, PRECOND_DENSE, PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL = 0, 1, 2, 3
 
 # every symbol include/dpgo_hip.h declares (checked by tests/test_abi.py)
@@ -101,7 +112,8 @@ dpgo_comm_unique_id dpgo_comm_create dpgo_comm_destroy dpgo_comm_rank dpgo_comm_
 dpgo_comm_allreduce_sum dpgo_comm_allreduce_max dpgo_team_attach_comm dpgo_team_detach_comm dpgo_team_exchange_all_ranks
 dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_iteration_log dpgo_team_run_simultaneous_ranks
 dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
-dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point""".split()
+dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
+dpgo_translations_given_rotations""".split()
 
 
 class DpgoError(RuntimeError):
@@ -266,6 +278,16 @@ def chordal_init(m, num_poses, device=0):
     T = np.zeros(12 * num_poses)
     _chk(lib().dpgo_chordal_init(device, _d(np.ascontiguousarray(m)), len(m), num_poses, _d(T)), "chordal_init")
     return T
+
+
+def translations_given_rotations(m, num_poses, T, device=0):
+    """the translations minimising sum_e w_e tau_e |t_j - t_i - R_i t~_e|^2 with t_0 = 0 for the rotations of T (12 doubles
+    per pose, single-robot numbering): a copy of T with its translations replaced"""
+    out = np.array(T, dtype=np.float64).reshape(-1)
+    assert out.size == 12 * num_poses
+    _chk(lib().dpgo_translations_given_rotations(device, _d(np.ascontiguousarray(m)), len(m), int(num_poses), _d(out)),
+         "translations_given_rotations")
+    return out
 
 
 def fixed_stiefel(r):
@@ -759,6 +781,16 @@ class Team:
                                      C.byref(res), _d(v)), "certify")
         return res, v
 
+    def round(self, refine_translations=True):
+        """SE-Sync rounding of the current iterate: (Rounding, T) with T flat, 12 doubles per pose in team order (the layout
+        of chordal_init), anchored at the first pose.  refine_translations: the translations re-solved for the rounded
+        rotations with the team's measurements and current weights.  Changes no solver state."""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        res, T = Rounding(), np.zeros(12 * N)
+        flags = ROUND_REFINE_TRANSLATIONS if refine_translations else 0
+        _chk(lib().dpgo_team_round(self.h, flags, _d(T), C.byref(res)), "round")
+        return res, T
+
 
 def _params_at_rank(params, r):
     p = Params.from_buffer_copy(params)
@@ -774,6 +806,12 @@ def riemannian_staircase(meas, params, r0, r_max=8, eta=1e-6, T=None, X0=None, i
     certified or at r_max.  The start is T lifted with the fixed Stiefel matrix (dpgo_team_set_initial), or X0 (rank r0,
     team order).  Returns dict(X=per-agent iterates, r=final rank, ranks=rank path, certificate=last Certificate,
     costs=cost at the end of every rank, escape_costs=[(cost before, cost after)] of every escape)."""
+    return _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, max_backtracks, certify_kw, device)
+
+
+def _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, max_backtracks, certify_kw, device,
+               on_final=None):
+    """the staircase loop; on_final(team, out) runs on the final team before it is closed and may add to `out`"""
     certify_kw = dict(certify_kw or {})
     r = r0
     team = Team.from_measurements(meas, _params_at_rank(params, r), device=device)
@@ -799,7 +837,10 @@ def riemannian_staircase(meas, params, r0, r_max=8, eta=1e-6, T=None, X0=None, i
             cert, v = team.certify(eta=eta, **certify_kw)
             if cert.certified != 0 or r >= r_max:
                 Xs = [team.agents[i].get_X() for i in team.ids]
-                return dict(X=Xs, r=r, ranks=ranks, certificate=cert, costs=costs, escape_costs=escapes)
+                out = dict(X=Xs, r=r, ranks=ranks, certificate=cert, costs=costs, escape_costs=escapes)
+                if on_final is not None:
+                    on_final(team, out)
+                return out
             Xs = [team.agents[i].get_X() for i in team.ids]
             ns = [team.agents[i].n for i in team.ids]
             team.close()
@@ -824,3 +865,21 @@ def riemannian_staircase(meas, params, r0, r_max=8, eta=1e-6, T=None, X0=None, i
             ranks.append(r)
     finally:
         team.close()
+
+
+def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None,
+                    refine_translations=True, certify_kw=None, device=0):
+    """End to end: the Riemannian staircase, then the SE-Sync rounding of its final point (Team.round on the final team).
+    Returns dict(T=trajectory, 12 doubles per pose in team order anchored at the first pose, r=final rank, ranks,
+    certificate, rounding=Rounding, f_relaxed, f_rounded, gap_rel, escape_costs).  gap_rel = (f_rounded - f_relaxed) /
+    f_relaxed bounds the relative suboptimality of T (up to the certificate's eta) when the point is certified; it is None
+    otherwise."""
+    def round_final(team, out):
+        out["rounding"], out["T"] = team.round(refine_translations=refine_translations)
+
+    out = _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, None, 30, certify_kw, device,
+                     on_final=round_final)
+    rd, cert = out["rounding"], out["certificate"]
+    gap = (rd.f_rounded - rd.f_relaxed) / rd.f_relaxed if cert.certified == 1 else None
+    return dict(T=out["T"], r=out["r"], ranks=out["ranks"], certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed,
+                f_rounded=rd.f_rounded, gap_rel=gap, escape_costs=out["escape_costs"])

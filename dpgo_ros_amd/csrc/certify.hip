@@ -13,8 +13,7 @@
 // Every reduction is a Gram matrix A^T B: fixed column chunks per workgroup, one partial per chunk, summed in chunk
 // order by ONE workgroup of a second launch -- two calls on the same inputs give the same bits.
 // Nothing here writes a solver vector, a slab, a counter or a Nesterov state: the workspace is the team's d_cert.
-#include "kernel_common.h"
-#include "team_internal.h"
+#include "certify_internal.h"
 
 namespace dpgo {
 
@@ -121,9 +120,6 @@ __global__ __launch_bounds__(256) void k_cert_lambda(const AgentDev *__restrict_
   if (threadIdx.x == 0) gmax[(size_t)ai * gstride + blockIdx.x] = red[0];
 }
 
-constexpr int CG_CH = 128;   // columns per workgroup of a Gram launch
-constexpr int CG_MAXK = 24;  // most rows of either operand (the 3K-row basis at K = 8)
-
 // partial Gram matrices: part[blk][p * kb + q] = sum over the block's columns of A[p] B[q]
 __global__ __launch_bounds__(256) void k_cert_gram(const double *__restrict__ A, int lda, int ka, const double *__restrict__ B,
                                                    int ldb, int kb, int ncols, double *__restrict__ part) {
@@ -156,18 +152,7 @@ __global__ __launch_bounds__(256) void k_cert_gram_sum(const double *__restrict_
   }
 }
 
-// OUT = beta OUT + sum_t s_t A_t C_t, one thread per element (column, q).  C_t row-major k_t x ko on the device (null:
-// the identity, k_t = ko).  No A_t may alias OUT.
-struct CertTerm {
-  const double *A;
-  const double *C;
-  int lda, ka;
-  double s;
-};
-struct CertTerms {
-  CertTerm t[3];
-  int n;
-};
+// OUT = beta OUT + sum_t s_t A_t C_t (CertTerm: certify_internal.h)
 __global__ __launch_bounds__(256) void k_cert_update(double *__restrict__ out, int ldo, int ko, double beta, CertTerms tm, int ncols) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (size_t)ncols * ko) return;
@@ -280,11 +265,10 @@ __global__ __launch_bounds__(256) void k_cert_precond(const AgentDev *__restrict
 // host side
 using namespace dpgo;
 using namespace dpgo_host;
+using namespace dpgo_cert;
 
-namespace {
+namespace dpgo_cert {
 
-// cyclic Jacobi eigendecomposition of a symmetric n x n matrix (row-major): ascending eigenvalues w, eigenvectors as the
-// columns of V (row-major, V[i * n + k] = component i of vector k)
 void jacobi_eig(int n, std::vector<double> A, std::vector<double> &w, std::vector<double> &V) {
   V.assign((size_t)n * n, 0.0);
   for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
@@ -334,99 +318,85 @@ void jacobi_eig(int n, std::vector<double> A, std::vector<double> &w, std::vecto
   V.swap(V2);
 }
 
-// the certificate's device state for one call
-struct Cert {
-  dpgo_team_t *t = nullptr;
-  int r = 0, K = 0, na = 0, N = 0, L = 0, max_n = 0, nz = 0;  // nz: rows of the orthonormal deflation basis Zo
-  bool deflate = true, precond = true;
-  double *Xt = nullptr, *E = nullptr, *lam = nullptr, *Zr = nullptr, *Zo = nullptr;
-  double *U[2] = {nullptr, nullptr}, *AU[2] = {nullptr, nullptr}, *T = nullptr, *T2 = nullptr;
-  double *part = nullptr, *G = nullptr, *gmax = nullptr;
-  int *off = nullptr;
-  int gstride = 0, nblk = 0;
-  static constexpr int SLOT = CG_MAXK * CG_MAXK;
-  // Gram slots: 0 basis x operator, 1 basis x basis, 2 residual x residual, 3 Cholesky failure word (read back together),
-  // 4 X^T S X, 5 deflation products, 6 Cholesky coefficients, 7 coefficients from the host
-  double *slot(int k) const { return G + (size_t)k * SLOT; }
-
-  int setup(int K_) {
-    K = K_;
-    r = t->prm.r;
-    na = (int)t->ag.size();
-    std::vector<int> offs(na + 1, 0);
-    max_n = 0;
-    for (int k = 0; k < na; ++k) {
-      offs[k + 1] = offs[k] + t->ag[k]->n;
-      max_n = std::max(max_n, t->ag[k]->n);
-    }
-    N = offs[na];
-    L = 4 * N;
-    nblk = (L + CG_CH - 1) / CG_CH;
-    gstride = (max_n + 255) / 256;
-    const size_t Ls = (size_t)L;
-    const size_t need = 2 * r * Ls + 9 * (size_t)N + 2 * (r + 1) * Ls + 4 * 3 * (size_t)K * Ls + 2 * (size_t)K * Ls +
-                        (size_t)nblk * SLOT + 8 * (size_t)SLOT + (size_t)na * gstride;
-    if (t->d_cert.alloc(need) || t->d_cert_int.alloc(na + 1) || t->h_cert.alloc(5 * SLOT + (size_t)K * L)) {
-      set_err("certificate: workspace allocation failed");
-      return DPGO_ERR;
-    }
-    double *p = t->d_cert.p;
-    auto take = [&](size_t n) { double *q = p; p += n; return q; };
-    Xt = take(r * Ls); E = take(r * Ls); lam = take(9 * (size_t)N);
-    Zr = take((r + 1) * Ls); Zo = take((r + 1) * Ls);
-    for (int b = 0; b < 2; ++b) { U[b] = take(3 * K * Ls); AU[b] = take(3 * K * Ls); }
-    T = take(K * Ls); T2 = take(K * Ls);
-    part = take((size_t)nblk * SLOT); G = take(8 * (size_t)SLOT); gmax = take((size_t)na * gstride);
-    off = t->d_cert_int.p;
-    HIPC(hipMemcpyAsync(off, offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, t->stream));
-    HIPC(hipMemsetAsync(G, 0, sizeof(double) * 8 * SLOT, t->stream));
-    // the team's iterate, gathered in team order (agent arrays are r x 4n each: ld r)
-    for (int k = 0; k < na; ++k)
-      HIPC(hipMemcpyAsync(Xt + (size_t)4 * offs[k] * r, t->ag[k]->dev.buf[B_X], sizeof(double) * r * 4 * t->ag[k]->n,
-                          hipMemcpyDeviceToDevice, t->stream));
-    apply(r, Xt, r, E, r, false);
-    DPGO_DISPATCH_R(r, (k_cert_lambda<R><<<dim3(gstride, na), 256, 0, t->stream>>>(t->d_agents.p, off, Xt, E, lam, gmax, gstride)));
-    HIPC(hipGetLastError());
-    return 0;
+int Cert::setup(int K_) {
+  K = K_;
+  r = t->prm.r;
+  na = (int)t->ag.size();
+  std::vector<int> offs(na + 1, 0);
+  max_n = 0;
+  for (int k = 0; k < na; ++k) {
+    offs[k + 1] = offs[k] + t->ag[k]->n;
+    max_n = std::max(max_n, t->ag[k]->n);
   }
-
-  void apply(int k, const double *V, int ldv, double *out, int ldo, bool with_lam) {
-    const dim3 grid(spmm_grid(k, max_n), na);
-    const double *lm = with_lam ? lam : nullptr;
-    DPGO_DISPATCH_R(k, (k_cert_apply<R><<<grid, 64, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo, lm)));
+  N = offs[na];
+  L = 4 * N;
+  nblk = (L + CG_CH - 1) / CG_CH;
+  gstride = (max_n + 255) / 256;
+  const size_t Ls = (size_t)L;
+  const size_t need = 2 * r * Ls + 9 * (size_t)N + 2 * (r + 1) * Ls + 4 * 3 * (size_t)K * Ls + 2 * (size_t)K * Ls +
+                      (size_t)nblk * SLOT + 8 * (size_t)SLOT + (size_t)na * gstride;
+  if (t->d_cert.alloc(need) || t->d_cert_int.alloc(na + 1) || t->h_cert.alloc(5 * SLOT + (size_t)K * L)) {
+    set_err("certificate: workspace allocation failed");
+    return DPGO_ERR;
   }
+  double *p = t->d_cert.p;
+  auto take = [&](size_t n) { double *q = p; p += n; return q; };
+  Xt = take(r * Ls); E = take(r * Ls); lam = take(9 * (size_t)N);
+  Zr = take((r + 1) * Ls); Zo = take((r + 1) * Ls);
+  for (int b = 0; b < 2; ++b) { U[b] = take(3 * K * Ls); AU[b] = take(3 * K * Ls); }
+  T = take(K * Ls); T2 = take(K * Ls);
+  part = take((size_t)nblk * SLOT); G = take(8 * (size_t)SLOT); gmax = take((size_t)na * gstride);
+  off = t->d_cert_int.p;
+  HIPC(hipMemcpyAsync(off, offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, t->stream));
+  HIPC(hipMemsetAsync(G, 0, sizeof(double) * 8 * SLOT, t->stream));
+  // the team's iterate, gathered in team order (agent arrays are r x 4n each: ld r)
+  for (int k = 0; k < na; ++k)
+    HIPC(hipMemcpyAsync(Xt + (size_t)4 * offs[k] * r, t->ag[k]->dev.buf[B_X], sizeof(double) * r * 4 * t->ag[k]->n,
+                        hipMemcpyDeviceToDevice, t->stream));
+  apply(r, Xt, r, E, r, false);
+  DPGO_DISPATCH_R(r, (k_cert_lambda<R><<<dim3(gstride, na), 256, 0, t->stream>>>(t->d_agents.p, off, Xt, E, lam, gmax, gstride)));
+  HIPC(hipGetLastError());
+  return 0;
+}
 
-  void gram(const double *A, int lda, int ka, const double *B, int ldb, int kb, double *out) {
-    k_cert_gram<<<nblk, 256, 0, t->stream>>>(A, lda, ka, B, ldb, kb, L, part);
-    k_cert_gram_sum<<<1, 256, 0, t->stream>>>(part, nblk, ka * kb, out);
-  }
+void Cert::apply(int k, const double *V, int ldv, double *out, int ldo, bool with_lam) {
+  const dim3 grid(spmm_grid(k, max_n), na);
+  const double *lm = with_lam ? lam : nullptr;
+  DPGO_DISPATCH_R(k, (k_cert_apply<R><<<grid, 64, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo, lm)));
+}
 
-  void update(double *out, int ldo, int ko, double beta, std::initializer_list<CertTerm> terms) {
-    CertTerms tm{};
-    for (const CertTerm &x : terms) tm.t[tm.n++] = x;
-    const size_t cnt = (size_t)L * ko;
-    k_cert_update<<<(unsigned)((cnt + 255) / 256), 256, 0, t->stream>>>(out, ldo, ko, beta, tm, L);
-  }
+void Cert::gram(const double *A, int lda, int ka, const double *B, int ldb, int kb, double *out) {
+  k_cert_gram<<<nblk, 256, 0, t->stream>>>(A, lda, ka, B, ldb, kb, L, part);
+  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(part, nblk, ka * kb, out);
+}
 
-  // V <- V - Zo^T (Zo V^T): onto the complement of the deflation basis
-  void project(double *V, int ld, int k) {
-    if (!deflate) return;
-    gram(Zo, nz, nz, V, ld, k, slot(5));
-    update(V, ld, k, 1.0, {CertTerm{Zo, slot(5), nz, nz, -1.0}});
-  }
+void Cert::sum_partials(const double *p, int nblk_, int m, double *out) {
+  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(p, nblk_, m, out);
+}
 
-  // rows of V orthonormal: V <- L^-1 V (CholQR) through scratch S (k rows, ld k)
-  void cholqr(double *V, int ld, int k, double *S) {
-    gram(V, ld, k, V, ld, k, slot(4));
-    k_cert_chol<<<1, 64, 0, t->stream>>>(slot(4), k, slot(6), slot(3));
-    update(S, k, k, 0.0, {CertTerm{V, slot(6), ld, k, 1.0}});
-    update(V, ld, k, 0.0, {CertTerm{S, nullptr, k, k, 1.0}});
-  }
+void Cert::update(double *out, int ldo, int ko, double beta, std::initializer_list<CertTerm> terms) {
+  CertTerms tm{};
+  for (const CertTerm &x : terms) tm.t[tm.n++] = x;
+  const size_t cnt = (size_t)L * ko;
+  k_cert_update<<<(unsigned)((cnt + 255) / 256), 256, 0, t->stream>>>(out, ldo, ko, beta, tm, L);
+}
 
-  void precondition(const double *V, int ldv, double *out, int ldo) {
-    DPGO_DISPATCH_R(K, (k_cert_precond<R><<<dim3(4 * max_n, na), 256, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo)));
-  }
-};
+void Cert::project(double *V, int ld, int k) {
+  if (!deflate) return;
+  gram(Zo, nz, nz, V, ld, k, slot(5));
+  update(V, ld, k, 1.0, {CertTerm{Zo, slot(5), nz, nz, -1.0}});
+}
+
+void Cert::cholqr(double *V, int ld, int k, double *S) {
+  gram(V, ld, k, V, ld, k, slot(4));
+  k_cert_chol<<<1, 64, 0, t->stream>>>(slot(4), k, slot(6), slot(3));
+  update(S, k, k, 0.0, {CertTerm{V, slot(6), ld, k, 1.0}});
+  update(V, ld, k, 0.0, {CertTerm{S, nullptr, k, k, 1.0}});
+}
+
+void Cert::precondition(const double *V, int ldv, double *out, int ldo) {
+  DPGO_DISPATCH_R(K, (k_cert_precond<R><<<dim3(4 * max_n, na), 256, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo)));
+}
 
 int check_team(dpgo_team_t *t, const char *what) {
   if ((int)t->ag.size() != t->prm.num_robots) {
@@ -448,7 +418,7 @@ int check_team(dpgo_team_t *t, const char *what) {
   return 0;
 }
 
-}  // namespace
+}  // namespace dpgo_cert
 
 extern "C" {
 

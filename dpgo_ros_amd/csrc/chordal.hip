@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <vector>
 
@@ -91,6 +92,7 @@ __global__ void k_project_so3(double *Rm, int n) {
 }  // namespace dpgo
 
 using namespace dpgo;
+using dpgo_host::set_err;
 
 namespace {
 
@@ -189,7 +191,11 @@ bool has_parallel_edges(const dpgo_measurement_t *m, int nm, int n) {
 // ~80 block steps in batched launches where the dense Cholesky of the 7500^2 system walks 312 --, applied with one launch.
 // One step of iterative refinement (residual through the sparse operator) brings the explicit-inverse form to the
 // accuracy of a triangular solve.  DPGO_CHORDAL_DENSE=1 keeps the dense path above.
-static int chordal_via_team(int device, const dpgo_measurement_t *m, int nm, int n, double *T) {
+namespace {
+
+// the relaxation's team: every translation measurement set to zero, pose 0 handed to a second "robot" (the pin), X = 0,
+// data matrices and Q^-1 built.  nullptr on failure.
+dpgo_team_t *relax_team(int device, const dpgo_measurement_t *m, int nm, int n, const std::function<void(const char *)> &lap) {
   const int r = 3, n1 = n - 1;
   std::vector<dpgo_measurement_t> mm;
   mm.reserve(nm);
@@ -205,29 +211,12 @@ static int chordal_via_team(int device, const dpgo_measurement_t *m, int nm, int
   dpgo_default_params(&p, r, 2);
   p.precond_shift = 0.0;
   const int id0 = 0;
-  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
-  auto tq = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "chordal: %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tq).count());
-    tq = now;
-  };
   dpgo_team_t *t = dpgo_team_create(device, &p, 1, &id0, nullptr);
-  if (!t) return DPGO_ERR;
+  if (!t) return nullptr;
   t->tl_max_sub = 200;  // (a fixed dissection: the search for the cheapest apply costs more than this whole relaxation)
   lap("team_create");
-  int rc = DPGO_ERR;
-  const size_t len = (size_t)r * 4 * n1;
-  std::vector<double> Z(len), V(len, 0.0), G(len), W(len), zero(len, 0.0);
-  auto solve = [&](std::vector<double> &rhs, std::vector<double> &out) -> int {  // out = rhs Q^-1, refined once
-    if (dpgo_agent_precondition(t, 0, zero.data(), rhs.data(), out.data())) return -1;
-    if (dpgo_agent_hessvec(t, 0, zero.data(), out.data(), W.data())) return -1;   // (at X = 0: W = out Q)
-    for (size_t i = 0; i < len; ++i) W[i] = rhs[i] - W[i];
-    if (dpgo_agent_precondition(t, 0, zero.data(), W.data(), G.data())) return -1;
-    for (size_t i = 0; i < len; ++i) out[i] += G[i];
-    return 0;
-  };
+  const std::vector<double> zero((size_t)r * 4 * n1, 0.0);
+  bool ok = false;
   do {
     if (dpgo_agent_add_measurements(t, 0, mm.data(), (int)mm.size()) < 0) break;
     if (dpgo_agent_num_poses(t, 0) != n1) break;  // (a pose no edge reaches: the dense path reports it as a failed pivot)
@@ -238,10 +227,99 @@ static int chordal_via_team(int device, const dpgo_measurement_t *m, int nm, int
     if (dpgo_agent_set_X(t, 0, zero.data())) break;
     lap("set_X (structure, Q, Q^-1)");
     if (dpgo_agent_build_problem(t, 0, 0)) break;
+    ok = true;
+  } while (false);
+  if (!ok) {
+    dpgo_team_destroy(t);
+    return nullptr;
+  }
+  return t;
+}
+
+// out = rhs Q^-1 through the relaxation's team, refined once (W, G: scratch of the same length)
+int relax_solve(dpgo_team_t *t, const std::vector<double> &zero, const std::vector<double> &rhs, std::vector<double> &out,
+                std::vector<double> &W, std::vector<double> &G) {
+  const size_t len = rhs.size();
+  if (dpgo_agent_precondition(t, 0, zero.data(), rhs.data(), out.data())) return -1;
+  if (dpgo_agent_hessvec(t, 0, zero.data(), out.data(), W.data())) return -1;   // (at X = 0: W = out Q)
+  for (size_t i = 0; i < len; ++i) W[i] = rhs[i] - W[i];
+  if (dpgo_agent_precondition(t, 0, zero.data(), W.data(), G.data())) return -1;
+  for (size_t i = 0; i < len; ++i) out[i] += G[i];
+  return 0;
+}
+
+// stage 2 through the relaxation's team: minimise sum tau |t_j - t_i - R_i t~|^2, t_0 = 0, for the rotations in T --
+// right-hand side on the translation entries (V, Z, W, G: scratch of 12 (n - 1) doubles)
+int translations_through_team(dpgo_team_t *t, const dpgo_measurement_t *m, int nm, int n, double *T, std::vector<double> &V,
+                              std::vector<double> &Z, std::vector<double> &W, std::vector<double> &G,
+                              const std::vector<double> &zero) {
+  std::fill(V.begin(), V.end(), 0.0);
+  for (int e = 0; e < nm; ++e) {
+    const int i = m[e].p1, j = m[e].p2;
+    if (i == j) continue;
+    const double tau = m[e].weight * m[e].tau;
+    const double *Ri = T + (size_t)12 * i;
+    for (int a = 0; a < 3; ++a) {
+      double v = 0;
+      for (int b = 0; b < 3; ++b) v += Ri[3 * b + a] * m[e].t[b];
+      if (i != 0) V[((size_t)4 * (i - 1) + 3) * 3 + a] -= tau * v;
+      if (j != 0) V[((size_t)4 * (j - 1) + 3) * 3 + a] += tau * v;
+    }
+  }
+  if (relax_solve(t, zero, V, Z, W, G)) return DPGO_ERR;
+  for (int a = 0; a < 3; ++a) T[9 + a] = 0.0;
+  for (int i = 1; i < n; ++i) for (int a = 0; a < 3; ++a) T[(size_t)12 * i + 9 + a] = Z[((size_t)4 * (i - 1) + 3) * 3 + a];
+  return DPGO_OK;
+}
+
+// stage 2 of the dense path: the scalar graph Laplacian with t_0 = 0 pinned by a Dirichlet row
+int dense_translations(hipStream_t s, const dpgo_measurement_t *m, int nm, int n, bool dup, double *T) {
+  Assembler A(n, dup);
+  std::vector<double> B((size_t)3 * n, 0.0);
+  A.add(0, 0, 1.0);
+  for (int e = 0; e < nm; ++e) {
+    const int i = m[e].p1, j = m[e].p2;
+    const double tau = m[e].weight * m[e].tau;
+    const double *Ri = T + (size_t)12 * i;
+    double v[3];
+    for (int a = 0; a < 3; ++a) { v[a] = 0; for (int b = 0; b < 3; ++b) v[a] += Ri[3 * b + a] * m[e].t[b]; }
+    if (i != 0) { A.add(i, i, tau); for (int a = 0; a < 3; ++a) B[(size_t)i * 3 + a] -= tau * v[a]; }
+    if (j != 0) { A.add(j, j, tau); for (int a = 0; a < 3; ++a) B[(size_t)j * 3 + a] += tau * v[a]; }
+    if (i != 0 && j != 0) { A.add(i, j, -tau); A.add(j, i, -tau); }
+  }
+  std::vector<double> X;
+  if (dense_solve<3>(s, A.triplets(), n, B, X) != 0) return DPGO_ERR;
+  for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) T[(size_t)12 * i + 9 + a] = X[(size_t)i * 3 + a];
+  return DPGO_OK;
+}
+
+bool dense_only() {
+  static const bool d = std::getenv("DPGO_CHORDAL_DENSE") && std::getenv("DPGO_CHORDAL_DENSE")[0] == '1';
+  return d;
+}
+
+}  // namespace
+
+static int chordal_via_team(int device, const dpgo_measurement_t *m, int nm, int n, double *T) {
+  const int r = 3, n1 = n - 1;
+  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+  auto tq = std::chrono::steady_clock::now();
+  auto lap = [&](const char *what) {
+    if (!timing) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "chordal: %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tq).count());
+    tq = now;
+  };
+  dpgo_team_t *t = relax_team(device, m, nm, n, lap);
+  if (!t) return DPGO_ERR;
+  int rc = DPGO_ERR;
+  const size_t len = (size_t)r * 4 * n1;
+  std::vector<double> Z(len), V(len, 0.0), G(len), W(len), zero(len, 0.0);
+  do {
     if (dpgo_agent_get_G(t, 0, G.data())) break;
     for (size_t i = 0; i < len; ++i) V[i] = -G[i];
     lap("G");
-    if (solve(V, Z)) break;
+    if (relax_solve(t, zero, V, Z, W, G)) break;
     lap("rotation solve");
     // rotations: pose 0 = I, pose i = the 3 x 3 block of Z (column c of the block = column c of R_i), projected to SO(3)
     std::vector<double> R((size_t)9 * n);
@@ -258,28 +336,24 @@ static int chordal_via_team(int device, const dpgo_measurement_t *m, int nm, int
     }
     std::memset(T, 0, sizeof(double) * 12 * (size_t)n);
     for (int i = 0; i < n; ++i) std::memcpy(T + (size_t)12 * i, R.data() + (size_t)9 * i, sizeof(double) * 9);
-    // translations: minimise sum tau |t_j - t_i - R_i t~|^2, t_0 = 0 -- right-hand side on the translation entries
-    std::fill(V.begin(), V.end(), 0.0);
-    for (int e = 0; e < nm; ++e) {
-      const int i = m[e].p1, j = m[e].p2;
-      if (i == j) continue;
-      const double tau = m[e].weight * m[e].tau;
-      const double *Ri = T + (size_t)12 * i;
-      for (int a = 0; a < 3; ++a) {
-        double v = 0;
-        for (int b = 0; b < 3; ++b) v += Ri[3 * b + a] * m[e].t[b];
-        if (i != 0) V[((size_t)4 * (i - 1) + 3) * 3 + a] -= tau * v;
-        if (j != 0) V[((size_t)4 * (j - 1) + 3) * 3 + a] += tau * v;
-      }
-    }
-    lap("projection + rhs");
-    if (solve(V, Z)) break;
+    lap("projection");
+    if (translations_through_team(t, m, nm, n, T, V, Z, W, G, zero)) break;
     lap("translation solve");
-    for (int i = 1; i < n; ++i) for (int a = 0; a < 3; ++a) T[(size_t)12 * i + 9 + a] = Z[((size_t)4 * (i - 1) + 3) * 3 + a];
     rc = DPGO_OK;
   } while (false);
   dpgo_team_destroy(t);
   lap("team_destroy");
+  return rc;
+}
+
+// dpgo_translations_given_rotations through the relaxation's team (the rotation rows of its Q are built and left unused)
+static int translations_via_team(int device, const dpgo_measurement_t *m, int nm, int n, double *T) {
+  dpgo_team_t *t = relax_team(device, m, nm, n, [](const char *) {});
+  if (!t) return DPGO_ERR;
+  const size_t len = (size_t)3 * 4 * (n - 1);
+  std::vector<double> Z(len), V(len, 0.0), G(len), W(len), zero(len, 0.0);
+  const int rc = translations_through_team(t, m, nm, n, T, V, Z, W, G, zero);
+  dpgo_team_destroy(t);
   return rc;
 }
 
@@ -290,9 +364,8 @@ extern "C" int dpgo_chordal_init(int device, const dpgo_measurement_t *m, int nm
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipSetDevice(device) != hipSuccess) return DPGO_ERR;
   {
-    static const bool dense_only = std::getenv("DPGO_CHORDAL_DENSE") && std::getenv("DPGO_CHORDAL_DENSE")[0] == '1';
     // (needs at least one edge into pose 0 -- the pin is a shared edge -- and falls back to the dense path on any failure)
-    if (!dense_only && num_poses >= 2 && num_poses <= DPGO_MAX_POSE_INDEX && chordal_via_team(device, m, nm, num_poses, T) == DPGO_OK)
+    if (!dense_only() && num_poses >= 2 && num_poses <= DPGO_MAX_POSE_INDEX && chordal_via_team(device, m, nm, num_poses, T) == DPGO_OK)
       return DPGO_OK;
   }
   hipStream_t s;
@@ -340,25 +413,42 @@ extern "C" int dpgo_chordal_init(int device, const dpgo_measurement_t *m, int nm
       }
     }
   }
-  if (rc == DPGO_OK) {
-    // ---- stage 2: translations, t_0 = 0
-    Assembler A(n, dup);
-    std::vector<double> B((size_t)3 * n, 0.0);
-    A.add(0, 0, 1.0);
-    for (int e = 0; e < nm; ++e) {
-      const int i = m[e].p1, j = m[e].p2;
-      const double tau = m[e].weight * m[e].tau;
-      const double *Ri = T + (size_t)12 * i;
-      double v[3];
-      for (int a = 0; a < 3; ++a) { v[a] = 0; for (int b = 0; b < 3; ++b) v[a] += Ri[3 * b + a] * m[e].t[b]; }
-      if (i != 0) { A.add(i, i, tau); for (int a = 0; a < 3; ++a) B[(size_t)i * 3 + a] -= tau * v[a]; }
-      if (j != 0) { A.add(j, j, tau); for (int a = 0; a < 3; ++a) B[(size_t)j * 3 + a] += tau * v[a]; }
-      if (i != 0 && j != 0) { A.add(i, j, -tau); A.add(j, i, -tau); }
-    }
-    std::vector<double> X;
-    if (dense_solve<3>(s, A.triplets(), n, B, X) != 0) rc = DPGO_ERR;
-    else for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) T[(size_t)12 * i + 9 + a] = X[(size_t)i * 3 + a];
-  }
+  if (rc == DPGO_OK) rc = dense_translations(s, m, nm, n, dup, T);  // ---- stage 2: translations, t_0 = 0
   (void)hipStreamDestroy(s);
+  return rc;
+}
+
+extern "C" int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, int nm, int num_poses, double *T) {
+  if (!m || nm < 0 || num_poses <= 0 || !T) { set_err("translations_given_rotations: null argument"); return DPGO_ERR; }
+  const int n = num_poses;
+  // every endpoint inside [0, n); every pose joined to pose 0 by edges of positive weight (else the Laplacian is singular)
+  std::vector<int> parent(n);
+  for (int i = 0; i < n; ++i) parent[i] = i;
+  auto root = [&](int i) { while (parent[i] != i) i = parent[i] = parent[parent[i]]; return i; };
+  for (int e = 0; e < nm; ++e) {
+    if (m[e].p1 < 0 || m[e].p1 >= n || m[e].p2 < 0 || m[e].p2 >= n) {
+      set_err("translations_given_rotations: measurement " + std::to_string(e) + " has an end point outside [0, num_poses)");
+      return DPGO_ERR;
+    }
+    if (m[e].weight * m[e].tau > 0.0) parent[root(m[e].p1)] = root(m[e].p2);
+  }
+  for (int i = 0; i < n; ++i)
+    if (root(i) != root(0)) {
+      set_err("translations_given_rotations: pose " + std::to_string(i) + " is not joined to pose 0 by edges of positive "
+              "weight (the weighted graph is disconnected: singular Laplacian)");
+      return DPGO_ERR;
+    }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipSetDevice(device) != hipSuccess) {
+    set_err("translations_given_rotations: no usable HIP device");
+    return DPGO_ERR;
+  }
+  // the same two paths as dpgo_chordal_init, in the same cases
+  if (!dense_only() && n >= 2 && n <= DPGO_MAX_POSE_INDEX && translations_via_team(device, m, nm, n, T) == DPGO_OK) return DPGO_OK;
+  hipStream_t s;
+  if (hipStreamCreate(&s) != hipSuccess) { set_err("translations_given_rotations: hipStreamCreate failed"); return DPGO_ERR; }
+  const int rc = dense_translations(s, m, nm, n, has_parallel_edges(m, nm, n), T);
+  (void)hipStreamDestroy(s);
+  if (rc != DPGO_OK) set_err("translations_given_rotations: the dense solve failed (singular Laplacian)");
   return rc;
 }

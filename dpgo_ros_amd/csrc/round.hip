@@ -1,0 +1,399 @@
+// round.hip -- SE-Sync rounding of a team's iterate (Rosen et al. 2019, Alg. 2) and the suboptimality gap it bounds.
+//
+// X (r x 4N, team order) -> T (3 x 4N: R_i, t_i):  U = the top-3 left singular vectors of the rotation block Y (r x 3N), the
+// eigenvectors of the r x r Gram matrix Y Y^T;  D = diag(1, 1, -1) when more poses have det(U^T Y_i) < 0 than > 0, else I;
+// R_i = the nearest rotation to D U^T Y_i,  t_i = D U^T p_i;  then every pose relative to the first:  T_i <- T_0^-1 T_i.
+// f_relaxed = 1/2 <X, X Q>, f_rounded = 1/2 <T, T Q> with the certificate's operator (Lambda off) and its fixed-order Gram:
+// T in the library's 12-doubles-per-pose layout (R column-major, then t) IS a K = 3 block of the iterate layout.
+//
+// One lane per pose, no atomics: every sum is a wave reduction in a fixed order into one partial per workgroup, the
+// partials summed in workgroup order -- two calls give the same bits.  The workspace is the team's certificate workspace
+// (d_cert): nothing here writes a solver vector.
+#include "certify_internal.h"
+#include "device_math.h"
+
+namespace dpgo {
+
+constexpr int RD_WG = 64;  // poses per workgroup of the rounding kernels (one wave)
+
+// sum over the 64 lanes of the wave in a fixed order; lane 0 holds it
+__device__ __forceinline__ double rd_wave_sum(double s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  return s;
+}
+
+// partial R x R Gram matrices of the rotation columns: part[blk * R * R + p * R + q] = sum over the workgroup's poses of
+// sum_c Y_i[p][c] Y_i[q][c]
+template <int R>
+__global__ __launch_bounds__(RD_WG) void k_round_gram(const double *__restrict__ X, int N, double *__restrict__ part) {
+  const int g = blockIdx.x * RD_WG + threadIdx.x;
+  double y[3][R];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int a = 0; a < R; ++a) y[c][a] = (g < N) ? X[((size_t)4 * g + c) * R + a] : 0.0;
+  double *out = part + (size_t)blockIdx.x * R * R;
+#pragma unroll
+  for (int p = 0; p < R; ++p)
+#pragma unroll
+    for (int q = 0; q <= p; ++q) {
+      const double s = rd_wave_sum(y[0][p] * y[0][q] + y[1][p] * y[1][q] + y[2][p] * y[2][q]);
+      if (threadIdx.x == 0) {
+        out[p * R + q] = s;
+        out[q * R + p] = s;
+      }
+    }
+}
+
+// B = U^T [Y_i | p_i] (3 x 4, B[k][c]); U is r x 3 row-major on the device
+template <int R>
+__device__ __forceinline__ void rd_load_block(const double *__restrict__ X, const double *__restrict__ U, int g, double B[3][4]) {
+  double x[4][R];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int a = 0; a < R; ++a) x[c][a] = X[((size_t)4 * g + c) * R + a];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int a = 0; a < R; ++a) s += U[3 * a + k] * x[c][a];
+      B[k][c] = s;
+    }
+}
+
+__device__ __forceinline__ double rd_det3(const double A[3][4]) {
+  return A[0][0] * (A[1][1] * A[2][2] - A[2][1] * A[1][2]) - A[0][1] * (A[1][0] * A[2][2] - A[2][0] * A[1][2]) +
+         A[0][2] * (A[1][0] * A[2][1] - A[2][0] * A[1][1]);
+}
+
+// per workgroup: poses with det(U^T Y_i) < 0 and > 0 -> cnt[2 blk], cnt[2 blk + 1]
+template <int R>
+__global__ __launch_bounds__(RD_WG) void k_round_det(const double *__restrict__ X, const double *__restrict__ U, int N,
+                                                     int *__restrict__ cnt) {
+  const int g = blockIdx.x * RD_WG + threadIdx.x;
+  double det = 0.0;
+  if (g < N) {
+    double B[3][4];
+    rd_load_block<R>(X, U, g, B);
+    det = rd_det3(B);
+  }
+  const unsigned long long neg = __ballot(det < 0.0), pos = __ballot(det > 0.0);
+  if (threadIdx.x == 0) {
+    cnt[2 * blockIdx.x] = __popcll(neg);
+    cnt[2 * blockIdx.x + 1] = __popcll(pos);
+  }
+}
+
+// ONE lane: the counts summed in workgroup order; flag[0] = -1 (reflect: D = diag(1, 1, -1)) when the negatives outnumber
+// the positives, else +1 (a tie keeps U); flag[1], flag[2] = the counts
+__global__ void k_round_sign(const int *__restrict__ cnt, int nblk, double *__restrict__ flag) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  long long neg = 0, pos = 0;
+  for (int k = 0; k < nblk; ++k) {
+    neg += cnt[2 * k];
+    pos += cnt[2 * k + 1];
+  }
+  flag[0] = neg > pos ? -1.0 : 1.0;
+  flag[1] = (double)neg;
+  flag[2] = (double)pos;
+}
+
+// nearest rotation to the 3 x 3 block A (A[k][c], c < 3), degenerate blocks included.  With A^T A = V diag(w) V^T (w
+// descending: v1, v2, v3), w1 = A v1 / |A v1| and w2 = A v2 orthogonalised against w1 and normalised, the nearest rotation
+// is w1 v1^T + w2 v2^T + det(V) (w1 x w2) v3^T -- for det A > 0 and det A < 0 alike -- and needs no division by the smallest
+// singular value.  Returns true when that value is below 1e-12 of the largest (then the third direction is the cross
+// product, and w2 an arbitrary unit vector orthogonal to w1 when the second is as small too; a zero block gives I).
+__device__ __forceinline__ bool rd_nearest_rotation(const double A[3][4], double Rm[3][3]) {
+  double S[9], w[3], V[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) S[3 * c + d] = A[0][c] * A[0][d] + A[1][c] * A[1][d] + A[2][c] * A[2][d];
+  sym3_eig(S, w, V);
+  int i1 = 0, i3 = 0;
+  if (w[1] > w[i1]) i1 = 1;
+  if (w[2] > w[i1]) i1 = 2;
+  if (w[1] < w[i3]) i3 = 1;
+  if (w[2] < w[i3]) i3 = 2;
+  if (i3 == i1) i3 = (i1 + 1) % 3;  // (all three equal)
+  const int i2 = 3 - i1 - i3;
+  double v1[3], v2[3], v3[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    v1[c] = V[3 * c + i1];
+    v2[c] = V[3 * c + i2];
+    v3[c] = V[3 * c + i3];
+  }
+  double u1[3], u2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    u1[k] = A[k][0] * v1[0] + A[k][1] * v1[1] + A[k][2] * v1[2];
+    u2[k] = A[k][0] * v2[0] + A[k][1] * v2[1] + A[k][2] * v2[2];
+  }
+  const double s1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+  if (!(s1 > 0.0)) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Rm[k][c] = (k == c) ? 1.0 : 0.0;
+    return true;
+  }
+  double w1[3] = {u1[0] / s1, u1[1] / s1, u1[2] / s1};
+  const double d12 = w1[0] * u2[0] + w1[1] * u2[1] + w1[2] * u2[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) u2[k] -= d12 * w1[k];
+  double s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+  bool degenerate = false;
+  if (!(s2 > 1e-12 * s1)) {
+    // rank one: w2 from the axis least aligned with w1
+    degenerate = true;
+    int e = 0;
+    if (fabs(w1[1]) < fabs(w1[e])) e = 1;
+    if (fabs(w1[2]) < fabs(w1[e])) e = 2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) u2[k] = ((k == e) ? 1.0 : 0.0) - w1[e] * w1[k];
+    s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+  } else {
+    // smallest singular value from |det A| = s1 s2 s3 (the eigenvalue of A^T A cannot resolve it below 1e-8 s1)
+    if (fabs(rd_det3(A)) < 1e-12 * s1 * s1 * s2) degenerate = true;
+  }
+  const double w2[3] = {u2[0] / s2, u2[1] / s2, u2[2] / s2};
+  const double detV = v1[0] * (v2[1] * v3[2] - v2[2] * v3[1]) - v1[1] * (v2[0] * v3[2] - v2[2] * v3[0]) +
+                      v1[2] * (v2[0] * v3[1] - v2[1] * v3[0]);
+  const double sg = detV < 0.0 ? -1.0 : 1.0;
+  const double w3[3] = {sg * (w1[1] * w2[2] - w1[2] * w2[1]), sg * (w1[2] * w2[0] - w1[0] * w2[2]),
+                        sg * (w1[0] * w2[1] - w1[1] * w2[0])};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Rm[k][c] = w1[k] * v1[c] + w2[k] * v2[c] + w3[k] * v3[c];
+  return degenerate;
+}
+
+// per pose: B = D U^T [Y_i | p_i]; T_i = [nearest rotation to B's 3 x 3 block | B's last column] (12 doubles: R column-major,
+// then t); degenerate blocks of the workgroup -> deg[blk]
+template <int R>
+__global__ __launch_bounds__(RD_WG) void k_round_project(const double *__restrict__ X, const double *__restrict__ U,
+                                                         const double *__restrict__ flag, int N, double *__restrict__ T,
+                                                         int *__restrict__ deg) {
+  const int g = blockIdx.x * RD_WG + threadIdx.x;
+  bool dg = false;
+  if (g < N) {
+    double B[3][4];
+    rd_load_block<R>(X, U, g, B);
+    const double d3 = flag[0];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) B[2][c] *= d3;
+    double Rm[3][3];
+    dg = rd_nearest_rotation(B, Rm);
+    double *o = T + (size_t)12 * g;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[3 * c + k] = Rm[k][c];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[9 + k] = B[k][3];
+  }
+  const unsigned long long m = __ballot(dg);
+  if (threadIdx.x == 0) deg[blockIdx.x] = __popcll(m);
+}
+
+// T_i <- T_0^-1 T_i  (R_0^T R_i, R_0^T (t_i - t_0)); pose 0 becomes exactly (I, 0)
+__global__ __launch_bounds__(RD_WG) void k_round_anchor(const double *__restrict__ Tin, int N, double *__restrict__ Tout) {
+  const int g = blockIdx.x * RD_WG + threadIdx.x;
+  if (g >= N) return;
+  double *o = Tout + (size_t)12 * g;
+  if (g == 0) {
+#pragma unroll
+    for (int e = 0; e < 12; ++e) o[e] = (e == 0 || e == 4 || e == 8) ? 1.0 : 0.0;
+    return;
+  }
+  double R0[9], t0[3], Ri[9], ti[3];  // column-major
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    R0[e] = Tin[e];
+    Ri[e] = Tin[(size_t)12 * g + e];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t0[k] = Tin[9 + k];
+    ti[k] = Tin[(size_t)12 * g + 9 + k] - t0[k];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)  // (R_0^T R_i)[k][c] = sum_m R_0[m][k] R_i[m][c]
+      o[3 * c + k] = R0[3 * k] * Ri[3 * c] + R0[3 * k + 1] * Ri[3 * c + 1] + R0[3 * k + 2] * Ri[3 * c + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[9 + k] = R0[3 * k] * ti[0] + R0[3 * k + 1] * ti[1] + R0[3 * k + 2] * ti[2];
+}
+
+}  // namespace dpgo
+
+// =================================================================================================
+// host side
+using namespace dpgo;
+using namespace dpgo_host;
+using namespace dpgo_cert;
+
+namespace {
+
+// the rounding's workspace inside the certificate's (d_cert, d_cert_int, h_cert)
+struct RoundWs {
+  Cert c;
+  int nbr = 0;  // workgroups of the per-pose kernels
+  double *E = nullptr, *Tp = nullptr, *Ta = nullptr, *TE = nullptr, *rpart = nullptr, *Ud = nullptr, *flag = nullptr;
+  int *cnt = nullptr, *deg = nullptr;
+  double *hG = nullptr, *hU = nullptr, *hS = nullptr, *hT = nullptr;
+  int *hD = nullptr;
+  // slots of c.G: 0 the rotation Gram, 1 X^T (X Q), 2 T^T (T Q)
+
+  int setup(dpgo_team_t *t) {
+    c.t = t;
+    c.r = t->prm.r;
+    c.K = 3;
+    c.na = (int)t->ag.size();
+    std::vector<int> offs(c.na + 1, 0);
+    c.max_n = 0;
+    for (int k = 0; k < c.na; ++k) {
+      offs[k + 1] = offs[k] + t->ag[k]->n;
+      c.max_n = std::max(c.max_n, t->ag[k]->n);
+    }
+    const int r = c.r, N = c.N = offs[c.na];
+    c.L = 4 * N;
+    c.nblk = (c.L + CG_CH - 1) / CG_CH;
+    nbr = (N + RD_WG - 1) / RD_WG;
+    const size_t Ls = (size_t)c.L, S = Cert::SLOT;
+    const size_t need = 2 * r * Ls + 3 * 3 * Ls + (size_t)c.nblk * S + (size_t)nbr * r * r + 3 * S + 32;
+    const size_t ineed = (size_t)c.na + 1 + 3 * (size_t)nbr;
+    const size_t hneed = 3 * S + (size_t)nbr + 3 * Ls;
+    if (t->d_cert.alloc(need) || t->d_cert_int.alloc(ineed) || t->h_cert.alloc(hneed)) {
+      set_err("round: workspace allocation failed");
+      return DPGO_ERR;
+    }
+    double *p = t->d_cert.p;
+    auto take = [&](size_t n) { double *q = p; p += n; return q; };
+    c.Xt = take(r * Ls); E = take(r * Ls);
+    Tp = take(3 * Ls); Ta = take(3 * Ls); TE = take(3 * Ls);
+    c.part = take((size_t)c.nblk * S); rpart = take((size_t)nbr * r * r);
+    c.G = take(3 * S); Ud = take(24); flag = take(8);
+    c.off = t->d_cert_int.p;
+    cnt = c.off + c.na + 1;
+    deg = cnt + 2 * nbr;
+    hG = t->h_cert.p; hU = hG + S; hS = hU + S;
+    hD = (int *)(hS + S);
+    hT = hS + S + nbr;
+    HIPC(hipMemcpyAsync(c.off, offs.data(), sizeof(int) * (c.na + 1), hipMemcpyHostToDevice, t->stream));
+    // the team's iterate, gathered in team order (agent arrays are r x 4n each: ld r)
+    for (int k = 0; k < c.na; ++k)
+      HIPC(hipMemcpyAsync(c.Xt + (size_t)4 * offs[k] * r, t->ag[k]->dev.buf[B_X], sizeof(double) * r * 4 * t->ag[k]->n,
+                          hipMemcpyDeviceToDevice, t->stream));
+    return 0;
+  }
+
+  // 1/2 <T, T Q> of the trajectory in Ta into slot 2
+  void rounded_cost() {
+    c.apply(3, Ta, 3, TE, 3, false);
+    c.gram(Ta, 3, 3, TE, 3, 3, c.slot(2));
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int dpgo_team_round(dpgo_team_t *t, int flags, double *T, dpgo_rounding_t *out) {
+  if (!t || !T || !out) { set_err("round: null argument"); return DPGO_ERR; }
+  if (check_team(t, "round")) return DPGO_ERR;
+  RoundWs ws;
+  if (ws.setup(t)) return DPGO_ERR;
+  Cert &c = ws.c;
+  const int r = c.r, N = c.N, nbr = ws.nbr;
+  const size_t Ls = (size_t)c.L;
+  // Gram matrix of the rotation block; f_relaxed queued behind it (the device runs it while the host solves for U)
+  DPGO_DISPATCH_R(r, (k_round_gram<R><<<nbr, RD_WG, 0, t->stream>>>(c.Xt, N, ws.rpart)));
+  c.sum_partials(ws.rpart, nbr, r * r, c.slot(0));
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(ws.hG, c.slot(0), sizeof(double) * r * r, hipMemcpyDeviceToHost, t->stream));
+  c.apply(r, c.Xt, r, ws.E, r, false);
+  c.gram(c.Xt, r, r, ws.E, r, r, c.slot(1));
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(t->stream));
+  // U: eigenvectors of the 3 largest eigenvalues, descending (row-major r x 3)
+  std::vector<double> A((size_t)r * r), w, V;
+  for (int p = 0; p < r; ++p)
+    for (int q = 0; q < r; ++q) A[(size_t)p * r + q] = 0.5 * (ws.hG[p * r + q] + ws.hG[q * r + p]);
+  jacobi_eig(r, A, w, V);
+  for (int a = 0; a < r; ++a)
+    for (int k = 0; k < 3; ++k) ws.hU[3 * a + k] = V[(size_t)a * r + (r - 1 - k)];
+  for (int k = 0; k < 8; ++k) out->sigma[k] = k < r ? std::sqrt(std::max(w[r - 1 - k], 0.0)) : 0.0;
+  HIPC(hipMemcpyAsync(ws.Ud, ws.hU, sizeof(double) * 3 * r, hipMemcpyHostToDevice, t->stream));
+  // determinant rule, projection, gauge
+  DPGO_DISPATCH_R(r, (k_round_det<R><<<nbr, RD_WG, 0, t->stream>>>(c.Xt, ws.Ud, N, ws.cnt)));
+  k_round_sign<<<1, 64, 0, t->stream>>>(ws.cnt, nbr, ws.flag);
+  DPGO_DISPATCH_R(r, (k_round_project<R><<<nbr, RD_WG, 0, t->stream>>>(c.Xt, ws.Ud, ws.flag, N, ws.Tp, ws.deg)));
+  k_round_anchor<<<nbr, RD_WG, 0, t->stream>>>(ws.Tp, N, ws.Ta);
+  ws.rounded_cost();
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(ws.hT, ws.Ta, sizeof(double) * 3 * Ls, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipMemcpyAsync(ws.hS, c.slot(1), sizeof(double) * r * r, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipMemcpyAsync(ws.hS + 64, c.slot(2), sizeof(double) * 9, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipMemcpyAsync(ws.hS + 80, ws.flag, sizeof(double) * 3, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipMemcpyAsync(ws.hD, ws.deg, sizeof(int) * nbr, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipStreamSynchronize(t->stream));
+  double fx = 0.0;
+  for (int a = 0; a < r; ++a) fx += ws.hS[a * r + a];
+  out->f_relaxed = 0.5 * fx;
+  out->f_rounded = 0.5 * (ws.hS[64] + ws.hS[68] + ws.hS[72]);
+  out->r = r;
+  out->reflected = ws.hS[80] < 0.0 ? 1 : 0;
+  out->refined = 0;
+  int nd = 0;
+  for (int k = 0; k < nbr; ++k) nd += ws.hD[k];
+  out->num_degenerate = nd;
+  std::memcpy(T, ws.hT, sizeof(double) * 3 * Ls);
+  if (!(flags & DPGO_ROUND_REFINE_TRANSLATIONS)) return DPGO_OK;
+
+  // translations given the rounded rotations: the team's measurements with their current weights in team-order numbering,
+  // each shared edge once (the copy of the lower robot, which owns its weight)
+  std::vector<int> offs(c.na + 1, 0);
+  for (int k = 0; k < c.na; ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
+  std::vector<dpgo_measurement_t> mm, ma;
+  for (int k = 0; k < c.na; ++k) {
+    const int id = t->ag[k]->id;
+    const int cntm = dpgo_agent_get_measurements(t, id, nullptr);
+    if (cntm < 0) return DPGO_ERR;
+    ma.resize(cntm);
+    if (cntm > 0 && dpgo_agent_get_measurements(t, id, ma.data()) != cntm) return DPGO_ERR;
+    for (const auto &m : ma) {
+      if (m.r1 != m.r2 && std::min(m.r1, m.r2) != id) continue;
+      const auto l1 = t->id2local.find(m.r1), l2 = t->id2local.find(m.r2);
+      if (l1 == t->id2local.end() || l2 == t->id2local.end()) { set_err("round: a measurement names a robot outside the team"); return DPGO_ERR; }
+      dpgo_measurement_t q = m;
+      q.r1 = q.r2 = 0;
+      q.p1 = offs[l1->second] + m.p1;
+      q.p2 = offs[l2->second] + m.p2;
+      mm.push_back(q);
+    }
+  }
+  if (dpgo_translations_given_rotations(t->device, mm.data(), (int)mm.size(), N, T)) {
+    set_err(std::string("round: ") + dpgo_last_error());
+    return DPGO_ERR;
+  }
+  HIPC(hipSetDevice(t->device));
+  std::memcpy(ws.hT, T, sizeof(double) * 3 * Ls);
+  HIPC(hipMemcpyAsync(ws.Ta, ws.hT, sizeof(double) * 3 * Ls, hipMemcpyHostToDevice, t->stream));
+  ws.rounded_cost();
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(ws.hS + 64, c.slot(2), sizeof(double) * 9, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipStreamSynchronize(t->stream));
+  out->f_rounded = 0.5 * (ws.hS[64] + ws.hS[68] + ws.hS[72]);
+  out->refined = 1;
+  return DPGO_OK;
+}
+
+}  // extern "C"

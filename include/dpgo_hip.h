@@ -293,6 +293,26 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
 /* staircase step, host arithmetic: X (r x 4n) and v (4n) -> the rank r+1 point [X; 0] + alpha [0; v^T],
  * rotation blocks projected back to the Stiefel manifold */
 int dpgo_escape_point(const double *X, int r, int num_poses, const double *v, double alpha, double *X_out);
+/* SE-Sync rounding of the current iterate (Rosen et al. 2019, Alg. 2; csrc/round.hip): U = the top-3 left singular vectors of
+ * the r x 3N rotation block of X; D = diag(1, 1, -1) when more poses have det(U^T Y_i) < 0 than > 0 (a tie keeps U);
+ * R_i = the nearest rotation to D U^T Y_i (degenerate blocks completed by a cross product), t_i = D U^T p_i; every pose
+ * then relative to the first in team order (T_0 = I, t_0 = 0).  With DPGO_ROUND_REFINE_TRANSLATIONS the translations are
+ * re-solved for the rounded rotations (dpgo_translations_given_rotations on the team's measurements, current weights).
+ * When the iterate is certified, f_rounded - f_relaxed bounds the suboptimality of T (up to the certificate's eta). */
+typedef struct {
+  double f_relaxed;      /* 1/2 <Q, X^T X> at the team's iterate */
+  double f_rounded;      /* 1/2 <Q, T^T T> of the returned trajectory (the team's Q: current weights) */
+  double sigma[8];       /* singular values of the r x 3N rotation block of X, descending; 0 beyond r */
+  int r, reflected, refined, num_degenerate;
+} dpgo_rounding_t;
+enum { DPGO_ROUND_REFINE_TRANSLATIONS = 1 };
+/* T = 12 doubles per pose in team order (R column-major, then t), anchored at the first pose.  All robots local and
+ * INITIALIZED (the certificate's refusals and messages).  Changes no solver state. */
+int dpgo_team_round(dpgo_team_t *t, int flags, double *T, dpgo_rounding_t *out);
+/* t minimising sum_e w_e tau_e |t_j - t_i - R_i t~_e|^2 with t_0 = 0, for the rotations already in T (12 doubles per pose,
+ * single-robot numbering); translations of T overwritten.  Stage 2 of dpgo_chordal_init, with its two paths in the same
+ * cases.  DPGO_ERR with a message when edges of positive weight do not join every pose to pose 0. */
+int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, int nm, int num_poses, double *T);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
