@@ -8,6 +8,7 @@ loudly when the HIP extension has not been built, and every compute call needs a
 import ctypes as C
 import os
 import sys
+import threading
 
 import numpy as np
 
@@ -113,7 +114,7 @@ dpgo_comm_allreduce_sum dpgo_comm_allreduce_max dpgo_team_attach_comm dpgo_team_
 dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_iteration_log dpgo_team_run_simultaneous_ranks
 dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
 dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
-dpgo_translations_given_rotations""".split()
+dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across""".split()
 
 
 class DpgoError(RuntimeError):
@@ -161,6 +162,152 @@ def two_level_plan(rowptr, col, max_sub=0):
     _chk(lib().dpgo_two_level_plan(n, _d(rowptr), _d(col), int(max_sub), _d(sub_of), _d(info)), "two_level_plan")
     return sub_of, dict(subdomains=int(info[0]), separator_poses=int(info[1]), workgroups=int(info[2]),
                         producer_workgroups=int(info[3]), bytes_per_apply=info[4], worthwhile=bool(info[5]))
+
+
+# ---- transports of the calls across teams (dpgo_transport_t) ----
+_ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double))
+_EXCHANGE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double),
+                        C.POINTER(C.c_longlong))
+
+
+class TransportStruct(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("rank", C.c_int), ("world", C.c_int), ("allgather", _ALLGATHER),
+                ("exchange", _EXCHANGE)]
+
+
+class Transport:
+    """A transport the library calls (dpgo_transport_t): subclasses implement
+        allgather(x) -> the world contributions of len(x) doubles each, concatenated in rank order,
+        exchange(parts, recv_counts) -> one array per peer rank, recv_counts[p] doubles from p (parts[p] goes to p).
+    This object keeps the C structure and its callbacks alive.  A callback that raises makes the library call fail on this
+    participant (DPGO_ERR); `calls` counts the calls by kind."""
+
+    def __init__(self, rank, world):
+        self.rank, self.world = int(rank), int(world)
+        self.calls = {"allgather": 0, "exchange": 0}
+        self.error = None
+        self._ag = _ALLGATHER(self._c_allgather)
+        self._ex = _EXCHANGE(self._c_exchange)
+        self.struct = TransportStruct(None, self.rank, self.world, self._ag, self._ex)
+
+    def _c_allgather(self, ctx, inp, n, out):
+        try:
+            self.calls["allgather"] += 1
+            x = np.ctypeslib.as_array(inp, shape=(n,)).copy() if n > 0 else np.zeros(0)
+            got = np.ascontiguousarray(self.allgather(x), dtype=np.float64).reshape(-1)
+            if got.size != self.world * n:
+                raise ValueError("allgather returned %d doubles, expected %d" % (got.size, self.world * n))
+            if got.size:
+                C.memmove(out, got.ctypes.data, 8 * got.size)
+            return 0
+        except Exception as e:  # (an exception must not cross the C boundary)
+            self.error = e
+            return -1
+
+    def _c_exchange(self, ctx, send, send_counts, recv, recv_counts):
+        try:
+            self.calls["exchange"] += 1
+            sc = np.ctypeslib.as_array(send_counts, shape=(self.world,)).astype(np.int64)
+            rc = np.ctypeslib.as_array(recv_counts, shape=(self.world,)).astype(np.int64)
+            tot = int(sc.sum())
+            data = np.ctypeslib.as_array(send, shape=(tot,)).copy() if tot else np.zeros(0)
+            parts = np.split(data, np.cumsum(sc)[:-1])
+            got = self.exchange(parts, rc)
+            flat = [np.ascontiguousarray(g, dtype=np.float64).reshape(-1) for g in got]
+            if len(flat) != self.world or any(f.size != int(c) for f, c in zip(flat, rc)):
+                raise ValueError("exchange delivered sizes that differ from the counts")
+            flat = np.concatenate(flat) if flat else np.zeros(0)
+            if flat.size:
+                C.memmove(recv, flat.ctypes.data, 8 * flat.size)
+            return 0
+        except Exception as e:
+            self.error = e
+            return -1
+
+    def allgather(self, x):
+        raise NotImplementedError
+
+    def exchange(self, parts, recv_counts):
+        raise NotImplementedError
+
+
+class _LocalTransport(Transport):
+    def __init__(self, group, rank):
+        super().__init__(rank, group.world)
+        self.group = group
+
+    def allgather(self, x):
+        g = self.group
+        g.slot[self.rank] = x
+        g.wait()
+        sizes = {len(s) for s in g.slot}
+        out = np.concatenate(g.slot) if len(sizes) == 1 else None
+        g.wait()  # (nobody overwrites a slot before every participant has read them all)
+        if out is None:
+            raise ValueError("allgather: the participants passed different sizes %s" % sorted(sizes))
+        return out
+
+    def exchange(self, parts, recv_counts):
+        g = self.group
+        g.box[self.rank] = parts
+        g.wait()
+        got = [g.box[q][self.rank] for q in range(self.world)]
+        g.wait()
+        return got
+
+
+class LocalGroup:
+    """`world` transports for teams driven from threads of one process (one team per GPU, or a problem split on one GPU):
+    a barrier with shared buffers.  A participant that leaves the sequence, or a barrier that waits longer than `timeout`
+    seconds, breaks the barrier: every participant's call then fails instead of waiting forever."""
+
+    def __init__(self, world, timeout=120.0):
+        self.world = int(world)
+        self.barrier = threading.Barrier(self.world, timeout=timeout)
+        self.slot = [None] * self.world
+        self.box = [None] * self.world
+        self.transports = [_LocalTransport(self, q) for q in range(self.world)]
+
+    def wait(self):
+        self.barrier.wait()
+
+    def abort(self):
+        self.barrier.abort()
+
+    def __len__(self):
+        return self.world
+
+    def __getitem__(self, q):
+        return self.transports[q]
+
+    def __iter__(self):
+        return iter(self.transports)
+
+    def run(self, fns, timeout=600.0):
+        """call fns[q]() on one thread each (q = rank) and join them within `timeout` seconds: [(result, exception)];
+        a thread still running at the end breaks the barrier and raises"""
+        res = [(None, None)] * len(fns)
+
+        def body(q):
+            try:
+                res[q] = (fns[q](), None)
+            except Exception as e:
+                res[q] = (None, e)
+                self.abort()  # (the others fail at their next barrier instead of waiting for this one)
+
+        th = [threading.Thread(target=body, args=(q,), daemon=True) for q in range(len(fns))]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join(timeout)
+        if any(t.is_alive() for t in th):
+            self.abort()
+            raise TimeoutError("a participant did not return within %g s" % timeout)
+        return res
+
+
+def _owner_array(owner_of_robot):
+    return np.ascontiguousarray(owner_of_robot, dtype=np.int32)
 
 
 def _chk(rc, what):
@@ -757,38 +904,57 @@ class Team:
     def global_X(self):
         return np.concatenate([self.agents[i].get_X() for i in self.ids])
 
-    def certificate_apply(self, V):
+    def certificate_apply(self, V, transport=None, owner_of_robot=None):
         """S(X) V for a K x 4N block (K in 3..8) in the iterate layout over the team's poses in team order:
-        element (b, column 4 g + c) at [(4 g + c) K + b]"""
+        element (b, column 4 g + c) at [(4 g + c) K + b].  With a transport (and the owner table: the participant that
+        holds each robot), the team holds part of the robots and V / the result its own columns; every participant calls."""
         N = int(sum(self.agents[i].n for i in self.ids))
         V = np.ascontiguousarray(V, dtype=np.float64).reshape(-1)
         K = V.size // (4 * N)
         assert V.size == K * 4 * N
         out = np.zeros_like(V)
-        _chk(lib().dpgo_team_certificate_apply(self.h, int(K), _d(V), _d(out)), "certificate_apply")
+        if transport is None:
+            _chk(lib().dpgo_team_certificate_apply(self.h, int(K), _d(V), _d(out)), "certificate_apply")
+        else:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_certificate_apply_across(self.h, C.byref(transport.struct), _d(own), int(K), _d(V), _d(out)),
+                 "certificate_apply_across")
         return out
 
-    def certify(self, eta=1e-6, tol=1e-8, max_iters=1000, block=0, deflate=True, precondition=True, eta_relative=True):
+    def certify(self, eta=1e-6, tol=1e-8, max_iters=1000, block=0, deflate=True, precondition=True, eta_relative=True,
+                transport=None, owner_of_robot=None):
         """smallest eigenvalue of the certificate matrix S(X) at the current iterate (LOBPCG on the device).  Returns
         (Certificate, v): certified 1 = converged with lambda_min >= -eta, 0 = lambda_min < -eta (v, 4N doubles in team
         order, is a direction of negative curvature), -1 = not converged.  eta is relative to the bound s on |S| unless
-        eta_relative is False; tol always is.  Changes no solver state."""
+        eta_relative is False; tol always is.  Changes no solver state.  With a transport: the certificate of the iterate
+        split across the participants' teams (every participant calls; v holds this team's columns)."""
         N = int(sum(self.agents[i].n for i in self.ids))
         flags = (0 if deflate else CERT_NO_DEFLATION) | (0 if precondition else CERT_NO_PRECONDITIONER) | \
             (CERT_ETA_RELATIVE if eta_relative else 0)
         res, v = Certificate(), np.zeros(4 * N)
-        _chk(lib().dpgo_team_certify(self.h, C.c_double(eta), C.c_double(tol), int(max_iters), int(block), flags,
-                                     C.byref(res), _d(v)), "certify")
+        if transport is None:
+            _chk(lib().dpgo_team_certify(self.h, C.c_double(eta), C.c_double(tol), int(max_iters), int(block), flags,
+                                         C.byref(res), _d(v)), "certify")
+        else:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_certify_across(self.h, C.byref(transport.struct), _d(own), C.c_double(eta), C.c_double(tol),
+                                                int(max_iters), int(block), flags, C.byref(res), _d(v)), "certify_across")
         return res, v
 
-    def round(self, refine_translations=True):
+    def round(self, refine_translations=True, transport=None, owner_of_robot=None):
         """SE-Sync rounding of the current iterate: (Rounding, T) with T flat, 12 doubles per pose in team order (the layout
         of chordal_init), anchored at the first pose.  refine_translations: the translations re-solved for the rounded
-        rotations with the team's measurements and current weights.  Changes no solver state."""
+        rotations with the team's measurements and current weights.  Changes no solver state.  With a transport: the
+        rounding of the iterate split across the participants' teams, anchored at robot 0's first pose (T: this team's poses)."""
         N = int(sum(self.agents[i].n for i in self.ids))
         res, T = Rounding(), np.zeros(12 * N)
         flags = ROUND_REFINE_TRANSLATIONS if refine_translations else 0
-        _chk(lib().dpgo_team_round(self.h, flags, _d(T), C.byref(res)), "round")
+        if transport is None:
+            _chk(lib().dpgo_team_round(self.h, flags, _d(T), C.byref(res)), "round")
+        else:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_round_across(self.h, C.byref(transport.struct), _d(own), flags, _d(T), C.byref(res)),
+                 "round_across")
         return res, T
 
 

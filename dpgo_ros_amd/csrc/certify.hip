@@ -19,11 +19,13 @@ namespace dpgo {
 
 // OUT = V Q_a + G_a(V) - V Lambda_a  for every pose of every agent (blockIdx.y = agent), one lane per (pose, row b).
 // lam == null: the Euclidean gradient product V Q_full alone.  The SpMM is the library's block product (spmm_row); the
-// neighbour term reads the neighbour's rows of V itself (every neighbour is a local agent: src_agent_local >= 0).
+// neighbour term reads the neighbour's rows of V itself when it is a local agent (src_agent_local >= 0), else from the
+// halo of the calls across teams: halo[(4 (hoff[agent] + slot) + c) K + b] (certify_across.hip; null for one team).
 template <int K>
 __global__ __launch_bounds__(64) void k_cert_apply(const AgentDev *__restrict__ agents, const int *__restrict__ off,
                                                    const double *__restrict__ V, int ldv, double *__restrict__ out, int ldo,
-                                                   const double *__restrict__ lam) {
+                                                   const double *__restrict__ lam, const double *__restrict__ halo,
+                                                   const int *__restrict__ hoff) {
   const int ai = blockIdx.y;
   const AgentDev &ag = agents[ai];
   constexpr int PPB = 64 / K;
@@ -39,10 +41,16 @@ __global__ __launch_bounds__(64) void k_cert_apply(const AgentDev *__restrict__ 
   const int e0 = ag.pose_eptr[j], e1 = ag.pose_eptr[j + 1];
   for (int e = e0; e < e1; ++e) {
     const SharedEdgeDev &se = ag.se[e];
-    const size_t nc = (size_t)4 * (off[se.src_agent_local] + se.src_frame);
     double x[4];
+    if (se.src_agent_local >= 0) {
+      const size_t nc = (size_t)4 * (off[se.src_agent_local] + se.src_frame);
 #pragma unroll
-    for (int cp = 0; cp < 4; ++cp) x[cp] = V[(nc + cp) * ldv + b];
+      for (int cp = 0; cp < 4; ++cp) x[cp] = V[(nc + cp) * ldv + b];
+    } else {
+      const size_t hc = (size_t)4 * (hoff[ai] + se.slot);
+#pragma unroll
+      for (int cp = 0; cp < 4; ++cp) x[cp] = halo[(hc + cp) * K + b];
+    }
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -334,47 +342,70 @@ int Cert::setup(int K_) {
   gstride = (max_n + 255) / 256;
   const size_t Ls = (size_t)L;
   const size_t need = 2 * r * Ls + 9 * (size_t)N + 2 * (r + 1) * Ls + 4 * 3 * (size_t)K * Ls + 2 * (size_t)K * Ls +
-                      (size_t)nblk * SLOT + 8 * (size_t)SLOT + (size_t)na * gstride;
-  if (t->d_cert.alloc(need) || t->d_cert_int.alloc(na + 1) || t->h_cert.alloc(5 * SLOT + (size_t)K * L)) {
+                      (size_t)nblk * SLOT + 8 * (size_t)SLOT + (size_t)na * gstride + (x ? x->dev_doubles() : 0);
+  if (t->d_cert.alloc(need) || t->d_cert_int.alloc(na + 1 + (x ? x->dev_ints() : 0)) ||
+      t->h_cert.alloc(5 * SLOT + (size_t)K * L)) {
     set_err("certificate: workspace allocation failed");
-    return DPGO_ERR;
+    if (!x) return DPGO_ERR;
+    x->fail_local("certificate: workspace allocation failed");
   }
-  double *p = t->d_cert.p;
-  auto take = [&](size_t n) { double *q = p; p += n; return q; };
-  Xt = take(r * Ls); E = take(r * Ls); lam = take(9 * (size_t)N);
-  Zr = take((r + 1) * Ls); Zo = take((r + 1) * Ls);
-  for (int b = 0; b < 2; ++b) { U[b] = take(3 * K * Ls); AU[b] = take(3 * K * Ls); }
-  T = take(K * Ls); T2 = take(K * Ls);
-  part = take((size_t)nblk * SLOT); G = take(8 * (size_t)SLOT); gmax = take((size_t)na * gstride);
-  off = t->d_cert_int.p;
-  HIPC(hipMemcpyAsync(off, offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, t->stream));
-  HIPC(hipMemsetAsync(G, 0, sizeof(double) * 8 * SLOT, t->stream));
+  if (!halted()) {
+    double *p = t->d_cert.p;
+    auto take = [&](size_t n) { double *q = p; p += n; return q; };
+    Xt = take(r * Ls); E = take(r * Ls); lam = take(9 * (size_t)N);
+    Zr = take((r + 1) * Ls); Zo = take((r + 1) * Ls);
+    for (int b = 0; b < 2; ++b) { U[b] = take(3 * K * Ls); AU[b] = take(3 * K * Ls); }
+    T = take(K * Ls); T2 = take(K * Ls);
+    part = take((size_t)nblk * SLOT); G = take(8 * (size_t)SLOT); gmax = take((size_t)na * gstride);
+    off = t->d_cert_int.p;
+    if (x) x->place(p, off + na + 1, t->stream);
+  }
+  CERT_CK(*this, hipMemcpyAsync(off, offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, t->stream));
+  CERT_CK(*this, hipMemsetAsync(G, 0, sizeof(double) * 8 * SLOT, t->stream));
   // the team's iterate, gathered in team order (agent arrays are r x 4n each: ld r)
   for (int k = 0; k < na; ++k)
-    HIPC(hipMemcpyAsync(Xt + (size_t)4 * offs[k] * r, t->ag[k]->dev.buf[B_X], sizeof(double) * r * 4 * t->ag[k]->n,
-                        hipMemcpyDeviceToDevice, t->stream));
+    CERT_CK(*this, hipMemcpyAsync(Xt + (size_t)4 * offs[k] * r, t->ag[k]->dev.buf[B_X], sizeof(double) * r * 4 * t->ag[k]->n,
+                                  hipMemcpyDeviceToDevice, t->stream));
   apply(r, Xt, r, E, r, false);
-  DPGO_DISPATCH_R(r, (k_cert_lambda<R><<<dim3(gstride, na), 256, 0, t->stream>>>(t->d_agents.p, off, Xt, E, lam, gmax, gstride)));
-  HIPC(hipGetLastError());
+  if (!halted())
+    DPGO_DISPATCH_R(r, (k_cert_lambda<R><<<dim3(gstride, na), 256, 0, t->stream>>>(t->d_agents.p, off, Xt, E, lam, gmax, gstride)));
+  CERT_CK(*this, hipGetLastError());
   return 0;
 }
 
+bool Cert::halted() const { return x && (x->bad || x->dead); }
+bool Cert::dead() const { return x && x->dead; }
+
+void Cert::reduce(std::initializer_list<std::pair<double *, int>> parts) {
+  if (x) x->reduce(*this, parts);
+}
+
 void Cert::apply(int k, const double *V, int ldv, double *out, int ldo, bool with_lam) {
+  const double *halo = nullptr;
+  const int *hoff = nullptr;
+  if (x) {
+    halo = x->halo_of(*this, k, V, ldv);
+    hoff = x->d_hoff;
+    if (halted()) return;
+  }
   const dim3 grid(spmm_grid(k, max_n), na);
   const double *lm = with_lam ? lam : nullptr;
-  DPGO_DISPATCH_R(k, (k_cert_apply<R><<<grid, 64, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo, lm)));
+  DPGO_DISPATCH_R(k, (k_cert_apply<R><<<grid, 64, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo, lm, halo, hoff)));
 }
 
 void Cert::gram(const double *A, int lda, int ka, const double *B, int ldb, int kb, double *out) {
+  if (halted()) return;
   k_cert_gram<<<nblk, 256, 0, t->stream>>>(A, lda, ka, B, ldb, kb, L, part);
   k_cert_gram_sum<<<1, 256, 0, t->stream>>>(part, nblk, ka * kb, out);
 }
 
 void Cert::sum_partials(const double *p, int nblk_, int m, double *out) {
+  if (halted()) return;
   k_cert_gram_sum<<<1, 256, 0, t->stream>>>(p, nblk_, m, out);
 }
 
 void Cert::update(double *out, int ldo, int ko, double beta, std::initializer_list<CertTerm> terms) {
+  if (halted()) return;
   CertTerms tm{};
   for (const CertTerm &x : terms) tm.t[tm.n++] = x;
   const size_t cnt = (size_t)L * ko;
@@ -384,18 +415,21 @@ void Cert::update(double *out, int ldo, int ko, double beta, std::initializer_li
 void Cert::project(double *V, int ld, int k) {
   if (!deflate) return;
   gram(Zo, nz, nz, V, ld, k, slot(5));
+  reduce({{slot(5), nz * k}});
   update(V, ld, k, 1.0, {CertTerm{Zo, slot(5), nz, nz, -1.0}});
 }
 
 void Cert::cholqr(double *V, int ld, int k, double *S) {
   gram(V, ld, k, V, ld, k, slot(4));
-  k_cert_chol<<<1, 64, 0, t->stream>>>(slot(4), k, slot(6), slot(3));
+  reduce({{slot(4), k * k}});
+  if (!halted()) k_cert_chol<<<1, 64, 0, t->stream>>>(slot(4), k, slot(6), slot(3));
   update(S, k, k, 0.0, {CertTerm{V, slot(6), ld, k, 1.0}});
   update(V, ld, k, 0.0, {CertTerm{S, nullptr, k, k, 1.0}});
 }
 
 void Cert::precondition(const double *V, int ldv, double *out, int ldo) {
-  DPGO_DISPATCH_R(K, (k_cert_precond<R><<<dim3(4 * max_n, na), 256, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo)));
+  if (halted()) return;
+  DPGO_DISPATCH_R(K,(k_cert_precond<R><<<dim3(4 * max_n, na), 256, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo)));
 }
 
 int check_team(dpgo_team_t *t, const char *what) {
@@ -438,19 +472,33 @@ int dpgo_team_certificate_apply(dpgo_team_t *t, int K, const double *V, double *
   return 0;
 }
 
-int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int block, int flags, dpgo_certificate_t *out,
-                      double *v) {
-  if (!t || !out) { set_err("certify: null argument"); return DPGO_ERR; }
-  const int K = block > 0 ? block : t->prm.r;
-  if (K < 3 || K > 8) { set_err("certify: the block size must lie in 3..8"); return DPGO_ERR; }
-  if (max_iters < 1 || !(tol > 0) || !(eta >= 0)) { set_err("certify: max_iters >= 1, tol > 0 and eta >= 0 required"); return DPGO_ERR; }
-  if (check_team(t, "certify")) return DPGO_ERR;
-  Cert c;
-  c.t = t;
+}  // extern "C"
+
+namespace dpgo_cert {
+
+// the state of the starting block's generator s <- 6364136223846793005 s + 1442695040888963407 after n steps, in O(log n)
+static unsigned long long lcg_skip(unsigned long long s, unsigned long long n) {
+  unsigned long long a = 6364136223846793005ull, c = 1442695040888963407ull, A = 1, C = 0;
+  for (; n; n >>= 1) {
+    if (n & 1) { A *= a; C = C * a + c; }
+    c *= a + 1;
+    a *= a;
+  }
+  return A * s + C;
+}
+
+// Across teams (c.x) every Gram matrix is summed over the participants before its first use (Cert::reduce, inside
+// project / cholqr), the operator exchanges its halo (Cert::apply), and every host decision is taken right behind an
+// allgather on the summed bits: all participants take the same branches and make the same transport calls.
+int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flags, dpgo_certificate_t *out, double *v) {
+#define CK(expr) CERT_CK(c, expr)
+  dpgo_team_t *t = c.t;
+  Across *x = c.x;
   c.deflate = !(flags & DPGO_CERT_NO_DEFLATION);
   c.precond = !(flags & DPGO_CERT_NO_PRECONDITIONER);
   for (auto &a : t->ag)
     if (!a->dev.M && !a->dev.Dinv) c.precond = false;  // (two-level agents: no raw apply of their operator)
+  if (x && !x->all_precond) c.precond = false;         // (one decision for every participant)
   if (c.setup(K)) return DPGO_ERR;
   const int r = c.r, L = c.L, K3 = 3 * K;
   const size_t Ls = (size_t)L;
@@ -460,11 +508,13 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
   // the largest (unit-scaled rows) dropped, then once more by CholQR
   if (c.deflate) {
     const int z = r + 1;
-    k_cert_zbasis<<<(L + 255) / 256, 256, 0, t->stream>>>(c.Xt, r, c.Zr, L);
+    if (!c.halted()) k_cert_zbasis<<<(L + 255) / 256, 256, 0, t->stream>>>(c.Xt, r, c.Zr, L);
     c.gram(c.Zr, z, z, c.Zr, z, z, c.slot(4));
+    c.reduce({{c.slot(4), z * z}});
+    if (c.dead()) return x->fail();
     std::vector<double> gz((size_t)z * z);
-    HIPC(hipMemcpyAsync(gz.data(), c.slot(4), sizeof(double) * z * z, hipMemcpyDeviceToHost, t->stream));
-    HIPC(hipStreamSynchronize(t->stream));
+    CK(hipMemcpyAsync(gz.data(), c.slot(4), sizeof(double) * z * z, hipMemcpyDeviceToHost, t->stream));
+    CK(hipStreamSynchronize(t->stream));
     std::vector<double> d(z), B((size_t)z * z), mu, Vz;
     for (int p = 0; p < z; ++p) d[p] = gz[p * z + p] > 0 ? 1.0 / std::sqrt(gz[p * z + p]) : 0.0;
     for (int p = 0; p < z; ++p)
@@ -476,33 +526,53 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
     double *hc = t->h_cert.p + 4 * Cert::SLOT;
     for (int p = 0; p < z; ++p)
       for (int k = 0; k < c.nz; ++k) hc[p * c.nz + k] = d[p] * Vz[(size_t)p * z + keep[k]] / std::sqrt(mu[keep[k]]);
-    HIPC(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * z * c.nz, hipMemcpyHostToDevice, t->stream));
+    CK(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * z * c.nz, hipMemcpyHostToDevice, t->stream));
     c.update(c.Zo, c.nz, c.nz, 0.0, {CertTerm{c.Zr, c.slot(7), z, z, 1.0}});
     c.cholqr(c.Zo, c.nz, c.nz, c.Zr);
   }
-  // starting block: fixed pseudo-random numbers (the call is a function of the iterate alone)
-  {
+  // starting block: fixed pseudo-random numbers (the call is a function of the iterate alone).  Across teams each
+  // participant draws its own columns of the single team's block: the generator skipped ahead to the global position
+  // (robots by id, then poses) of each of its robots
+  if (!c.halted()) {
     double *h = t->h_cert.p + 5 * Cert::SLOT;  // (behind the coefficients, whose upload may still be queued)
-    unsigned long long s = 0x2545F4914F6CDD1Dull;
-    for (size_t i = 0; i < (size_t)K * Ls; ++i) {
-      s = s * 6364136223846793005ull + 1442695040888963407ull;
-      h[i] = (double)(s >> 11) / 9007199254740992.0 - 0.5;
+    if (!x) {
+      unsigned long long s = 0x2545F4914F6CDD1Dull;
+      for (size_t i = 0; i < (size_t)K * Ls; ++i) {
+        s = s * 6364136223846793005ull + 1442695040888963407ull;
+        h[i] = (double)(s >> 11) / 9007199254740992.0 - 0.5;
+      }
+    } else {
+      size_t o = 0;
+      for (auto &a : t->ag) {
+        const size_t cnt = (size_t)K * 4 * a->n;
+        unsigned long long s = lcg_skip(0x2545F4914F6CDD1Dull, (unsigned long long)K * 4 * x->robot_goff[a->id]);
+        for (size_t i = 0; i < cnt; ++i) {
+          s = s * 6364136223846793005ull + 1442695040888963407ull;
+          h[o + i] = (double)(s >> 11) / 9007199254740992.0 - 0.5;
+        }
+        o += cnt;
+      }
     }
-    HIPC(hipMemcpyAsync(c.T, h, sizeof(double) * K * Ls, hipMemcpyHostToDevice, t->stream));
-    HIPC(hipStreamSynchronize(t->stream));  // (the pinned image is reused for the read-backs)
+    CK(hipMemcpyAsync(c.T, h, sizeof(double) * K * Ls, hipMemcpyHostToDevice, t->stream));
+    CK(hipStreamSynchronize(t->stream));  // (the pinned image is reused for the read-backs)
   }
   int cur = 0;
   c.update(c.U[cur], K3, K, 0.0, {CertTerm{c.T, nullptr, K, K, 1.0}});
   c.project(c.U[cur], K3, K);
   c.cholqr(c.U[cur], K3, K, c.T);
   c.cholqr(c.U[cur], K3, K, c.T);
-  HIPC(hipGetLastError());
+  CK(hipGetLastError());
   // Gershgorin bound on |S| (once per call)
   std::vector<double> gm((size_t)c.na * c.gstride);
-  HIPC(hipMemcpyAsync(gm.data(), c.gmax, sizeof(double) * gm.size(), hipMemcpyDeviceToHost, t->stream));
-  HIPC(hipStreamSynchronize(t->stream));
+  CK(hipMemcpyAsync(gm.data(), c.gmax, sizeof(double) * gm.size(), hipMemcpyDeviceToHost, t->stream));
+  CK(hipStreamSynchronize(t->stream));
   double s_bound = 0.0;
-  for (double x : gm) s_bound = std::max(s_bound, x);
+  for (double g : gm) s_bound = std::max(s_bound, g);
+  if (x) {
+    std::vector<double> mine{0.0, s_bound};
+    if (x->gather(mine, x->hall)) return x->fail();
+    for (int q = 0; q < x->world; ++q) s_bound = std::max(s_bound, x->hall[2 * q + 1]);
+  }
   const double eta_abs = (flags & DPGO_CERT_ETA_RELATIVE) ? eta * s_bound : eta;
   const double tol_abs = tol * s_bound;
 
@@ -511,12 +581,14 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
   double theta0 = 0.0, res0 = 0.0;
   std::vector<double> y0(K, 0.0);
   for (it = 0; it < max_iters; ++it) {
+    if (c.dead()) return x->fail();
     double *U = c.U[cur], *AU = c.AU[cur];
     double *X = U, *W = U + K, *P = U + 2 * K, *AX = AU, *AW = AU + K;
     // AX = P S X;  R = AX - X (X^T AX)
     c.apply(K, X, K3, AX, K3, true);
     c.project(AX, K3, K);
     c.gram(X, K3, K, AX, K3, K, c.slot(4));
+    c.reduce({{c.slot(4), K * K}});
     c.update(W, K3, K, 0.0, {CertTerm{AX, nullptr, K3, K, 1.0}, CertTerm{X, c.slot(4), K3, K, -1.0}});
     c.gram(W, K3, K, W, K3, K, c.slot(2));
     if (c.precond) {
@@ -529,10 +601,18 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
     const int nb = it == 0 ? 2 * K : K3;
     c.gram(U, K3, nb, AU, K3, nb, c.slot(0));
     c.gram(U, K3, nb, U, K3, nb, c.slot(1));
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(hG, c.G, sizeof(double) * 4 * Cert::SLOT, hipMemcpyDeviceToHost, t->stream));
-    HIPC(hipStreamSynchronize(t->stream));
-    if (hG[3 * Cert::SLOT] != 0.0) { set_err("certify: the block lost rank (Cholesky of its Gram matrix failed)"); return DPGO_ERR; }
+    // (across teams: the residual Gram of slot 2 travels with the basis Grams -- the Cholesky word of slot 3 needs no
+    // reduction, it comes from summed Grams and is the same on every participant)
+    c.reduce({{c.slot(0), nb * nb}, {c.slot(1), nb * nb}, {c.slot(2), K * K}});
+    if (c.dead()) return x->fail();
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(hG, c.G, sizeof(double) * 4 * Cert::SLOT, hipMemcpyDeviceToHost, t->stream));
+    CK(hipStreamSynchronize(t->stream));
+    if (hG[3 * Cert::SLOT] != 0.0) {
+      set_err("certify: the block lost rank (Cholesky of its Gram matrix failed)");
+      if (x) x->finish();  // (the same on every participant: the closing status word keeps the sequence)
+      return DPGO_ERR;
+    }
     const double *G1 = hG, *G2 = hG + Cert::SLOT, *Grr = hG + 2 * Cert::SLOT;
     // Ritz pairs of X: M = X^T S X (the X block of G1)
     std::vector<double> M((size_t)K * K), th, Y;
@@ -560,7 +640,11 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
     std::vector<int> keep;
     for (int k = 0; k < nb; ++k) if (mu[k] > 1e-10 * mu_max) keep.push_back(k);
     const int nk = (int)keep.size();
-    if (nk < K) { set_err("certify: the search space collapsed below the block size"); return DPGO_ERR; }
+    if (nk < K) {
+      set_err("certify: the search space collapsed below the block size");
+      if (x) x->finish();
+      return DPGO_ERR;
+    }
     std::vector<double> Tm((size_t)nb * nk);  // basis -> orthonormal coordinates
     for (int p = 0; p < nb; ++p)
       for (int k = 0; k < nk; ++k) Tm[(size_t)p * nk + k] = d[p] * Vb[(size_t)p * nb + keep[k]] / std::sqrt(mu[keep[k]]);
@@ -580,7 +664,7 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
         for (int k = 0; k < nk; ++k) s += Tm[(size_t)p * nk + k] * Y2[(size_t)k * nk + q];
         hc[p * K + q] = s;
       }
-    HIPC(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * nb * K, hipMemcpyHostToDevice, t->stream));
+    CK(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * nb * K, hipMemcpyHostToDevice, t->stream));
     const int nxt = 1 - cur;
     double *Un = c.U[nxt], *AUn = c.AU[nxt];
     c.update(Un, K3, K, 0.0, {CertTerm{U, c.slot(7), K3, nb, 1.0}});
@@ -599,17 +683,36 @@ int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int
   out->iterations = std::min(it + 1, max_iters);
   out->block = K;
   out->deflated = c.deflate ? 1 : 0;
-  if (v) {
+  if (v && !c.halted()) {
     double *hc = hG + 4 * Cert::SLOT;
     for (int p = 0; p < K; ++p) hc[p] = y0[p];
-    HIPC(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+    CK(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
     c.update(c.T2, 1, 1, 0.0, {CertTerm{c.U[cur], c.slot(7), K3, K, 1.0}});
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(v, c.T2, sizeof(double) * Ls, hipMemcpyDeviceToHost, t->stream));
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(v, c.T2, sizeof(double) * Ls, hipMemcpyDeviceToHost, t->stream));
   }
-  HIPC(hipStreamSynchronize(t->stream));
+  CK(hipStreamSynchronize(t->stream));
+  if (x && x->finish()) return DPGO_ERR;
   return 0;
+#undef CK
 }
+
+}  // namespace dpgo_cert
+
+extern "C" {
+
+int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int block, int flags, dpgo_certificate_t *out,
+                      double *v) {
+  if (!t || !out) { set_err("certify: null argument"); return DPGO_ERR; }
+  const int K = block > 0 ? block : t->prm.r;
+  if (K < 3 || K > 8) { set_err("certify: the block size must lie in 3..8"); return DPGO_ERR; }
+  if (max_iters < 1 || !(tol > 0) || !(eta >= 0)) { set_err("certify: max_iters >= 1, tol > 0 and eta >= 0 required"); return DPGO_ERR; }
+  if (check_team(t, "certify")) return DPGO_ERR;
+  Cert c;
+  c.t = t;
+  return certify_body(c, eta, tol, max_iters, K, flags, out, v);
+}
+
 
 // staircase step, host arithmetic: [X; 0] + alpha [0; v^T], rotation blocks back onto the Stiefel manifold (polar factor)
 int dpgo_escape_point(const double *X, int r, int num_poses, const double *v, double alpha, double *X_out) {

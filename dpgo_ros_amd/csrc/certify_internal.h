@@ -1,8 +1,10 @@
 // certify_internal.h -- the certificate's device workspace and host helpers (certify.hip), shared with the rounding of a
-// certified point (round.hip).  The kernels stay in certify.hip; Cert's launching methods are defined there.
+// certified point (round.hip) and with the calls across teams (certify_across.hip).  The kernels stay in certify.hip;
+// Cert's launching methods are defined there.
 #pragma once
 #include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kernel_common.h"
@@ -36,9 +38,12 @@ using namespace dpgo_host;
 // columns of V (row-major, V[i * n + k] = component i of vector k)
 void jacobi_eig(int n, std::vector<double> A, std::vector<double> &w, std::vector<double> &V);
 
+struct Across;
+
 // the certificate's device state for one call
 struct Cert {
   dpgo_team_t *t = nullptr;
+  Across *x = nullptr;  // across teams (certify_across.hip): halo exchange inside apply, reductions through the transport
   int r = 0, K = 0, na = 0, N = 0, L = 0, max_n = 0, nz = 0;  // nz: rows of the orthonormal deflation basis Zo
   bool deflate = true, precond = true;
   double *Xt = nullptr, *E = nullptr, *lam = nullptr, *Zr = nullptr, *Zo = nullptr;
@@ -62,9 +67,73 @@ struct Cert {
   // rows of V orthonormal: V <- L^-1 V (CholQR) through scratch S (k rows, ld k)
   void cholqr(double *V, int ld, int k, double *S);
   void precondition(const double *V, int ldv, double *out, int ldo);
+  // across teams: the listed device arrays summed over the participants in rank order, in place (no-op for one team)
+  void reduce(std::initializer_list<std::pair<double *, int>> parts);
+  bool halted() const;  // across teams: this participant failed or the collective did -- no more device work
+  bool dead() const;  // across teams: the collective found a failure -- every participant returns DPGO_ERR
 };
+
+// across teams: the transport, the agreement of the participants, the halo plan and the failure protocol
+// (certify_across.hip).  A participant that fails locally sets `bad`: it launches nothing more but keeps to
+// the sequence of transport calls up to the next allgather, whose status word makes every participant set `dead`; from
+// then on nobody calls the transport and every participant returns DPGO_ERR.
+struct Across {
+  const dpgo_transport_t *tr = nullptr;
+  std::string what;
+  int rank = 0, world = 1, num_robots = 0;
+  std::vector<int> owner;
+  bool bad = false, dead = false, all_precond = true;
+  std::string err;
+  // global numbering: robots by id, then poses
+  std::vector<int> robot_n, robot_holder, robot_lidx;
+  std::vector<long long> robot_goff;
+  long long nglob = 0;
+  // halo plan: this team's public poses per peer (team pose index) and where received poses land (halo slot), both in
+  // plan order -- by peer rank, then (sending robot, receiving robot, frame)
+  std::vector<int> scol, rdst, hoffs;
+  std::vector<long long> sent_p, recv_p;  // poses per peer
+  int halo_slots = 0;
+  int *d_scol = nullptr, *d_rdst = nullptr, *d_hoff = nullptr;
+  double *d_halo = nullptr, *d_send = nullptr, *d_recv = nullptr;
+  std::vector<double> hsend, hrecv, hred[2], hall;
+  int hflip = 0;
+  long long n_allgather = 0, n_exchange = 0;
+
+  // local checks, the agreement record (two allgathers) and the plan; DPGO_ERR on every participant when they disagree.
+  // argerr: this participant's arguments are invalid (the others learn it from the record)
+  int begin(dpgo_team_t *t, const dpgo_transport_t *tr_, const int *owner_, const char *what_, int op, int K, int flags,
+            double eta, double tol, int max_iters, const char *argerr);
+  size_t dev_doubles() const { return (size_t)(halo_slots + scol.size() + rdst.size()) * 4 * 8 + 8; }
+  size_t dev_ints() const { return scol.size() + rdst.size() + hoffs.size() + 1; }
+  // carve the device tables out of d_cert / d_cert_int (behind the caller's part) and upload them
+  void place(double *d, int *di, hipStream_t s);
+  void note(hipError_t e, int line);
+  void fail_local(const std::string &m);
+  // the halo of the k-row block V (ld ldv): pack, exchange, unpack.  Returns the device halo ([(4 slot + c) k + b])
+  const double *halo_of(Cert &c, int k, const double *V, int ldv);
+  // allgather of mine = [status, payload...]: `all` receives world records of that length
+  int gather(std::vector<double> &mine, std::vector<double> &all);
+  // the listed device arrays summed (or maximised) over the participants in rank order, in place
+  int reduce(Cert &c, std::initializer_list<std::pair<double *, int>> parts, bool take_max = false);
+  const double *reduced() const { return hred[1 - hflip].data() + 1; }  // the host copy of the last reduce
+  int finish();  // the closing status word: DPGO_ERR on every participant when any failed
+  int fail();    // set_err(what: err), DPGO_ERR
+};
+
+// a HIP step: DPGO_ERR for one team; across teams the error is noted (and the step skipped once this participant has halted)
+#define CERT_CK(c, expr)                                \
+  do {                                                  \
+    if ((c).x) {                                        \
+      if (!(c).halted()) (c).x->note((expr), __LINE__); \
+    } else {                                            \
+      HIPC(expr);                                       \
+    }                                                   \
+  } while (0)
 
 // every robot local and INITIALIZED, every neighbour inside the team; descriptors synchronised.  `what` prefixes the message.
 int check_team(dpgo_team_t *t, const char *what);
+
+// the LOBPCG of dpgo_team_certify on a Cert whose t (and x, across teams) is set (certify.hip)
+int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flags, dpgo_certificate_t *out, double *v);
 
 }  // namespace dpgo_cert

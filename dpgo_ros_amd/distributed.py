@@ -553,3 +553,90 @@ class DistributedRBCD:
             t = torch_module.tensor([self.be.partial_cost()], dtype=torch_module.float64, device=device)
             self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
             return float(t.item())
+
+
+# ---- the certificate and the rounding across ranks (csrc/certify_across.hip) ----
+from .capi import Transport as _Transport  # noqa: E402
+
+
+class TorchTransport(_Transport):
+    """dpgo_transport_t over torch.distributed: `all_gather` of float64 tensors and batch_isend_irecv for the non-zero
+    counts of an exchange.  gloo moves CPU tensors; other backends (nccl = RCCL) device tensors, copied in and out.
+    group: a sub-group (its ranks are the transport's ranks) or None for the whole world."""
+
+    def __init__(self, dist, group=None, device=None):
+        import torch
+        super().__init__(dist.get_rank(group), dist.get_world_size(group))
+        self.dist, self.group, self.torch = dist, group, torch
+        if device is None:
+            device = torch.device("cpu") if dist.get_backend(group) == "gloo" else \
+                torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+
+    def _peer(self, p):
+        return p if self.group is None else self.dist.get_global_rank(self.group, p)
+
+    def allgather(self, x):
+        t = self.torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
+        outs = [self.torch.empty_like(t) for _ in range(self.world)]
+        self.dist.all_gather(outs, t, group=self.group)
+        return np.concatenate([o.cpu().numpy() for o in outs])
+
+    def exchange(self, parts, recv_counts):
+        ops, got = [], [np.zeros(0)] * self.world
+        bufs = {}
+        for p in range(self.world):
+            if p == self.rank:
+                got[p] = np.array(parts[p], dtype=np.float64)
+                continue
+            if len(parts[p]):
+                t = self.torch.from_numpy(np.ascontiguousarray(parts[p], dtype=np.float64)).to(self.device)
+                ops.append(self.dist.P2POp(self.dist.isend, t, self._peer(p), self.group))
+            if int(recv_counts[p]):
+                bufs[p] = self.torch.empty(int(recv_counts[p]), dtype=self.torch.float64, device=self.device)
+                ops.append(self.dist.P2POp(self.dist.irecv, bufs[p], self._peer(p), self.group))
+        if ops:
+            for req in self.dist.batch_isend_irecv(ops):
+                req.wait()
+        for p, b in bufs.items():
+            got[p] = b.cpu().numpy()
+        return got
+
+
+def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8, max_iters=1000, block=0,
+                      refine_translations=True, certify_kw=None):
+    """The certificate and the SE-Sync rounding of an iterate split across ranks (one team per rank), with global results on
+    every rank that owns a robot: dict(T = the rounded poses of all robots in global order (robots by id), certificate,
+    rounding, f_relaxed, f_rounded, gap_rel as in capi.solve_certified).  Every rank of the world calls (ranks that own no
+    robot are left out through a sub-group, whose creation is collective) and gets None back when it owns none."""
+    owners = sorted(set(int(o) for o in owner_of_robot))
+    group = None
+    if dist.get_world_size() != len(owners):
+        group = dist.new_group(owners)
+    team = getattr(backend_or_team, "team", backend_or_team)
+    if dist.get_rank() not in owners:
+        return None
+    own = np.array([owners.index(int(o)) for o in owner_of_robot], dtype=np.int32)
+    tr = TorchTransport(dist, group)
+    cert, _ = team.certify(eta=eta, tol=tol, max_iters=max_iters, block=block, transport=tr, owner_of_robot=own,
+                           **(certify_kw or {}))
+    rd, T = team.round(refine_translations=refine_translations, transport=tr, owner_of_robot=own)
+    # every rank's poses, padded to one length, then placed by robot id
+    ids = list(team.ids)
+    head = np.array([len(ids)] + ids + [team.agents[i].n for i in ids], dtype=np.float64)
+    sizes = tr.allgather(np.array([head.size, T.size], dtype=np.float64)).reshape(tr.world, 2).astype(int)
+    L = int(sizes.sum(1).max())
+    mine = np.zeros(L)
+    mine[:head.size], mine[head.size:head.size + T.size] = head, T
+    allr = tr.allgather(mine).reshape(tr.world, L)
+    blocks = {}
+    for q in range(tr.world):
+        k = int(allr[q, 0])
+        rid, rn = allr[q, 1:1 + k].astype(int), allr[q, 1 + k:1 + 2 * k].astype(int)
+        o = 1 + 2 * k
+        for i, n in zip(rid, rn):
+            blocks[int(i)] = allr[q, o:o + 12 * n]
+            o += 12 * n
+    Tg = np.concatenate([blocks[i] for i in sorted(blocks)])
+    gap = (rd.f_rounded - rd.f_relaxed) / rd.f_relaxed if cert.certified == 1 else None
+    return dict(T=Tg, certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed, f_rounded=rd.f_rounded, gap_rel=gap)

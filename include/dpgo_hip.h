@@ -313,6 +313,37 @@ int dpgo_team_round(dpgo_team_t *t, int flags, double *T, dpgo_rounding_t *out);
  * single-robot numbering); translations of T overwritten.  Stage 2 of dpgo_chordal_init, with its two paths in the same
  * cases.  DPGO_ERR with a message when edges of positive weight do not join every pose to pose 0. */
 int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, int nm, int num_poses, double *T);
+/* ---- certificate and rounding across teams (csrc/certify_across.hip) ----
+ * A participant is one team that holds a subset of the robots; owner_rank_of_robot[num_robots] says which participant holds
+ * each (the meaning of dpgo_team_attach_comm).  The library does not own the transport: it calls the two functions below,
+ * host memory in and out, on the calling thread.  Every participant enters the same calls in the same order.
+ *   allgather: every participant passes n doubles; out receives world * n doubles in rank order.
+ *   exchange:  send_counts[p] doubles to participant p (send packed in rank order), recv_counts[p] from p into recv (packed
+ *              in rank order); both ends know the counts in advance, zero counts included.
+ * Both return 0 on success.  A transport that fails or times out makes the calling participant return DPGO_ERR. */
+typedef struct {
+  void *ctx;
+  int rank, world; /* this participant, number of participants */
+  int (*allgather)(void *ctx, const double *in, int n, double *out);
+  int (*exchange)(void *ctx, const double *send, const long long *send_counts, double *recv, const long long *recv_counts);
+} dpgo_transport_t;
+/* The three calls of the single team over a split problem.  V / out / v / T hold this team's columns (poses) in team order;
+ * every scalar output is bitwise identical on every participant, and one participant holding every robot reproduces
+ * dpgo_team_certificate_apply / _certify / _round bit for bit.  The first allgather carries an agreement record (block,
+ * r, num_robots, flags, eta, tol, max_iters, the owner table, this team's robots); a disagreement, a robot held by no or two
+ * participants, an uninitialised robot anywhere, a participant without robots, or a local failure later on (allocation,
+ * device error) makes every participant return DPGO_ERR at the next allgather, with a message that names the rank.
+ * Transport calls: certify 2 exchanges + 8 allgathers per LOBPCG iteration that continues (2 + 5 in the last); the set-up
+ * and the closing status add a fixed few.  Changes no solver state. */
+int dpgo_team_certificate_apply_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, int K,
+                                       const double *V, double *out);
+int dpgo_team_certify_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, double eta,
+                             double tol, int max_iters, int block, int flags, dpgo_certificate_t *out, double *v);
+/* anchored at robot 0's first pose; DPGO_ROUND_REFINE_TRANSLATIONS: every participant gathers the owned measurements and
+ * the rounded rotations of all and solves the same translation problem (global numbering: robots by id, then poses), then
+ * keeps its own poses' translations */
+int dpgo_team_round_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, int flags, double *T,
+                           dpgo_rounding_t *out);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
