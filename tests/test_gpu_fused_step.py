@@ -169,6 +169,24 @@ def test_one_launch_iterations_follow_the_oracle():
     th.close()
 
 
+@pytest.mark.parametrize("r", [6, 7, 8])
+def test_ranks_above_five_keep_the_two_launch_sequence_and_follow_the_oracle(r):
+    """step_fe_supported serves r = 3..5 only: a team at r = 6..8 asked for the one-launch form runs the two-launch sequence
+    (counters[7] stays 0) and follows the oracle as closely as the two-launch runs of test_gpu_parity.py do"""
+    th = _team("sphere2500", 5, True, r=r, **RGD)
+    m, mp, n = load("sphere2500", 5)
+    to = O.Team(mp, n, O.default_params(r=r, num_robots=5, **RGD))
+    to.set_initial(O.odometry_init(m, n), O.fixed_stiefel(r))
+    th.run(40)
+    th.synchronize()
+    for _ in range(40):
+        to.iterate()
+    assert th.counters()[7] == 0
+    for k in th.ids:
+        assert np.abs(th.agents[k].get_X() - to.agents[k].get_X()).max() < 1e-10
+    th.close()
+
+
 def test_teams_the_one_launch_form_cannot_serve_keep_the_two_launch_sequence():
     """agents beyond 512 poses (torus3D / 8: 625), agents of <= 256 poses (sphere2500 / 10), the two-level form, no
     acceleration: dpgo_team_run runs, counters[7] stays 0"""

@@ -18,7 +18,7 @@ def scratch_team():
     t.close()
 
 
-@pytest.mark.parametrize("r", [3, 4, 5, 6, 8])
+@pytest.mark.parametrize("r", [3, 4, 5, 6, 7, 8])
 def test_manifold_ops(r):
     rng = np.random.default_rng(r)
     n = 257
@@ -563,7 +563,7 @@ def test_long_rows_take_the_csr_tail():
     th.close()
 
 
-@pytest.mark.parametrize("r", [3, 4, 6, 8])
+@pytest.mark.parametrize("r", [3, 4, 6, 7, 8])
 @pytest.mark.parametrize("method", [capi.METHOD_RGD, capi.METHOD_RTR])
 def test_other_relaxation_ranks(r, method):
     kw = dict(method=method, acceleration=1, rgd_stepsize=0.2, restart_interval=5, gradnorm_tol=1e-2)

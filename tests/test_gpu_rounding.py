@@ -52,7 +52,7 @@ def test_lifted_chordal_point_rounds_to_chordal(ds, N):
 
 
 @pytest.mark.parametrize("ds,N", [("smallGrid3D", 3), ("sphere2500", 5)])
-@pytest.mark.parametrize("r", [5, 8])
+@pytest.mark.parametrize("r", [5, 7, 8])
 def test_random_point_matches_numpy(ds, N, r):
     m, n = capi.read_g2o(os.path.join(DATA, ds + ".g2o"))
     X = random_manifold_point(np.random.default_rng(20 + r), r, n)

@@ -34,7 +34,7 @@ def _handoffs(team, agent):
     return int(out[17 * 16]) if rc == 0 else 0
 
 
-@pytest.mark.parametrize("r", [3, 4, 5, 6, 8])
+@pytest.mark.parametrize("r", [3, 4, 5, 6, 7, 8])
 def test_one_launch_solve_equals_the_launch_per_step_sequence_and_the_oracle(r):
     N, iters = 3, 12
     kw = dict(method=capi.METHOD_RTR, acceleration=1, restart_interval=5, gradnorm_tol=1e-3, rtr_iterations=3, rtr_tcg_iterations=30)
