@@ -83,6 +83,15 @@ class Rounding(C.Structure):
                    self.reflected, self.refined, self.num_degenerate))
 
 
+class Covariance(C.Structure):
+    _fields_ = [("n", C.c_int), ("logdet", C.c_double), ("min_pivot", C.c_double), ("max_pivot", C.c_double),
+                ("seconds_assemble", C.c_double), ("seconds_invert", C.c_double)]
+
+    def __repr__(self):
+        return ("Covariance(n=%d, logdet=%.12g, min_pivot=%.6g, max_pivot=%.6g, seconds_assemble=%.3g, seconds_invert=%.3g)"
+                % (self.n, self.logdet, self.min_pivot, self.max_pivot, self.seconds_assemble, self.seconds_invert))
+
+
 METHOD_RTR, METHOD_RGD = 0, 1
 COST_L2, COST_L1, COST_HUBER, COST_TLS, COST_GM, COST_GNC_TLS = 0, 1, 2, 3, 4, 5
 WEIGHT_LIBRARY, WEIGHT_WRAPPER = 0, 1
@@ -114,7 +123,8 @@ dpgo_comm_allreduce_sum dpgo_comm_allreduce_max dpgo_team_attach_comm dpgo_team_
 dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_iteration_log dpgo_team_run_simultaneous_ranks
 dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
 dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
-dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across""".split()
+dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
+dpgo_team_marginal_covariances""".split()
 
 
 class DpgoError(RuntimeError):
@@ -957,6 +967,46 @@ class Team:
                  "round_across")
         return res, T
 
+    def covariances(self, T=None, pairs=None):
+        """Marginal pose covariances at the trajectory T (12 doubles per pose in team order; None: the rounding of the
+        current iterate, self.round()): (Covariance, diag[N, 6, 6], cross[len(pairs), 6, 6]).  Pose i is perturbed by
+        (phi, delta), rotation first: R_i <- R_i Exp(phi) (body frame), t_i <- t_i + delta (world frame); pose 0 is held
+        fixed (its blocks are zero).  The blocks are those of the inverse of the cost's Hessian at the measurements' current
+        weights; cross[k] is the block of the pose pair pairs[k] = (a, b).  Raises DpgoError when T is not in SE(3), the
+        weighted graph is disconnected, the dense Hessian does not fit the device, or T is not a minimum (a non-positive
+        pivot).  Changes no solver state."""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("covariances: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        res, diag, cross = Covariance(), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
+        _chk(lib().dpgo_team_marginal_covariances(self.h, _d(T), 0, len(pr), _d(pr) if len(pr) else None, _d(diag),
+                                                  _d(cross) if len(pr) else None, C.byref(res)), "marginal_covariances")
+        return res, diag, cross
+
+
+def covariance_to_body_frame(cov, T):
+    """Blocks of Team.covariances in the convention that perturbs the translation in the body frame as well (GTSAM's Pose3:
+    t_i <- t_i + R_i delta'): A Sigma A^T with A_i = blockdiag(I, R_i^T).  cov: diagonal blocks [N, 6, 6] with T the
+    trajectory (12 doubles per pose), or cross blocks [K, 6, 6] with T = (T_a, T_b): the trajectories' poses of each pair,
+    e.g. (Tm[pairs[:, 0]], Tm[pairs[:, 1]]) for Tm = T.reshape(N, 12)."""
+    cov = np.asarray(cov, dtype=np.float64)
+
+    def A_of(Tx):
+        R = np.asarray(Tx, dtype=np.float64).reshape(-1, 4, 3)[:, :3, :].transpose(0, 2, 1)  # [pose][b][c]
+        A = np.zeros((len(R), 6, 6))
+        A[:, :3, :3] = np.eye(3)
+        A[:, 3:, 3:] = R.transpose(0, 2, 1)
+        return A
+
+    Aa, Ab = (A_of(T[0]), A_of(T[1])) if isinstance(T, tuple) else (A_of(T),) * 2
+    if len(Aa) != len(cov) or len(Ab) != len(cov):
+        raise ValueError("covariance_to_body_frame: %d blocks, %d / %d poses" % (len(cov), len(Aa), len(Ab)))
+    return Aa @ cov @ Ab.transpose(0, 2, 1)
+
 
 def _params_at_rank(params, r):
     p = Params.from_buffer_copy(params)
@@ -1034,18 +1084,23 @@ def _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, 
 
 
 def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None,
-                    refine_translations=True, certify_kw=None, device=0):
+                    refine_translations=True, certify_kw=None, device=0, covariances=False):
     """End to end: the Riemannian staircase, then the SE-Sync rounding of its final point (Team.round on the final team).
     Returns dict(T=trajectory, 12 doubles per pose in team order anchored at the first pose, r=final rank, ranks,
     certificate, rounding=Rounding, f_relaxed, f_rounded, gap_rel, escape_costs).  gap_rel = (f_rounded - f_relaxed) /
     f_relaxed bounds the relative suboptimality of T (up to the certificate's eta) when the point is certified; it is None
-    otherwise."""
+    otherwise.  covariances=True adds covariances=(Covariance, diag[N, 6, 6]): Team.covariances of the final team at T."""
     def round_final(team, out):
         out["rounding"], out["T"] = team.round(refine_translations=refine_translations)
+        if covariances:
+            out["covariances"] = team.covariances(out["T"])[:2]
 
     out = _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, None, 30, certify_kw, device,
                      on_final=round_final)
     rd, cert = out["rounding"], out["certificate"]
     gap = (rd.f_rounded - rd.f_relaxed) / rd.f_relaxed if cert.certified == 1 else None
-    return dict(T=out["T"], r=out["r"], ranks=out["ranks"], certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed,
-                f_rounded=rd.f_rounded, gap_rel=gap, escape_costs=out["escape_costs"])
+    res = dict(T=out["T"], r=out["r"], ranks=out["ranks"], certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed,
+               f_rounded=rd.f_rounded, gap_rel=gap, escape_costs=out["escape_costs"])
+    if covariances:
+        res["covariances"] = out["covariances"]
+    return res

@@ -9,6 +9,7 @@
 
 #include <mutex>
 #include <random>
+#include "certify_internal.h"
 #include "team_internal.h"
 
 using namespace dpgo;
@@ -2250,3 +2251,81 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
 }
 
 }  // extern "C"
+
+// ---- marginal pose covariances (covariance.hip): every refusal that can be decided on the host comes first
+extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
+                                              double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
+  const char *what = "marginal_covariances";
+  if (res) std::memset(res, 0, sizeof *res);
+  if (!t || !T || !cov_diag || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))) {
+    set_err(std::string(what) + ": null argument");
+    return DPGO_ERR;
+  }
+  if (flags != 0) { set_err(std::string(what) + ": flags must be 0"); return DPGO_ERR; }
+  if (dpgo_cert::check_team_local(t, what)) return DPGO_ERR;
+  const int na = (int)t->ag.size();
+  std::vector<int> offs(na + 1, 0);
+  for (int k = 0; k < na; ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
+  const int N = offs[na];
+  // T in SE(3): R column-major in the first 9 of the 12 doubles of a pose
+  for (int g = 0; g < N; ++g) {
+    const double *R = T + (size_t)12 * g;
+    double orth = 0.0;
+    for (int p = 0; p < 3; ++p)
+      for (int q = 0; q < 3; ++q) {
+        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
+        orth = std::max(orth, std::fabs(d));
+      }
+    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
+    bool finite = true;
+    for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(R[k]);
+    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "%s: pose %d of T is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", what, g, orth, det);
+      set_err(buf);
+      return DPGO_ERR;
+    }
+  }
+  for (int k = 0; k < 2 * num_pairs; ++k)
+    if (pairs[k] < 0 || pairs[k] >= N) {
+      set_err(std::string(what) + ": pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) +
+              ", outside [0, " + std::to_string(N) + ")");
+      return DPGO_ERR;
+    }
+  {
+    std::vector<dpgo_measurement_t> mm;
+    if (dpgo_cert::team_measurements(t, offs, what, mm)) return DPGO_ERR;
+    if (check_joined_to_pose0(mm.data(), (int)mm.size(), N, what)) return DPGO_ERR;
+  }
+  if (N < 2) {  // the anchor alone: nothing is free
+    std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
+    if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
+    return DPGO_OK;
+  }
+  HIPC(hipSetDevice(t->device));
+  {
+    // three dense matrices of order 6 (N - 1); idle pooled buffers count as used memory but are one flush away from free
+    // (the accounting of the preconditioner budget, assembly.hip)
+    const double n = 6.0 * (N - 1), need = 3.0 * n * n * 8.0;
+    size_t free_b = 0, total_b = 0;
+    HIPC(hipMemGetInfo(&free_b, &total_b));
+    const double avail = (double)free_b + (double)pool_held(t->device);
+    if (need > avail) {
+      char buf[240];
+      std::snprintf(buf, sizeof buf, "%s: the dense Hessian of order %.0f and its inverse need %.0f bytes, %.0f are available on the device",
+                    what, n, need, avail);
+      set_err(buf);
+      return DPGO_ERR;
+    }
+  }
+  const int rc = dpgo_cert::covariance_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res);
+  if (rc > 0) {
+    std::memset(res, 0, sizeof *res);
+    const int row = rc - 1;
+    set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(row) + " of the reduced Hessian (pose " +
+            std::to_string(row / 6 + 1) + "): the Hessian is not positive definite at this T: not a minimum");
+    return DPGO_ERR;
+  }
+  if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
+  return rc;
+}

@@ -326,6 +326,17 @@ void jacobi_eig(int n, std::vector<double> A, std::vector<double> &w, std::vecto
   V.swap(V2);
 }
 
+void launch_cert_apply3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *V, double *out,
+                        const double *lam) {
+  k_cert_apply<3><<<dim3(spmm_grid(3, max_n), na), 64, 0, s>>>(agents, off, V, 3, out, 3, lam, nullptr, nullptr);
+}
+
+void launch_cert_lambda3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *X,
+                         const double *E, double *lam, double *gmax) {
+  const int gstride = (max_n + 255) / 256;
+  k_cert_lambda<3><<<dim3(gstride, na), 256, 0, s>>>(agents, off, X, E, lam, gmax, gstride);
+}
+
 int Cert::setup(int K_) {
   K = K_;
   r = t->prm.r;
@@ -432,7 +443,7 @@ void Cert::precondition(const double *V, int ldv, double *out, int ldo) {
   DPGO_DISPATCH_R(K,(k_cert_precond<R><<<dim3(4 * max_n, na), 256, 0, t->stream>>>(t->d_agents.p, off, V, ldv, out, ldo)));
 }
 
-int check_team(dpgo_team_t *t, const char *what) {
+int check_team_local(dpgo_team_t *t, const char *what) {
   if ((int)t->ag.size() != t->prm.num_robots) {
     set_err(std::string(what) + ": the team must hold every robot (num_local == num_robots)");
     return DPGO_ERR;
@@ -442,6 +453,11 @@ int check_team(dpgo_team_t *t, const char *what) {
       set_err(std::string(what) + ": robot " + std::to_string(a->id) + " is not initialized");
       return DPGO_ERR;
     }
+  return 0;
+}
+
+int check_team(dpgo_team_t *t, const char *what) {
+  if (check_team_local(t, what)) return DPGO_ERR;
   if (sync_descs(t)) return DPGO_ERR;
   for (auto &a : t->ag)
     for (const auto &d : a->se_host)

@@ -132,8 +132,28 @@ struct Across {
 
 // every robot local and INITIALIZED, every neighbour inside the team; descriptors synchronised.  `what` prefixes the message.
 int check_team(dpgo_team_t *t, const char *what);
+// its first half: every robot local and initialized, decided on the host without touching the device
+int check_team_local(dpgo_team_t *t, const char *what);
+
+// the rank-3 forms of the certificate's kernels for a trajectory T in the iterate layout (3 x 4N, ld 3; covariance.hip):
+// out = T Q (lam null) or T S, one team;  Lambda_i = Sym(R_i^T E_i,rot) into lam (9 per pose), gmax: na x ceil(max_n / 256)
+// doubles of scratch (the Gershgorin sums k_cert_lambda leaves)
+void launch_cert_apply3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *V, double *out,
+                        const double *lam);
+void launch_cert_lambda3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *X,
+                         const double *E, double *lam, double *gmax);
+
+// the team's measurements with their current weights in team-order pose numbering (robot fields zeroed), each shared
+// edge once: the copy of the lower robot, which owns its weight.  offs: pose offsets of the local agents (na + 1)
+int team_measurements(dpgo_team_t *t, const std::vector<int> &offs, const char *what, std::vector<dpgo_measurement_t> &mm);
 
 // the LOBPCG of dpgo_team_certify on a Cert whose t (and x, across teams) is set (certify.hip)
 int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flags, dpgo_certificate_t *out, double *v);
+
+
+// the device part of dpgo_team_marginal_covariances (covariance.hip; the host-side refusals are in capi.hip): DPGO_OK,
+// DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian was not positive
+int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
+                      dpgo_covariance_t *res);
 
 }  // namespace dpgo_cert

@@ -418,26 +418,31 @@ extern "C" int dpgo_chordal_init(int device, const dpgo_measurement_t *m, int nm
   return rc;
 }
 
-extern "C" int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, int nm, int num_poses, double *T) {
-  if (!m || nm < 0 || num_poses <= 0 || !T) { set_err("translations_given_rotations: null argument"); return DPGO_ERR; }
-  const int n = num_poses;
-  // every endpoint inside [0, n); every pose joined to pose 0 by edges of positive weight (else the Laplacian is singular)
+// every endpoint inside [0, n); every pose joined to pose 0 by edges of positive weight (else the Laplacian is singular)
+int dpgo_host::check_joined_to_pose0(const dpgo_measurement_t *m, int nm, int n, const char *what) {
   std::vector<int> parent(n);
   for (int i = 0; i < n; ++i) parent[i] = i;
   auto root = [&](int i) { while (parent[i] != i) i = parent[i] = parent[parent[i]]; return i; };
   for (int e = 0; e < nm; ++e) {
     if (m[e].p1 < 0 || m[e].p1 >= n || m[e].p2 < 0 || m[e].p2 >= n) {
-      set_err("translations_given_rotations: measurement " + std::to_string(e) + " has an end point outside [0, num_poses)");
+      set_err(std::string(what) + ": measurement " + std::to_string(e) + " has an end point outside [0, num_poses)");
       return DPGO_ERR;
     }
     if (m[e].weight * m[e].tau > 0.0) parent[root(m[e].p1)] = root(m[e].p2);
   }
   for (int i = 0; i < n; ++i)
     if (root(i) != root(0)) {
-      set_err("translations_given_rotations: pose " + std::to_string(i) + " is not joined to pose 0 by edges of positive "
+      set_err(std::string(what) + ": pose " + std::to_string(i) + " is not joined to pose 0 by edges of positive "
               "weight (the weighted graph is disconnected: singular Laplacian)");
       return DPGO_ERR;
     }
+  return 0;
+}
+
+extern "C" int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, int nm, int num_poses, double *T) {
+  if (!m || nm < 0 || num_poses <= 0 || !T) { set_err("translations_given_rotations: null argument"); return DPGO_ERR; }
+  const int n = num_poses;
+  if (dpgo_host::check_joined_to_pose0(m, nm, n, "translations_given_rotations")) return DPGO_ERR;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipSetDevice(device) != hipSuccess) {
     set_err("translations_given_rotations: no usable HIP device");

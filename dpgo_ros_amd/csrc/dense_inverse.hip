@@ -81,7 +81,7 @@ __device__ __forceinline__ void potrf_diag_body(const InvJob &jb_, int kb, int *
 #pragma unroll
   for (int k = 0; k < NB; ++k) {
     double d = lane_bcast(row[k], k);
-    if (!(d > 0.0)) { if (lane == 0) fail[z] = k0 + k + 1; d = 1.0; }
+    if (!(d > 0.0)) { if (lane == 0 && fail[z] == 0) fail[z] = k0 + k + 1; d = 1.0; }  // (the FIRST one: what follows it is not meaningful)
     const double inv = rsqrt_nr(d);
     const double lik = (lane == k) ? d * inv : ((lane > k) ? row[k] * inv : 0.0);  // L[i][k]
     row[k] = lik;

@@ -360,6 +360,36 @@ struct RoundWs {
 
 }  // namespace
 
+namespace dpgo_cert {
+
+int team_measurements(dpgo_team_t *t, const std::vector<int> &offs, const char *what, std::vector<dpgo_measurement_t> &mm) {
+  std::vector<dpgo_measurement_t> ma;
+  mm.clear();
+  for (size_t k = 0; k < t->ag.size(); ++k) {
+    const int id = t->ag[k]->id;
+    const int cntm = dpgo_agent_get_measurements(t, id, nullptr);
+    if (cntm < 0) return DPGO_ERR;
+    ma.resize(cntm);
+    if (cntm > 0 && dpgo_agent_get_measurements(t, id, ma.data()) != cntm) return DPGO_ERR;
+    for (const auto &m : ma) {
+      if (m.r1 != m.r2 && std::min(m.r1, m.r2) != id) continue;
+      const auto l1 = t->id2local.find(m.r1), l2 = t->id2local.find(m.r2);
+      if (l1 == t->id2local.end() || l2 == t->id2local.end()) {
+        set_err(std::string(what) + ": a measurement names a robot outside the team");
+        return DPGO_ERR;
+      }
+      dpgo_measurement_t q = m;
+      q.r1 = q.r2 = 0;
+      q.p1 = offs[l1->second] + m.p1;
+      q.p2 = offs[l2->second] + m.p2;
+      mm.push_back(q);
+    }
+  }
+  return 0;
+}
+
+}  // namespace dpgo_cert
+
 extern "C" {
 
 int dpgo_team_round(dpgo_team_t *t, int flags, double *T, dpgo_rounding_t *out) {
@@ -418,24 +448,8 @@ int dpgo_team_round(dpgo_team_t *t, int flags, double *T, dpgo_rounding_t *out) 
   // each shared edge once (the copy of the lower robot, which owns its weight)
   std::vector<int> offs(c.na + 1, 0);
   for (int k = 0; k < c.na; ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
-  std::vector<dpgo_measurement_t> mm, ma;
-  for (int k = 0; k < c.na; ++k) {
-    const int id = t->ag[k]->id;
-    const int cntm = dpgo_agent_get_measurements(t, id, nullptr);
-    if (cntm < 0) return DPGO_ERR;
-    ma.resize(cntm);
-    if (cntm > 0 && dpgo_agent_get_measurements(t, id, ma.data()) != cntm) return DPGO_ERR;
-    for (const auto &m : ma) {
-      if (m.r1 != m.r2 && std::min(m.r1, m.r2) != id) continue;
-      const auto l1 = t->id2local.find(m.r1), l2 = t->id2local.find(m.r2);
-      if (l1 == t->id2local.end() || l2 == t->id2local.end()) { set_err("round: a measurement names a robot outside the team"); return DPGO_ERR; }
-      dpgo_measurement_t q = m;
-      q.r1 = q.r2 = 0;
-      q.p1 = offs[l1->second] + m.p1;
-      q.p2 = offs[l2->second] + m.p2;
-      mm.push_back(q);
-    }
-  }
+  std::vector<dpgo_measurement_t> mm;
+  if (team_measurements(t, offs, "round", mm)) return DPGO_ERR;
   if (dpgo_translations_given_rotations(t->device, mm.data(), (int)mm.size(), N, T)) {
     set_err(std::string("round: ") + dpgo_last_error());
     return DPGO_ERR;

@@ -399,6 +399,11 @@ int sync_descs_noflush(dpgo_team *t);  // the same without the upload (used whil
 int flush_stage(dpgo_team *t);
 int stage_to_pinned(dpgo_team *t, Agent &a, int *n0, int *n1);
 
+// ---- chordal.hip
+// every end point inside [0, n) and every pose joined to pose 0 by edges of positive weight, else DPGO_ERR with a message
+// that `what` prefixes (dpgo_translations_given_rotations, dpgo_team_marginal_covariances)
+int check_joined_to_pose0(const dpgo_measurement_t *m, int nm, int n, const char *what);
+
 // ---- solve.hip
 bool acquire_fused_rtr_lock(dpgo_team *t);
 void release_fused_rtr_lock(dpgo_team *t);

@@ -313,6 +313,30 @@ int dpgo_team_round(dpgo_team_t *t, int flags, double *T, dpgo_rounding_t *out);
  * single-robot numbering); translations of T overwritten.  Stage 2 of dpgo_chordal_init, with its two paths in the same
  * cases.  DPGO_ERR with a message when edges of positive weight do not join every pose to pose 0. */
 int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, int nm, int num_poses, double *T);
+/* ---- marginal pose covariances of a trajectory (csrc/covariance.hip) ----
+ * T = (R_i, t_i) in team order, the layout dpgo_team_round returns.  Pose i is perturbed by xi_i = (phi_i, delta_i), rotation
+ * first:  R_i <- R_i Exp(phi_i) (body frame),  t_i <- t_i + delta_i (world frame).  H = the Hessian at xi = 0 of the team's
+ * cost 1/2 <T, T Q> (current weights) in these 6N coordinates; pose 0 (the anchor of dpgo_team_round) is held fixed:
+ * H_red = H without its first 6 rows and columns, Sigma = H_red^-1 (the Laplace approximation of the posterior under the
+ * cost's own noise model).  H is assembled on the device from S = Q - Lambda(T) (the certificate's operator at rank 3) and
+ * inverted there by the blocked fp64 Cholesky of the dense preconditioner: three square matrices of 6(N-1) doubles a side. */
+typedef struct {
+  int n;                 /* 6 (N - 1): the order of H_red */
+  double logdet;         /* log det H_red = 2 sum_k log L_kk, summed in index order */
+  double min_pivot;      /* smallest and largest L_kk^2 of the Cholesky factor */
+  double max_pivot;
+  double seconds_assemble; /* device time (events on the team's stream): Lambda, clearing and filling H_red */
+  double seconds_invert;   /* ... Cholesky, triangular inverse, W^T W */
+} dpgo_covariance_t;
+/* cov_diag: the N diagonal 6 x 6 blocks of Sigma, 36 doubles each, row-major, bitwise symmetric (pose 0: zeros);
+ * cov_pairs (may be NULL when num_pairs is 0): the blocks Sigma_ab for pairs[2k] = a, pairs[2k + 1] = b (a pair that names
+ * pose 0: zeros).  flags: 0.  All robots local and INITIALIZED.  Refused with DPGO_ERR and a message before any device work:
+ * T outside SE(3) (|R^T R - I| or |det R - 1| above 1e-8), a pair index outside [0, N), positive-weight edges that do not
+ * join every pose to pose 0, 3 x n^2 x 8 bytes above the free device memory.  Refused after the factorisation: a
+ * non-positive pivot (T is not a minimum).  A refused call leaves cov_diag / cov_pairs untouched and *res all zero.
+ * Changes no solver state; two calls give the same bits. */
+int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
+                                   double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
 /* ---- certificate and rounding across teams (csrc/certify_across.hip) ----
  * A participant is one team that holds a subset of the robots; owner_rank_of_robot[num_robots] says which participant holds
  * each (the meaning of dpgo_team_attach_comm).  The library does not own the transport: it calls the two functions below,
