@@ -52,41 +52,22 @@ __global__ void k_apply_sym(const double *B, const double *M, double *out, int N
   for (int a = 0; a < RR; ++a) out[(size_t)c * RR + a] = acc[a];
 }
 
-// nearest rotation to each 3x3 block (column-major, 9 doubles per pose), det-corrected
+// nearest rotation to each 3x3 block (column-major, 9 doubles per pose): the rounding's routine (device_math.h), which divides
+// by no singular value -- a relaxed block of rank two, one or zero (loop closures that disagree shrink it) still gives a
+// proper rotation, and an ill-conditioned one is resolved to its own conditioning
 __global__ void k_project_so3(double *Rm, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  double A[9];
+  double A[3][4], R[3][3];
 #pragma unroll
-  for (int e = 0; e < 9; ++e) A[e] = Rm[(size_t)9 * i + e];
-  double S[9], w[3], V[9];
-  gram3<3>(A, S);
-  sym3_eig(S, w, V);
-  const double det = A[0] * (A[4] * A[8] - A[7] * A[5]) - A[3] * (A[1] * A[8] - A[7] * A[2]) + A[6] * (A[1] * A[5] - A[4] * A[2]);
-  int kmin = 0;
-  if (w[1] < w[kmin]) kmin = 1;
-  if (w[2] < w[kmin]) kmin = 2;
-  double Mx[9], T[9];
+  for (int c = 0; c < 3; ++c)
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
+    for (int k = 0; k < 3; ++k) A[k][c] = Rm[(size_t)9 * i + 3 * c + k];
+  (void)rd_nearest_rotation(A, R);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      double s = 0;
+  for (int c = 0; c < 3; ++c)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) s += ((k == kmin && det < 0) ? -1.0 : 1.0) * V[3 * p + k] * V[3 * q + k] / sqrt(w[k]);
-      Mx[3 * p + q] = s;
-    }
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      double s = 0;
-#pragma unroll
-      for (int p = 0; p < 3; ++p) s += A[p * 3 + a] * Mx[3 * p + q];
-      T[q * 3 + a] = s;
-    }
-#pragma unroll
-  for (int e = 0; e < 9; ++e) Rm[(size_t)9 * i + e] = T[e];
+    for (int k = 0; k < 3; ++k) Rm[(size_t)9 * i + 3 * c + k] = R[k][c];
 }
 
 }  // namespace dpgo
@@ -279,6 +260,7 @@ int dense_translations(hipStream_t s, const dpgo_measurement_t *m, int nm, int n
   A.add(0, 0, 1.0);
   for (int e = 0; e < nm; ++e) {
     const int i = m[e].p1, j = m[e].p2;
+    if (i == j) continue;  // (a self-loop constrains nothing; the team path skips it too)
     const double tau = m[e].weight * m[e].tau;
     const double *Ri = T + (size_t)12 * i;
     double v[3];
@@ -291,6 +273,11 @@ int dense_translations(hipStream_t s, const dpgo_measurement_t *m, int nm, int n
   if (dense_solve<3>(s, A.triplets(), n, B, X) != 0) return DPGO_ERR;
   for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) T[(size_t)12 * i + 9 + a] = X[(size_t)i * 3 + a];
   return DPGO_OK;
+}
+
+bool all_finite(const double *T, int n) {
+  for (size_t k = 0; k < (size_t)12 * n; ++k) if (!std::isfinite(T[k])) return false;
+  return true;
 }
 
 bool dense_only() {
@@ -365,11 +352,13 @@ extern "C" int dpgo_chordal_init(int device, const dpgo_measurement_t *m, int nm
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipSetDevice(device) != hipSuccess) return DPGO_ERR;
   {
     // (needs at least one edge into pose 0 -- the pin is a shared edge -- and falls back to the dense path on any failure)
-    if (!dense_only() && num_poses >= 2 && num_poses <= DPGO_MAX_POSE_INDEX && chordal_via_team(device, m, nm, num_poses, T) == DPGO_OK)
+    // (poses that are not finite -- a singular system the explicit inverse went through -- count as a failure)
+    if (!dense_only() && num_poses >= 2 && num_poses <= DPGO_MAX_POSE_INDEX && chordal_via_team(device, m, nm, num_poses, T) == DPGO_OK &&
+        all_finite(T, num_poses))
       return DPGO_OK;
   }
   hipStream_t s;
-  if (hipStreamCreate(&s) != hipSuccess) return DPGO_ERR;
+  if (hipStreamCreate(&s) != hipSuccess) { set_err("chordal_init: hipStreamCreate failed"); return DPGO_ERR; }
   const int n = num_poses;
   int rc = DPGO_OK;
   const bool dup = has_parallel_edges(m, nm, n);
@@ -383,6 +372,7 @@ extern "C" int dpgo_chordal_init(int device, const dpgo_measurement_t *m, int nm
     for (int a = 0; a < 3; ++a) { add(a, a, 1.0); B[(size_t)a * 3 + a] = 1.0; }
     for (int e = 0; e < nm; ++e) {
       const int i = m[e].p1, j = m[e].p2;
+      if (i == j) continue;  // (a self-loop: its two off-diagonal scatters would overwrite one another)
       const double k = m[e].weight * m[e].kappa;
       // k |R_j - R_i R~|^2:  A_ii += kI, A_jj += kI, A_ij += -k R~, A_ji += -k R~^T  (X A = B convention)
       if (i != 0) for (int a = 0; a < 3; ++a) add(3 * i + a, 3 * i + a, k);
@@ -415,6 +405,9 @@ extern "C" int dpgo_chordal_init(int device, const dpgo_measurement_t *m, int nm
   }
   if (rc == DPGO_OK) rc = dense_translations(s, m, nm, n, dup, T);  // ---- stage 2: translations, t_0 = 0
   (void)hipStreamDestroy(s);
+  if (rc == DPGO_OK && !all_finite(T, n)) rc = DPGO_ERR;
+  if (rc != DPGO_OK)
+    set_err("chordal_init: the dense solve failed (a singular system: is every pose joined to pose 0 by edges of positive weight?)");
   return rc;
 }
 
@@ -449,7 +442,8 @@ extern "C" int dpgo_translations_given_rotations(int device, const dpgo_measurem
     return DPGO_ERR;
   }
   // the same two paths as dpgo_chordal_init, in the same cases
-  if (!dense_only() && n >= 2 && n <= DPGO_MAX_POSE_INDEX && translations_via_team(device, m, nm, n, T) == DPGO_OK) return DPGO_OK;
+  if (!dense_only() && n >= 2 && n <= DPGO_MAX_POSE_INDEX && translations_via_team(device, m, nm, n, T) == DPGO_OK && all_finite(T, n))
+    return DPGO_OK;
   hipStream_t s;
   if (hipStreamCreate(&s) != hipSuccess) { set_err("translations_given_rotations: hipStreamCreate failed"); return DPGO_ERR; }
   const int rc = dense_translations(s, m, nm, n, has_parallel_edges(m, nm, n), T);

@@ -72,6 +72,129 @@ __device__ __forceinline__ void gram3(const double *A, double S[9]) {
     }
 }
 
+// ---- nearest rotation to a 3 x 3 block (the SE-Sync rounding of round.hip and the projection of chordal.hip).  Blocks
+// are A[k][c], k the row, in rows of FOUR doubles: the rounding keeps the translation in the fourth column.
+__device__ __forceinline__ double rd_det3(const double A[3][4]) {
+  return A[0][0] * (A[1][1] * A[2][2] - A[2][1] * A[1][2]) - A[0][1] * (A[1][0] * A[2][2] - A[2][0] * A[1][2]) +
+         A[0][2] * (A[1][0] * A[2][1] - A[2][0] * A[1][1]);
+}
+
+// (v, p, q) a right-handed orthonormal frame for the unit vector v: p from the axis least aligned with v, q = v x p
+__device__ __forceinline__ void rd_complement(const double v[3], double p[3], double q[3]) {
+  int e = 0;
+  if (fabs(v[1]) < fabs(v[e])) e = 1;
+  if (fabs(v[2]) < fabs(v[e])) e = 2;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = ((k == e) ? 1.0 : 0.0) - v[e] * v[k];
+  const double n = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] /= n;
+  q[0] = v[1] * p[2] - v[2] * p[1];
+  q[1] = v[2] * p[0] - v[0] * p[2];
+  q[2] = v[0] * p[1] - v[1] * p[0];
+}
+
+// nearest rotation to the 3 x 3 block A (A[k][c], c < 3), degenerate blocks included.  With A^T A = V diag(w) V^T (w
+// descending: v1, v2, v3), w1 = A v1 / |A v1| and w2 = A v2 orthogonalised against w1 and normalised, the nearest rotation
+// is w1 v1^T + w2 v2^T + det(V) (w1 x w2) v3^T -- for det A > 0 and det A < 0 alike -- and needs no division by the smallest
+// singular value.  Returns true when that value is below 1e-12 of the largest (then the third direction is the cross
+// product, and w2 an arbitrary unit vector orthogonal to w1 when the second is as small too; a zero block gives I).
+__device__ __forceinline__ bool rd_nearest_rotation(const double A[3][4], double Rm[3][3]) {
+  double S[9], w[3], V[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) S[3 * c + d] = A[0][c] * A[0][d] + A[1][c] * A[1][d] + A[2][c] * A[2][d];
+  sym3_eig(S, w, V);
+  int i1 = 0, i3 = 0;
+  if (w[1] > w[i1]) i1 = 1;
+  if (w[2] > w[i1]) i1 = 2;
+  if (w[1] < w[i3]) i3 = 1;
+  if (w[2] < w[i3]) i3 = 2;
+  if (i3 == i1) i3 = (i1 + 1) % 3;  // (all three equal)
+  const int i2 = 3 - i1 - i3;
+  double v1[3], v2[3], v3[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    v1[c] = V[3 * c + i1];
+    v2[c] = V[3 * c + i2];
+    v3[c] = V[3 * c + i3];
+  }
+  double u1[3], u2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    u1[k] = A[k][0] * v1[0] + A[k][1] * v1[1] + A[k][2] * v1[2];
+    u2[k] = A[k][0] * v2[0] + A[k][1] * v2[1] + A[k][2] * v2[2];
+  }
+  const double s1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+  if (!(s1 > 0.0)) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Rm[k][c] = (k == c) ? 1.0 : 0.0;
+    return true;
+  }
+  double w1[3] = {u1[0] / s1, u1[1] / s1, u1[2] / s1};
+  if (w[i2] < 1e-4 * w[i1]) {
+    // s2 < 1e-2 s1: v2 and v3, eigenvectors of A^T A, are resolved only to eps s1^2 / (s2^2 - s3^2) (1e-4 at singular
+    // values 1, 1e-6, 1e-7), and the rotation built on them inherits that.  Resolve the complement of v1 as its own 2-D
+    // problem instead: right-handed frames (v1, p, q) and (w1, s, t), C = [s t]^T A [p q], and the 2-D rotation nearest
+    // to C maps (p, q) to (s, t); the answer is then determined to eps s1 / (s2 + s3), the problem's own conditioning.
+    double p[3], q[3], s[3], t[3];
+    rd_complement(v1, p, q);
+    rd_complement(w1, s, t);
+    double ap[3], aq[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      ap[k] = A[k][0] * p[0] + A[k][1] * p[1] + A[k][2] * p[2];
+      aq[k] = A[k][0] * q[0] + A[k][1] * q[1] + A[k][2] * q[2];
+    }
+    const double c11 = s[0] * ap[0] + s[1] * ap[1] + s[2] * ap[2], c12 = s[0] * aq[0] + s[1] * aq[1] + s[2] * aq[2];
+    const double c21 = t[0] * ap[0] + t[1] * ap[1] + t[2] * ap[2], c22 = t[0] * aq[0] + t[1] * aq[1] + t[2] * aq[2];
+    // tr(R2^T C) = cos (c11 + c22) + sin (c21 - c12) is largest at the angle of (c11 + c22, c21 - c12)
+    const double a = c11 + c22, b = c21 - c12;
+    const double h = sqrt(a * a + b * b), h2 = sqrt((c11 - c22) * (c11 - c22) + (c21 + c12) * (c21 + c12));
+    const double cs = h > 0.0 ? a / h : 1.0, sn = h > 0.0 ? b / h : 0.0;
+    const double sg2 = 0.5 * (h + h2);  // the larger singular value of C: s2
+    const bool degenerate = !(sg2 > 1e-12 * s1) || fabs(rd_det3(A)) < 1e-12 * s1 * s1 * sg2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        Rm[k][c] = w1[k] * v1[c] + (cs * s[k] + sn * t[k]) * p[c] + (cs * t[k] - sn * s[k]) * q[c];
+    return degenerate;
+  }
+  const double d12 = w1[0] * u2[0] + w1[1] * u2[1] + w1[2] * u2[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) u2[k] -= d12 * w1[k];
+  double s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+  bool degenerate = false;
+  if (!(s2 > 1e-12 * s1)) {
+    // rank one: w2 from the axis least aligned with w1
+    degenerate = true;
+    int e = 0;
+    if (fabs(w1[1]) < fabs(w1[e])) e = 1;
+    if (fabs(w1[2]) < fabs(w1[e])) e = 2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) u2[k] = ((k == e) ? 1.0 : 0.0) - w1[e] * w1[k];
+    s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+  } else {
+    // smallest singular value from |det A| = s1 s2 s3 (the eigenvalue of A^T A cannot resolve it below 1e-8 s1)
+    if (fabs(rd_det3(A)) < 1e-12 * s1 * s1 * s2) degenerate = true;
+  }
+  const double w2[3] = {u2[0] / s2, u2[1] / s2, u2[2] / s2};
+  const double detV = v1[0] * (v2[1] * v3[2] - v2[2] * v3[1]) - v1[1] * (v2[0] * v3[2] - v2[2] * v3[0]) +
+                      v1[2] * (v2[0] * v3[1] - v2[1] * v3[0]);
+  const double sg = detV < 0.0 ? -1.0 : 1.0;
+  const double w3[3] = {sg * (w1[1] * w2[2] - w1[2] * w2[1]), sg * (w1[2] * w2[0] - w1[0] * w2[2]),
+                        sg * (w1[0] * w2[1] - w1[1] * w2[0])};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Rm[k][c] = w1[k] * v1[c] + w2[k] * v2[c] + w3[k] * v3[c];
+  return degenerate;
+}
+
 // polar factor through the symmetric eigen-decomposition:  A (A^T A)^{-1/2}   (any full-rank A)
 template <int R>
 __device__ __forceinline__ void polar_eig_inplace(double *A) {
