@@ -119,7 +119,6 @@ dpgo_team_t *dpgo_team_create(int device, const dpgo_params_t *p, int num_local,
     if (const char *e6 = std::getenv("DPGO_FE_MIN_N")) t->fe_min_n = std::max(32, std::atoi(e6));
     if (const char *e7 = std::getenv("DPGO_FE_CARRY")) t->use_fe_carry = (e7[0] == '0') ? 0 : 1;
     if (const char *e8 = std::getenv("DPGO_FE_DEEP")) t->use_fe_deep = (e8[0] == '0') ? 0 : 1;
-    if (const char *e9 = std::getenv("DPGO_FE_PERSIST")) t->use_fe_persist = (e9[0] == '1') ? 1 : 0;
     if (const char *e10 = std::getenv("DPGO_REPORT_TAIL")) t->use_report_tail = (e10[0] == '0') ? 0 : 1;
     if (const char *e11 = std::getenv("DPGO_REPORT_PREFETCH")) t->prefetch_reports = (e11[0] == '0') ? 0 : 1;
     if (t->d_nest_all.alloc(3 * std::max(1, num_local)) ||
@@ -146,29 +145,13 @@ void dpgo_team_destroy(dpgo_team_t *t) {
   close_iteration_log(t);
   release_fused_rtr_lock(t);
   if (t->rtr_lock_fd >= 0) { ::close(t->rtr_lock_fd); t->rtr_lock_fd = -1; }
-  for (auto &kv : t->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
+  drop_graphs(t);
   for (auto &kv : t->peers) if (kv.second.base) (void)hipIpcCloseMemHandle(kv.second.base);
   for (void *p : t->mail_handles) if (p) (void)hipIpcCloseMemHandle(p);
   t->ag.clear();
   if (t->h_block) pinned_give(t->h_block, t->h_block_bytes, false);
   if (t->own_stream) stream_give(t->device, t->stream);  // (drained above)
   delete t;
-}
-
-// An in-kernel exchange that timed out (codes: 2 hand-off of the one-launch RTR solve, 3 two-level preconditioner, 4 mailbox
-// of the device-side UPDATE token) leaves its code in a pinned word.  Every entry point that has just drained the team's
-// stream looks at it, so a time-out is an error at the next host read-back whichever call that is (advisor, round 3: only
-// dpgo_team_synchronize did, and the run_peer path never called it).
-static int check_exchange_error(dpgo_team_t *t) {
-  if (!t->h_bar_err || !*t->h_bar_err) return 0;
-  const int code = *t->h_bar_err;
-  *t->h_bar_err = 0;
-  for (auto &kv : t->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-  t->graphs.clear(); t->graph_flip.clear();
-  set_err("an in-kernel exchange timed out (code " + std::to_string(code) + ": 2 hand-off of the one-launch RTR solve, 3 two-level "
-          "preconditioner, 4 mailbox of the device-side UPDATE token, 5 hand-off of the persistent RGD launch): the iterates since the last "
-          "successful synchronisation are invalid");
-  return DPGO_ERR;
 }
 
 int dpgo_team_num_local(const dpgo_team_t *t) { return (int)t->ag.size(); }
@@ -434,8 +417,8 @@ static int finish_report(dpgo_team_t *t, Agent *a) {
     }
   }
   // diagnostics (dpgo_team_get_counters [5..6]): host time between the launch of a report and its arrival (us), reports
-  t->counters[5] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - rp.t_launch).count();
-  t->counters[6] += 1;
+  t->counters[CNT_REPORT_WAIT_US] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - rp.t_launch).count();
+  t->counters[CNT_REPORTS] += 1;
   for (auto &b : t->ag) b->up_pending = false;  // this team's stream has drained past every upload enqueued before
   release_fused_rtr_lock(t);                    // ... and past any one-launch solve (also when it timed out: the device lock
                                                 // must not stay with a team that is about to report an error)
@@ -492,9 +475,8 @@ static int report_prepare(dpgo_team_t *t, Agent *a) {
 
 static int report_after_iterate(dpgo_team_t *t, Agent *a, bool did_opt, bool advance, bool upload, bool one_seq = false,
                                 bool whole_iterate_false = false, bool wait = true) {
-  const bool want_status = did_opt && !t->prm.status_every_iterate && (a->opt_rel_src == 1 || a->opt_rel_src == 5);
-  const bool tiles = a->opt_rel_src == 5;
-  const int scnt = want_status ? (tiles ? (a->n + 63) / 64 : precond_nblk(*a)) : 0;
+  const bool want_status = did_opt && !t->prm.status_every_iterate && (a->opt_rel_src == REL_FUSED_B || a->opt_rel_src == REL_TILES_E);
+  const StatusSpan st = status_span(*a, want_status ? a->opt_rel_src : REL_NONE);
   const int ppb = 64 / t->prm.r, nb = (a->n + ppb - 1) / ppb;
   const bool want_opt = did_opt && a->opt_pending_rgd;
   if (report_prepare(t, a)) return DPGO_ERR;
@@ -506,7 +488,7 @@ static int report_after_iterate(dpgo_team_t *t, Agent *a, bool did_opt, bool adv
     launch_iterate_false(t->ctx(), a->local, a->n, t->prm.num_robots, t->prm.restart_interval, a->d_pubpos_ptr.p, a->d_pubpos.p,
                          a->h_down.p, a->d_report_seq.p, a->d_report_seq.p + 1, a->h_up_idx.p, a->h_up.p, up0, up1);
   } else
-  launch_report(t->ctx(), a->local, a->d_pub_all.p, a->n_pub_all, a->h_down.p, tiles ? PART_E : PART_B + 2, scnt, PART_STRIDE,
+  launch_report(t->ctx(), a->local, a->d_pub_all.p, a->n_pub_all, a->h_down.p, st.off, st.cnt, st.stride,
                 want_opt ? nb : 0, a->d_report_seq.p, advance ? 1 : 0, t->prm.acceleration, t->prm.num_robots,
                 t->prm.restart_interval, a->h_up_idx.p, a->h_up.p, up0, up1, one_seq ? 1 : 0);
   a->rep.pending = true; a->rep.expect = expect; a->rep.epoch = t->epoch; a->rep.one_seq = one_seq;
@@ -537,7 +519,7 @@ int dpgo_agent_iterate(dpgo_team_t *t, int id, int do_optimization) {
   const bool will_report = t->prm.acceleration || opt || a->publish_requested;
   // an accelerated iterate(false) is ONE launch (k_iterate_false): Nesterov step, staged poses, bookkeeping and report
   const bool one_launch = defer_upload && !t->prm.status_every_iterate;
-  if (one_launch) a->rel_src = 0;
+  if (one_launch) a->rel_src = REL_TILES_D;
   // iterate(true) with a local solve: the report is offered to the call's last launch (solve.hip takes it when that is the
   // closing statistics evaluation of a fused RGD step; anything else -- RTR, a restart iteration, the line search -- leaves it,
   // and k_report follows as a launch of its own)
@@ -556,16 +538,16 @@ int dpgo_agent_iterate(dpgo_team_t *t, int id, int do_optimization) {
   const bool folded = offer && t->rep_offer.taken;
   t->rep_offer = dpgo_team::ReportOffer();
   if (rc) return rc;
-  if (do_optimization) mark_optimized(t, *a, opt ? (a->rel_src == 1 ? 1 : 5) : 2, opt);
+  if (do_optimization) mark_optimized(t, *a, opt ? (a->rel_src == REL_FUSED_B ? REL_FUSED_B : REL_TILES_E) : REL_NONE, opt);
   a->iter++;
   if (t->prm.acceleration || opt) a->publish_requested = true;
   if (folded) {
     // (what report_after_iterate would have asked k_report for: the status of a fused step -- PART_B partials -- and the
     // result of an RGD solve; an RTR solve leaves its record in pinned memory itself)
-    if (a->opt_rel_src != 1) { set_err("internal: folded report on a path without the fused status partials"); return DPGO_ERR; }
+    if (a->opt_rel_src != REL_FUSED_B) { set_err("internal: folded report on a path without the fused status partials"); return DPGO_ERR; }
     a->rep.pending = true; a->rep.expect = ++a->report_seq; a->rep.epoch = t->epoch; a->rep.one_seq = false;
     a->rep.want_status = true; a->rep.want_opt = a->opt_pending_rgd; a->rep.t_launch = tq0;
-    t->counters[10] += 1;
+    t->counters[CNT_REPORT_TAILS] += 1;
     const int rr = finish_report(t, a);
     if (rr) return rr;
   } else if (will_report) {
@@ -581,6 +563,18 @@ int dpgo_agent_iterate(dpgo_team_t *t, int id, int do_optimization) {
   return a->last_success ? DPGO_OK : DPGO_NOT_READY;
 }
 
+// the |X - XPrev|^2 partials a status source names, read back and summed in their fixed order
+static int read_status_sum(dpgo_team_t *t, const Agent &a, int src, double *sum) {
+  const StatusSpan st = status_span(a, src);
+  std::vector<double> part((size_t)st.cnt * st.stride);
+  HIPC(hipMemcpyAsync(part.data(), a.dev.part + st.off, sizeof(double) * ((size_t)(st.cnt - 1) * st.stride + 1),
+                      hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipStreamSynchronize(t->stream));
+  *sum = 0;
+  for (int k = 0; k < st.cnt; ++k) *sum += part[(size_t)k * st.stride];
+  return DPGO_OK;
+}
+
 int dpgo_agent_get_status(dpgo_team_t *t, int id, dpgo_status_t *s) {
   Agent *a = find_agent(t, id);
   if (!a) return DPGO_ERR;
@@ -589,20 +583,10 @@ int dpgo_agent_get_status(dpgo_team_t *t, int id, dpgo_status_t *s) {
   const bool robust = t->prm.robust_cost_type != DPGO_COST_L2;
   if (!t->prm.status_every_iterate) {
     // the status block describes the agent's last iterate(true)
-    if (!a->has_X || a->opt_rel_src < 0) return DPGO_OK;
+    if (!a->has_X || a->opt_rel_src == REL_NEVER) return DPGO_OK;
     if (!a->opt_cached) {
       double sum = 0;
-      if (a->opt_rel_src != 2) {
-        const bool tiles = a->opt_rel_src == 5;
-        const int cnt = tiles ? (a->n + 63) / 64 : precond_nblk(*a);
-        const int off = tiles ? PART_E : PART_B + 2;
-        std::vector<double> part((size_t)cnt * PART_STRIDE);
-        HIPC(hipMemcpyAsync(part.data(), a->dev.part + off, sizeof(double) * ((size_t)(cnt - 1) * PART_STRIDE + 1),
-                            hipMemcpyDeviceToHost, t->stream));
-        HIPC(hipStreamSynchronize(t->stream));
-        if (check_exchange_error(t)) return DPGO_ERR;
-        for (int k = 0; k < cnt; ++k) sum += part[(size_t)k * PART_STRIDE];
-      }
+      if (a->opt_rel_src != REL_NONE && (read_status_sum(t, *a, a->opt_rel_src, &sum) || check_exchange_error(t))) return DPGO_ERR;
       a->opt_rel_change = std::sqrt(sum / a->n);
       a->opt_cached = true;
     }
@@ -611,17 +595,10 @@ int dpgo_agent_get_status(dpgo_team_t *t, int id, dpgo_status_t *s) {
                             (!robust || a->opt_ratio >= t->prm.robust_opt_min_convergence_ratio);
     return DPGO_OK;
   }
-  if (!a->has_X || a->iter == 0 || a->rel_src == 2) { s->ready_to_terminate = a->has_X && a->iter > 0 && a->last_success; return DPGO_OK; }
+  if (!a->has_X || a->iter == 0 || a->rel_src == REL_NONE) { s->ready_to_terminate = a->has_X && a->iter > 0 && a->last_success; return DPGO_OK; }
   // |X - XPrev|^2 partials were left by the last kernel that moved X (fixed summation order)
-  const int cnt = a->rel_src == 4 ? a->n : (a->rel_src ? precond_nblk(*a) : (a->n + 63) / 64);
-  const int stride = a->rel_src == 4 ? 1 : PART_STRIDE;
-  const int off = a->rel_src == 1 ? PART_B + 2 : PART_D;
-  std::vector<double> part((size_t)cnt * stride);
-  HIPC(hipMemcpyAsync(part.data(), a->dev.part + off, sizeof(double) * ((size_t)(cnt - 1) * stride + 1),
-                      hipMemcpyDeviceToHost, t->stream));
-  HIPC(hipStreamSynchronize(t->stream));
   double sum = 0;
-  for (int k = 0; k < cnt; ++k) sum += part[(size_t)k * stride];
+  if (read_status_sum(t, *a, a->rel_src, &sum)) return DPGO_ERR;
   s->relative_change = std::sqrt(sum / a->n);
   s->ready_to_terminate = a->last_success && (s->relative_change <= t->prm.rel_change_tol) &&
                           (!robust || converged_ratio(*a) >= t->prm.robust_opt_min_convergence_ratio);
@@ -1112,357 +1089,6 @@ int dpgo_team_exchange_all(dpgo_team_t *t) {
   return 0;
 }
 
-int dpgo_team_step_begin(dpgo_team_t *t, int sel_id) {
-  if (sync_descs(t)) return DPGO_ERR;
-  auto it = t->id2local.find(sel_id);
-  const int sel = (it == t->id2local.end()) ? -2 : it->second;
-  const bool restart = t->prm.acceleration && ((t->iter + 2) % t->prm.restart_interval) == 0;
-  return enqueue_team_iteration(t, false, restart, sel, 1);
-}
-
-int dpgo_team_step_end(dpgo_team_t *t, int sel_id) {
-  auto it = t->id2local.find(sel_id);
-  const int sel = (it == t->id2local.end()) ? -2 : it->second;
-  const dpgo_params_t &p = t->prm;
-  const bool restart = p.acceleration && ((t->iter + 2) % p.restart_interval) == 0;
-  if (sel >= 0 && !neighbor_poses_ready(*t->ag[sel], p.acceleration ? 1 : 0)) { set_err("neighbour poses missing"); return DPGO_NOT_READY; }
-  const int rc = enqueue_team_iteration(t, false, restart, sel, 2);
-  if (rc) return rc;
-  const bool fused = p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && !restart && sel >= 0;
-  account_iteration(t, sel, fused || t->last_iteration_folded);
-  return 0;
-}
-
-// Carried rows of the one-launch iterations (step_fused.hip): launch `rep` of a run of nfe one-launch iterations finds the
-// row products of its agent formed by launch rep - 1, from the evaluation point launch rep - 2 left -- which takes the
-// agents of the three iterations to be three different ones (the point is formed while the agent rests) and both earlier
-// launches to be part of the same run.  The first two launches of a run form their row products themselves.
-static int fe_carry_flags(dpgo_team_t *t, int rep, int nfe, const std::function<int(int)> &sel_at) {
-  if (!t->use_fe_carry) return 0;
-  auto consumes = [&](int q) {
-    if (q < 2 || q >= nfe) return false;
-    const int a = sel_at(q - 2), b = sel_at(q - 1), c = sel_at(q);
-    if (a < 0 || a == b || a == c || b == c) return false;
-    // (the poses of agent c are spread over the workgroups of the launch of agent b)
-    const int nblk = precond_nblk(*t->ag[b]);
-    if ((t->ag[c]->n + nblk - 1) / nblk > step_fe_carry_max_poses()) return false;
-    // (a gradient wave of the launch of agent c finishes 64 public poses and fetches their shared edges, two per lane)
-    if (t->ag[c]->npub < 1 || t->ag[c]->npub > 256 || !t->ag[c]->dev.fe_code_ok) return false;  // (no public pose: no table to read)
-    for (int g = 0; g < 4; ++g)
-      if (t->ag[c]->dev.fe_eptr[g + 1] - t->ag[c]->dev.fe_eptr[g] > 128) return false;
-    return true;
-  };
-  return (consumes(rep) ? FE_CARRY_IN : 0) | (consumes(rep + 1) ? FE_CARRY_W : 0) | (consumes(rep + 2) ? FE_CARRY_Y : 0);
-}
-
-// every one-launch iteration of a long run finds carried rows (every three consecutive agents of the schedule differ)
-static bool fe_carry_everywhere(dpgo_team_t *t) {
-  const int P = (int)t->sched.size();
-  if (P < 3) return false;
-  const std::function<int(int)> sel_at = [&](int rep) { return t->sched[(size_t)(rep % P)]; };
-  for (int q = 2; q < P + 2; ++q)
-    if (!(fe_carry_flags(t, q, 1 << 30, sel_at) & FE_CARRY_IN)) return false;
-  return true;
-}
-
-// prepare_only: capture and instantiate every graph a run of `iters` iterations from the current state would replay
-// (both alternating instances of each), execute nothing
-// the one-launch iteration (step_fused.hip) may serve this team: dense agents of fe_min_n (449: where it is faster) .. 512 poses whose rows fit the ELL
-// part, few enough public poses / shared edges for its LDS tables, the schedule and the descriptors baked into the
-// launches (period <= 8), every neighbour co-resident (the twins of its poses are addressed through the shared-edge table)
-static bool fused_eval_eligible(dpgo_team_t *t) {
-  const dpgo_params_t &p = t->prm;
-  const int P = (int)t->sched.size();
-  if (!(t->use_fused_eval && t->bake_sel && t->bake_desc && P >= 1 && P <= 8 && step_fe_supported(p.r) && p.acceleration &&
-        p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && (int)t->ag.size() <= LOOKAHEAD_MAX_AGENTS &&
-        t->h_descs.size() == t->ag.size() && t->precond_of.size() == t->ag.size() && t->peers.empty() && !t->isolated &&
-        (int)t->ag.size() == p.num_robots))
-    return false;
-  // (with carried rows the one-launch form is the faster one at every size it was measured at, 41 .. 500 poses; without them
-  // only from about 450 poses up -- profiles/experiments/fe_small.py)
-  const int min_n = t->fe_min_n > 0 ? t->fe_min_n : (fe_carry_everywhere(t) ? 32 : 449);
-  for (size_t k = 0; k < t->ag.size(); ++k) {
-    const int n = t->ag[k]->n;
-    if (t->precond_of[k] != DPGO_PRECOND_DENSE || n < min_n || n > 512 || !t->ag[k]->has_soa ||
-        t->h_descs[k].nshared > step_fe_max_edges())
-      return false;
-  }
-  return true;
-}
-
-// The deep-carried form (step_deep.hip) may serve this team: the private part of every agent's product is formed one launch
-// early, its row products two, its evaluation point three -- so every FOUR consecutive agents of the schedule differ; the
-// first 24 chunks of every agent's order are private (24 is returned; 0: not this team); an agent's
-// public poses fit two waves, its shared edges three edge slots of 64, and the partial sums have their buffers.
-static int fe_deep_m0(dpgo_team_t *t) {
-  if (!t->use_fe_deep || !t->use_fe_carry || !fused_eval_eligible(t)) return 0;
-  const int P = (int)t->sched.size();
-  if (P < 4) return 0;
-  for (int q = 0; q < P; ++q)
-    for (int u = 1; u < 4; ++u)
-      if (t->sched[(size_t)q] == t->sched[(size_t)((q + u) % P)]) return 0;
-  int min_priv = 32, nblk_all = 0, total = 0;
-  for (auto &a : t->ag) {
-    if (a->npub < 1 || a->npub > 128 || !a->dev.fe_code_ok || (int)a->se_host.size() > FE_MAX_EDGES) return 0;
-    min_priv = std::min(min_priv, a->dev.fe_npriv);
-    nblk_all = std::max(nblk_all, (4 * a->n + 7) / 8);
-    total += a->n;
-  }
-  for (auto &a : t->ag)
-    if ((total - a->n + nblk_all - 1) / nblk_all > 64) return 0;
-  int m0 = step_fd_pick_m0(min_priv);
-  if (const char *e = std::getenv("DPGO_FD_M0")) { const int f = std::atoi(e); if (f > 0 && f <= min_priv && step_fd_pick_m0(f) == f) m0 = f; }  // (experiments)
-  if (m0 == 0) return 0;
-  const size_t want = (size_t)2 * nblk_all * t->prm.r * 256;
-  if (t->d_fd_pacc.n < want && t->d_fd_pacc.alloc(want)) return 0;
-  if (t->use_fe_persist && !t->d_pd_bar.p && t->d_pd_bar.alloc(PD_BAR_WORDS)) return 0;
-  return m0;
-}
-
-// one run of nfe deep-carried one-launch iterations from the state k_nest_pre leaves: the points of the first three agents,
-// two launches that only produce (the row products of sel(0); then its private partial sums and the row products of
-// sel(1)), then the iterations -- each consuming what the three launches before it left
-// how many iterations of a graph of B run as one launch each.  Round 5's form leaves the last L + 1 (L = schedule period:
-// every agent's last block update of the run, whose statistics a status query reads) to the two-launch sequence; the
-// deep-carried form leaves those statistics itself (FD_STATS / FD_LASTAT) and hands over only the last iteration, which does
-// not look ahead.  An even number either way: the launches alternate between the two copies of the poses.
-static int fe_run_length(bool fe, int fd_m0, int B, int L) {
-  if (!fe) return 0;
-  if (fd_m0 > 0 && ((B - 1) & ~1) >= 4) return (B - 1) & ~1;
-  return std::max(0, B - L - 1) & ~1;
-}
-static bool fe_run_is_deep(bool fe, int fd_m0, int B) { return fe && fd_m0 > 0 && ((B - 1) & ~1) >= 4; }
-
-static void enqueue_fe_deep(dpgo_team_t *t, const LaunchCtx &c, int m0, int nfe, int B, int L, int iter0, const std::function<int(int)> &sel_at,
-                            NestState *nest_own, NestState *const nest_fe[2]) {
-  const dpgo_params_t &p = t->prm;
-  if (t->use_fe_persist && t->d_pd_bar.p) {
-    // the same run as ONE persistent launch (step_persist.hip): the points of the first three agents, the counters zeroed,
-    // then the two producing iterations and the nfe real ones behind grid hand-offs inside the kernel
-    launch_fd_prime(c, sel_at(0), sel_at(1), sel_at(2), t->max_n, p.num_robots, p.restart_interval, nest_own);
-    (void)hipMemsetAsync(t->d_pd_bar.p, 0, sizeof(unsigned long long) * PD_BAR_WORDS, c.stream);
-    launch_step_pd(c, m0, t->d_sched.p, (int)t->sched.size(), iter0 % (int)t->sched.size(), nfe, B, L, p.rgd_stepsize, p.num_robots,
-                   p.restart_interval, nest_own, nest_fe[nfe & 1], t->d_pd_bar.p, t->h_bar_err);
-    return;
-  }
-  int nblk_all = 0;
-  for (auto &a : t->ag) nblk_all = std::max(nblk_all, (4 * a->n + 7) / 8);
-  double *pacc[2] = {t->d_fd_pacc.p, t->d_fd_pacc.p + (size_t)nblk_all * p.r * 256};
-  const int s0 = sel_at(0), s1 = sel_at(1), s2 = sel_at(2);
-  launch_fd_prime(c, s0, s1, s2, t->max_n, p.num_robots, p.restart_interval, nest_own);
-  launch_fd_open(c, m0, s0, s1, pacc[0]);
-  for (int rep = 0; rep < nfe; ++rep) {
-    const int flags = FD_IN | (rep + 1 < nfe ? FD_P : 0) | (rep + 2 < nfe ? FD_W : 0) | (rep + 3 < nfe ? FD_Y : 0) |
-                      (rep >= B - L ? FD_STATS : 0) | ((rep + 1 < B && rep + 1 >= B - L) ? FD_LASTAT : 0);
-    launch_step_fd(c, m0, sel_at(rep), sel_at(rep + 1), sel_at(rep + 2), sel_at(rep + 3), p.rgd_stepsize, p.num_robots,
-                   p.restart_interval, rep == 0 ? nest_own : nest_fe[rep & 1], nest_fe[(rep + 1) & 1], rep & 1, flags,
-                   pacc[rep & 1], pacc[(rep + 1) & 1]);
-  }
-}
-
-static int team_run_impl(dpgo_team_t *t, int iters, bool prepare_only) {
-  if (sync_descs(t)) return DPGO_ERR;
-  const dpgo_params_t &p = t->prm;
-  for (auto &a : t->ag) if (!a->has_X) { set_err("team_run before set_initial"); return DPGO_NOT_READY; }
-  const bool graphable = (p.method == DPGO_METHOD_RGD) && p.rgd_use_preconditioner;
-  if (graphable && !t->graph_valid) {
-    for (auto &kv : t->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    t->graphs.clear();
-    t->graph_flip.clear();
-    t->graph_valid = true;
-  }
-  // look-ahead Nesterov steps need every workgroup's share of the other agents' poses to fit one wave, and one
-  // double per pose in the PART_D region
-  // (a line search decides the step after the whole agent's trial costs are known: its iterations are the un-fused
-  // launch sequence of enqueue_team_iteration, captured as it is)
-  const bool ls = p.rgd_line_search != 0;
-  bool pipelined = p.acceleration != 0 && (int)t->ag.size() <= LOOKAHEAD_MAX_AGENTS && !ls;
-  {
-    int total = 0;
-    for (auto &a : t->ag) total += a->n;
-    for (auto &a : t->ag) {
-      const int nblk = precond_nblk(*a);
-      if ((total - a->n + nblk - 1) / nblk > 64 || a->n > MAX_PART * PART_STRIDE) pipelined = false;
-    }
-  }
-  // the schedule, the counters and the Nesterov scalars live on the device, so a run of B iterations is one
-  // fixed launch sequence: captured once per B and replayed
-  // lead: the window opens with a restart iteration (un-fused kernels, same launch sequence every time); B: fused
-  // iterations that follow.  Pipelined teams have no windows: restart iterations are part of the uniform sequence
-  // (lead is never set).  Two instances per key alternate, so that a launch never has to wait for the previous
-  // replay of the same executable graph.
-  // Pipelined teams with a short schedule period bake the agent of every iteration into its launches (one graph per
-  // phase of the schedule): the kernels then address the agent's descriptor from a kernel argument instead of through
-  // team->cur_sel / next_sel, one dependent round trip less in each prologue.
-  const int P = (int)t->sched.size();
-  const bool bake = t->bake_sel && P >= 1 && P <= 8;
-  // One-launch iterations (step_fused.hip) for the mid-run part of a pipelined graph: dense agents of 449 .. 512 poses,
-  // the schedule and the descriptors baked in.  Their launches alternate between the two copies of the poses (parity),
-  // so they need neither each other's company on the device nor its lock
-  const bool fe_ok = pipelined && graphable && fused_eval_eligible(t);
-  const int fd_m0 = fe_ok ? fe_deep_m0(t) : 0;  // > 0: runs of one-launch iterations take the deep-carried form (step_deep.hip)
-  if (t->use_fe_persist && fd_m0 > 0 && !prepare_only && !acquire_fused_rtr_lock(t)) {
-    // the persistent form waits for its own workgroups: like the one-launch RTR solve it runs only under the device's lock
-    // (given back wherever the stream is known to have drained); without it the team keeps the per-launch form for good
-    t->use_fe_persist = 0;
-    for (auto &kv : t->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    t->graphs.clear();
-    t->graph_flip.clear();
-  }
-  auto graph_for = [&](bool lead, int B, int iter0, bool fe, hipGraphExec_t *out) -> int {
-    const int phase = bake ? iter0 % P : -1;
-    const int base = ((((lead ? 1 : 0) + 2 * B) * 16 + phase + 1) * 2 + (fe ? 1 : 0)) * 2;
-    const int key = base + (t->graph_flip[base / 2] ^= 1);
-    auto sel_at = [&](int rep) { return bake ? t->sched[(size_t)((iter0 + rep) % P)] : -1; };
-    auto it = t->graphs.find(key);
-    if (it != t->graphs.end()) { *out = it->second; return 0; }
-    hipGraph_t g = nullptr;
-    HIPC(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    if (lead) rc = enqueue_team_iteration(t, true, true, -1, 0);
-    if (rc == 0 && B > 0 && p.acceleration && pipelined) {
-      // pipelined: 2 launches per iteration (see k_eval_stats), restart iterations included.  The Nesterov step of
-      // the first iteration is a launch of its own, the last iteration does not look ahead, and its statistics /
-      // bookkeeping close the run.
-      LaunchCtx c = t->ctx();
-      c.bake_desc = bake && t->bake_desc;  // the agent's descriptor by value in the launches that name their agent
-      const int na = (int)t->ag.size(), mn = t->max_n;
-      launch_nest_pre(c, -1, -1, na, mn, p.num_robots, p.restart_interval, 1);
-      // the last L = min(B, schedule period) steps leave their statistics (X2 snapshot, |X - XPrev|^2: every agent's
-      // last block update of the run lies among them, and a status query reads it, a9), the look-aheads in front of
-      // them leave XPrev and |Y' - X|^2; nothing reads these values earlier in the run
-      const int L = std::min(B, (int)t->sched.size());
-      // iterations [0, nfe): one launch each (they are the ones that leave nothing behind: ahead == 3); an even number,
-      // so that the poses end in the primary arrays
-      const int nfe = fe_run_length(fe, fd_m0, B, L);
-      NestState *nest_own = t->d_nest_all.p, *nest_fe[2] = {t->d_nest_all.p + na, t->d_nest_all.p + 2 * na};
-      const bool deep = fe_run_is_deep(fe, fd_m0, B);
-      if (deep) enqueue_fe_deep(t, c, fd_m0, nfe, B, L, iter0, sel_at, nest_own, nest_fe);
-      for (int rep = deep ? nfe : 0; rep < B; ++rep) {
-        const int ahead = (rep + 1 < B ? 3 : 0) | ((rep + 1 < B && rep + 1 >= B - L) ? 4 : 0) | (rep >= B - L ? 8 : 0);
-        if (rep < nfe) {
-          launch_step_fe(c, sel_at(rep), sel_at(rep + 1), p.rgd_stepsize, p.num_robots, p.restart_interval,
-                         rep == 0 ? nest_own : nest_fe[rep & 1], nest_fe[(rep + 1) & 1], rep & 1, sel_at(rep + 2),
-                         fe_carry_flags(t, rep, nfe, sel_at));
-          continue;
-        }
-        launch_eval_stats(c, mn, rep == 0, 1, 0, p.num_robots, p.restart_interval, sel_at(rep), -1,
-                          (rep == nfe && nfe > 0) ? nest_fe[nfe & 1] : nullptr);
-        launch_precond(c, sel_at(rep), mn, PM_RGD_, B_X, B_GF, B_Z, 0, 0, p.rgd_stepsize, 1, p.num_robots, 2, p.restart_interval,
-                       ahead);
-      }
-      launch_eval_stats(c, mn, 0, 0, 1, p.num_robots, p.restart_interval, -1, sel_at(B - 1));
-    } else if (rc == 0 && B > 0 && p.acceleration && !ls) {
-      // 3 launches per iteration: [statistics of iteration k-1 + Nesterov step of iteration k] in one
-      // heterogeneous kernel, cost/gradient (+ G from the neighbours' Y), preconditioner + RGD step +
-      // Nesterov V + bookkeeping
-      LaunchCtx c = t->ctx();
-      const int na = (int)t->ag.size(), mn = t->max_n;
-      for (int rep = 0; rep < B; ++rep) {
-        if (rep == 0) launch_nest_pre(c, -1, -1, na, mn, p.num_robots, p.restart_interval);
-        else launch_stats_nest(c, na, mn, p.num_robots, p.restart_interval);
-        launch_eval(c, -1, mn, B_X, B_EGRAD, B_GF, PART_C, eval_opts(t, 2, 1, 0));
-        launch_precond(c, -1, mn, PM_RGD_, B_X, B_GF, B_Z, 0, 0, p.rgd_stepsize, 1, p.num_robots, 1, p.restart_interval);
-      }
-      launch_eval(c, -5, mn, B_X2, B_EGRAD2, B_GF2, PART_A, eval_opts(t, 0, 0, 0));
-    } else if (rc == 0) {
-      for (int rep = 0; rep < B && !rc; ++rep) rc = enqueue_team_iteration(t, true, false, -1, 0, rep + 1 < B);
-    }
-    HIPC(hipStreamEndCapture(t->stream, &g));
-    if (rc) { (void)hipGraphDestroy(g); return rc; }
-    hipGraphExec_t ge = nullptr;
-    HIPC(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
-    (void)hipGraphUpload(ge, t->stream);  // (the first replay of a prepared graph then costs what the later ones do)
-    t->graphs[key] = ge;
-    *out = ge;
-    return 0;
-  };
-  // evals: sparse evaluations of the iteration -- the gradient and the closing statistics of the two-launch form, the
-  // gradient alone in a one-launch iteration (it leaves no statistics); a line-search iteration adds its trial passes
-  auto account = [&](int sel, int evals) {
-    t->counters[0] += 1; t->counters[1] += precond_operator_bytes(*t->ag[sel]);
-    t->counters[2] += evals; t->counters[3] += evals * spmm_bytes_of(t, *t->ag[sel]);
-  };
-  int k = 0;
-  int cur_iter = t->iter;
-  if (prepare_only && !graphable) return 0;
-  while (k < iters) {
-    const bool uniform = graphable && p.acceleration && pipelined;  // restart iterations are ordinary iterations of the sequence
-    const bool restart = !uniform && p.acceleration && ((cur_iter + 2) % p.restart_interval) == 0;
-    int batch = 1;
-    if (graphable) {
-      // one graph per window: [the restart iteration, if the window opens with one] + the fused iterations up to
-      // the next restart iteration
-      int fusedn = iters - k - (restart ? 1 : 0);
-      if (p.acceleration && !uniform) {
-        const int it0 = cur_iter + (restart ? 1 : 0);
-        const int to_restart = (p.restart_interval - ((it0 + 2) % p.restart_interval)) % p.restart_interval;
-        fusedn = std::min(fusedn, to_restart);
-      }
-      // (the uniform pipelined sequence pays two extra launches per graph -- the first Nesterov step, the closing
-      // statistics -- and six two-launch iterations at its end: longer graphs)
-      fusedn = std::max(0, std::min(fusedn, uniform ? dpgo_team::MAX_PIPELINED_GRAPH_ITERS : dpgo_team::MAX_GRAPH_ITERS));
-      batch = fusedn + (restart ? 1 : 0);
-      hipGraphExec_t ge = nullptr;
-      // (prepared graphs are the ones a run will ask for: with the one-launch iterations if this team may take the lock)
-      const bool fe = fe_ok && (fd_m0 > 0 ? fusedn >= 6 : fusedn > (int)t->sched.size() + 2);
-      const int grc = graph_for(restart, fusedn, cur_iter, fe, &ge);
-      if (grc) return grc;
-      if (prepare_only) {
-        const int grc2 = graph_for(restart, fusedn, cur_iter, fe, &ge);  // the other instance; leaves the alternation where it was
-        if (grc2) return grc2;
-        cur_iter += batch;
-        k += batch;
-        continue;
-      }
-      ++t->epoch;
-      HIPC(hipGraphLaunch(ge, t->stream));
-      const int nfe_run = fe_run_length(fe, fd_m0, fusedn, std::min(fusedn, (int)t->sched.size()));
-      t->counters[7] += nfe_run;  // one-launch iterations
-      {
-        const int P_ = (int)t->sched.size(), it0 = t->iter;
-        const std::function<int(int)> sel_run = [&](int rep) { return t->sched[(size_t)((it0 + rep) % P_)]; };
-        if (fe_run_is_deep(fe, fd_m0, fusedn)) { t->counters[8] += nfe_run; t->counters[9] += nfe_run; }  // ... deep-carried: every one of them
-        else
-        for (int q = 0; q < nfe_run; ++q) t->counters[8] += (fe_carry_flags(t, q, nfe_run, sel_run) & FE_CARRY_IN) ? 1 : 0;  // ... with carried rows
-      }
-      // after >= 2 pipelined iterations every agent took its last Nesterov step as a look-ahead (per-pose partials)
-      for (auto &a : t->ag) a->rel_src = p.acceleration ? ((pipelined && fusedn >= 2) ? 4 : 0) : 2;
-      for (int q = 0; q < batch; ++q) {
-        const int sel = t->sched[(t->iter + q) % t->sched.size()];
-        const int evals = ls ? 2 + (ls_trials(p) + 3) / 4 : ((q - (restart ? 1 : 0) < nfe_run && !(restart && q == 0)) ? 1 : 2);
-        account(sel, evals);
-        if (restart && q == 0) account(sel, evals);  // the restart iteration solves twice (from Y, then from XPrev)
-        // status of this block update: the fused step leaves PART_B[2], the un-fused restart iteration k_status tiles
-        mark_optimized(t, *t->ag[sel], ((restart && q == 0) || ls) ? 5 : 1, true);
-        if (q == batch - 1) {
-          t->ag[sel]->opt_pending_rgd = true;
-          t->ag[sel]->rel_src = (fusedn > 0 && !ls) ? 1 : 0;  // a lone restart iteration ends with k_status (PART_D tiles)
-        }
-      }
-    } else {
-      const int sel = t->sched[t->iter % t->sched.size()];
-      for (auto &a : t->ag) a->rel_src = p.acceleration ? 0 : 2;
-      const int rc = enqueue_team_iteration(t, false, restart, sel, 0);
-      if (rc) return rc;
-      // status of the block update: k_status tiles, or -- where the one-launch RTR solve took the iteration's tail --
-      // one partial per pose pair in PART_B[2], the fused RGD step's layout
-      t->ag[sel]->rel_src = t->last_iteration_folded ? 1 : 0;
-      mark_optimized(t, *t->ag[sel], t->last_iteration_folded ? 1 : 5, true);
-    }
-    t->iter += batch;
-    cur_iter = t->iter;
-    for (auto &a : t->ag) { a->iter += batch; if (p.robust_cost_type != DPGO_COST_L2) a->robust_inner_iter += batch; }
-    t->counters[4] += batch;
-    k += batch;
-  }
-  return 0;
-}
-
-int dpgo_team_run(dpgo_team_t *t, int iters) { return team_run_impl(t, iters, false); }
-int dpgo_team_prepare(dpgo_team_t *t, int iters) { return team_run_impl(t, iters, true); }
-
 int dpgo_team_get_coloring(dpgo_team_t *t, int *color_of_agent) {
   if (sync_descs(t)) return DPGO_ERR;
   for (size_t k = 0; k < t->ag.size(); ++k) color_of_agent[k] = t->color_of[k];
@@ -1485,136 +1111,6 @@ int dpgo_team_set_groups(dpgo_team_t *t, int num_groups, const int *group_ptr, c
     }
   t->user_groups = true;
   t->descs_dirty = true;
-  return 0;
-}
-
-// one colour class: `count` block updates of the global schedule (count = global size of the class)
-int dpgo_team_run_group(dpgo_team_t *t, int g, int count) {
-  if (sync_descs(t)) return DPGO_ERR;
-  const dpgo_params_t &p = t->prm;
-  if (p.acceleration) { set_err("colour-parallel sweeps need acceleration = 0"); return DPGO_ERR; }
-  if (g < 0 || g >= (int)t->groups.size()) { set_err("bad group"); return DPGO_ERR; }
-  LaunchCtx c = t->ctx();
-  const int na = (int)t->ag.size();
-  if (na == 0) return 0;
-  launch_copy(c, -3, -1, na, t->max_n, B_X, B_XPREV, 0);
-  if (!t->groups[g].empty()) {
-    const int rc = enqueue_optimize_group(t, g);
-    if (rc) return rc;
-  }
-  launch_status(c, -3, -1, na, t->max_n);
-  if (!t->groups[g].empty()) {
-    LaunchCtx cg = c;
-    cg.ny = (int)t->groups[g].size();
-    int gmn = 0;
-    for (int k : t->groups[g]) gmn = std::max(gmn, t->ag[k]->n);
-    launch_status(cg, SEL_GROUP0 - g, -1, cg.ny, gmn, 1);
-  }
-  launch_advance(c, -1, na, 0, p.num_robots, p.restart_interval, 1, count);
-  for (auto &a : t->ag) { a->rel_src = 0; a->iter += count; if (p.robust_cost_type != DPGO_COST_L2) a->robust_inner_iter += count; }
-  for (int k : t->groups[g]) { t->ag[k]->publish_requested = true; mark_optimized(t, *t->ag[k], 5, true); }
-  t->iter += count;
-  t->counters[4] += count;
-  return 0;
-}
-
-// Simultaneous updates: every local agent takes one preconditioned RGD step per tick, all in the same launches
-// (blockIdx.y = agent), each from the neighbour poses as they were when the tick began.  This is the deterministic
-// instance of the asynchronous (ASAPP) mode in which all Poisson clocks fire together (src/PGOAgentROS.cpp:119-127
-// runs the same RGD step from whatever neighbour poses have arrived); one graph replay per call.
-int dpgo_team_run_simultaneous(dpgo_team_t *t, int ticks) {
-  if (sync_descs(t)) return DPGO_ERR;
-  const dpgo_params_t &p = t->prm;
-  if (p.method != DPGO_METHOD_RGD || !p.rgd_use_preconditioner || p.acceleration || p.rgd_line_search) {
-    set_err("simultaneous updates: preconditioned RGD with the fixed step, without acceleration (the ASAPP configuration)");
-    return DPGO_ERR;
-  }
-  for (auto &a : t->ag) if (!a->has_X) { set_err("run_simultaneous before set_initial"); return DPGO_NOT_READY; }
-  const int na = (int)t->ag.size();
-  if (na == 0 || ticks <= 0) return 0;
-  if (!t->graph_valid) {
-    for (auto &kv : t->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    t->graphs.clear();
-    t->graph_flip.clear();
-    t->graph_valid = true;
-  }
-  LaunchCtx c = t->ctx();
-  c.ny = na;
-  const int sel = SEL_ALL, mn = t->max_n;  // (= the class t->all_group: the local agents in index order)
-  auto body = [&](int reps) {
-    for (int rep = 0; rep < reps; ++rep) {
-      // XPrev only feeds the status of the LAST tick of a run (|X - XPrev|^2 left by its step kernel): the copy is
-      // taken in the last tick of every graph, two launches per tick otherwise
-      if (rep == reps - 1) launch_copy(c, -3, -1, na, mn, B_X, B_XPREV, 0);
-      launch_eval(c, sel, mn, B_X, B_EGRAD, B_GF, PART_C, eval_opts(t, 2, 0, 0));
-      // (statistics -- X2 snapshot, |X - XPrev|^2 -- only from the last tick of a graph: nothing reads the others')
-      launch_precond(c, sel, mn, PM_RGD_, B_X, B_GF, B_Z, 0, 0, p.rgd_stepsize, 0, p.num_robots, 0, p.restart_interval,
-                     rep == reps - 1 ? 0 : 16);
-    }
-  };
-  int left = ticks;
-  while (left > 0) {
-    const int B = std::min(left, dpgo_team::MAX_GRAPH_ITERS);
-    const int key = -(B + 1);  // negative keys: simultaneous-update graphs
-    hipGraphExec_t ge = nullptr;
-    auto it = t->graphs.find(key);
-    if (it != t->graphs.end()) ge = it->second;
-    else {
-      hipGraph_t g = nullptr;
-      HIPC(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
-      body(B);
-      HIPC(hipStreamEndCapture(t->stream, &g));
-      HIPC(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(g);
-      t->graphs[key] = ge;
-    }
-    ++t->epoch;
-    HIPC(hipGraphLaunch(ge, t->stream));
-    left -= B;
-  }
-  // f_opt / gradnorm_opt of every agent on the snapshot of its last step, then the counters
-  launch_eval(c, sel, mn, B_X2, B_EGRAD2, B_GF2, PART_A, eval_opts(t, 0, 0, 0));
-  LaunchCtx c1 = t->ctx();
-  launch_advance(c1, -1, na, 0, p.num_robots, p.restart_interval, 1, ticks, ticks * na);
-  for (auto &a : t->ag) {
-    t->counters[0] += ticks; t->counters[1] += ticks * precond_operator_bytes(*a);
-    t->counters[2] += ticks + 1; t->counters[3] += (ticks + 1) * spmm_bytes_of(t, *a);
-    a->rel_src = 1; a->iter += ticks; a->opt_pending_rgd = true; a->publish_requested = true;
-    mark_optimized(t, *a, 1, true);
-    if (p.robust_cost_type != DPGO_COST_L2) a->robust_inner_iter += ticks;
-  }
-  t->iter += ticks * na;
-  t->counters[4] += ticks * na;
-  return 0;
-}
-
-int dpgo_team_run_colored(dpgo_team_t *t, int sweeps) {
-  if (sync_descs(t)) return DPGO_ERR;
-  const dpgo_params_t &p = t->prm;
-  if (p.acceleration) { set_err("colour-parallel sweeps need acceleration = 0"); return DPGO_ERR; }
-  for (auto &a : t->ag) if (!a->has_X) { set_err("run_colored before set_initial"); return DPGO_NOT_READY; }
-  LaunchCtx c = t->ctx();
-  const int na = (int)t->ag.size();
-  for (int sw = 0; sw < sweeps; ++sw)
-    for (size_t g = 0; g < t->groups.size(); ++g) {
-      const int gs = (int)t->groups[g].size();
-      launch_copy(c, -3, -1, na, t->max_n, B_X, B_XPREV, 0);
-      const int rc = enqueue_optimize_group(t, (int)g);
-      if (rc) return rc;
-      launch_status(c, -3, -1, na, t->max_n);
-      if (gs > 0) {
-        LaunchCtx cg = c;
-        cg.ny = gs;
-        int gmn = 0;
-        for (int k : t->groups[g]) gmn = std::max(gmn, t->ag[k]->n);
-        launch_status(cg, SEL_GROUP0 - (int)g, -1, gs, gmn, 1);
-      }
-      launch_advance(c, -1, na, 0, p.num_robots, p.restart_interval, 1, gs);
-      for (auto &a : t->ag) { a->rel_src = 0; a->iter += gs; if (p.robust_cost_type != DPGO_COST_L2) a->robust_inner_iter += gs; }
-      for (int k : t->groups[g]) mark_optimized(t, *t->ag[k], 5, true);
-      t->iter += gs;
-      t->counters[4] += gs;
-    }
   return 0;
 }
 
@@ -1891,9 +1387,11 @@ int dpgo_team_import_peer(dpgo_team_t *t, int robot_id, const unsigned char *han
   return DPGO_OK;
 }
 
+}  // extern "C"
+
 // ---- the synchronous schedule across processes with the UPDATE token on the device (src/PGOAgentROS.cpp:136-149,
-// 443-504, 1161-1189 replaced): see k_mail_signal / k_mail_wait in pose_ops.hip
-static int ensure_mailbox(dpgo_team_t *t) {
+// 443-504, 1161-1189 replaced): see k_mail_signal / k_mail_wait in pose_ops.hip; dpgo_team_run_peer (team_run.hip) drives it
+int dpgo_host::ensure_mailbox(dpgo_team_t *t) {
   const size_t words = 2 * (size_t)t->prm.num_robots;
   if (t->d_mail.p) return 0;
   // fine-grained device memory: a peer GPU's system-scope store must become visible to a wait kernel that is ALREADY
@@ -1916,6 +1414,8 @@ static int ensure_mailbox(dpgo_team_t *t) {
   t->last_fin.assign(t->prm.num_robots, 0ull);
   return 0;
 }
+
+extern "C" {
 
 int dpgo_team_export_mailbox(dpgo_team_t *t, unsigned char *handle64) {
   if (ensure_mailbox(t)) return DPGO_ERR;
@@ -1942,90 +1442,6 @@ int dpgo_team_import_mailbox(dpgo_team_t *t, const unsigned char *handle64, cons
   return DPGO_OK;
 }
 
-// `iters` global iterations in which robot sel_ids[q] holds the token, enqueued without any host synchronisation:
-// every process calls this with the same list; neighbours in other processes are read in place (dpgo_team_import_peer)
-// and ordered by the mailboxes.  Per iteration k (t->iter), with acceleration:
-//   wait   fin[s] >= k         for s = the token holder of k - 1, if it neighbours a local robot from another process
-//                              (it has finished reading the Y this process is about to move)
-//   P1     iterate(false) part of every local robot (dpgo_team_step_begin)
-//   signal ready[a] = k + 1    into the mailbox of the token holder's team, for its local neighbours a
-//   wait   ready[b] >= k + 1   for the remote neighbours b of a local token holder
-//   P2     the block update (dpgo_team_step_end)
-//   signal fin[sel] = k + 1    into the mailboxes of the token holder's remote neighbours
-// Without acceleration only block updates move poses: the token holder waits for fin[b] of every remote neighbour's last
-// block update (what it reads is final, and nobody still reads what it overwrites).
-int dpgo_team_run_peer(dpgo_team_t *t, const int *sel_ids, int iters) {
-  if (check_exchange_error(t)) return DPGO_ERR;  // (a time-out of an earlier run that nobody has looked at yet)
-  if (sync_descs(t)) return DPGO_ERR;
-  if (ensure_mailbox(t)) return DPGO_ERR;
-  const dpgo_params_t &p = t->prm;
-  const int NR = p.num_robots;
-  for (auto &a : t->ag) if (!a->has_X) { set_err("run_peer before set_initial"); return DPGO_NOT_READY; }
-  // remote neighbours of every local robot must be readable in place and reachable by mail
-  for (auto &a : t->ag)
-    for (int b : a->neighbors)
-      if (!t->id2local.count(b) && (!t->peers.count(b) || !t->peer_mail.count(b))) {
-        set_err("run_peer: neighbour " + std::to_string(b) + " of robot " + std::to_string(a->id) + " was not imported (state + mailbox)");
-        return DPGO_ERR;
-      }
-  auto is_nbr = [](const Agent &a, int b) { return std::binary_search(a.neighbors.begin(), a.neighbors.end(), b); };
-  auto flush_waits = [&](MailWaits &w) { launch_mail_wait(t->stream, t->d_mail.p, w, t->h_bar_err); w.count = 0; };
-  auto add_wait = [&](MailWaits &w, int index, unsigned long long value) {
-    for (int q = 0; q < w.count; ++q) if (w.index[q] == index) { w.value[q] = std::max(w.value[q], value); return; }
-    if (w.count == MAIL_MAX) flush_waits(w);
-    w.index[w.count] = index; w.value[w.count] = value; ++w.count;
-  };
-  auto flush_sigs = [&](MailSignals &s) { launch_mail_signal(t->stream, s); s.count = 0; };
-  auto add_sig = [&](MailSignals &s, unsigned long long *word, unsigned long long value) {
-    for (int q = 0; q < s.count; ++q) if (s.word[q] == word) { s.value[q] = value; return; }
-    if (s.count == MAIL_MAX) flush_sigs(s);
-    s.word[s.count] = word; s.value[s.count] = value; ++s.count;
-  };
-  int prev_sel = -1;
-  {
-    // (the token holder of the iteration in front of this call, if any)
-    unsigned long long best = 0;
-    for (int b = 0; b < NR; ++b) if (t->last_fin[b] > best) { best = t->last_fin[b]; prev_sel = b; }
-    if (best != (unsigned long long)t->iter) prev_sel = -1;
-  }
-  for (int q = 0; q < iters; ++q) {
-    const int sel_id = sel_ids[q];
-    if (sel_id < 0 || sel_id >= NR) { set_err("run_peer: bad robot id in the schedule"); return DPGO_ERR; }
-    const unsigned long long k = (unsigned long long)t->iter;
-    auto it = t->id2local.find(sel_id);
-    const int sel = (it == t->id2local.end()) ? -2 : it->second;
-    const bool restart = p.acceleration && ((t->iter + 2) % p.restart_interval) == 0;
-    MailWaits w{};
-    MailSignals s{};
-    if (p.acceleration && prev_sel >= 0 && !t->id2local.count(prev_sel))
-      for (auto &a : t->ag) if (is_nbr(*a, prev_sel)) { add_wait(w, NR + prev_sel, k); break; }
-    flush_waits(w);
-    int rc = enqueue_team_iteration(t, false, restart, sel, 1);
-    if (rc) return rc;
-    if (p.acceleration && sel == -2)
-      for (auto &a : t->ag) if (is_nbr(*a, sel_id)) add_sig(s, t->peer_mail[sel_id] + a->id, k + 1);
-    flush_sigs(s);
-    if (sel >= 0)
-      for (int b : t->ag[sel]->neighbors)
-        if (!t->id2local.count(b)) {
-          if (p.acceleration) add_wait(w, b, k + 1);
-          if (t->last_fin[b] > 0) add_wait(w, NR + b, t->last_fin[b]);
-        }
-    flush_waits(w);
-    rc = enqueue_team_iteration(t, false, restart, sel, 2);
-    if (rc) return rc;
-    const bool fused = p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && !restart && sel >= 0;
-    account_iteration(t, sel, fused || t->last_iteration_folded);
-    if (sel >= 0)
-      for (int b : t->ag[sel]->neighbors)
-        if (!t->id2local.count(b)) add_sig(s, t->peer_mail[b] + NR + sel_id, k + 1);
-    flush_sigs(s);
-    t->last_fin[sel_id] = k + 1;
-    prev_sel = sel_id;
-  }
-  return DPGO_OK;
-}
-
 // diagnostic: the hand-off words of an agent's one-launch RTR solve (phase timestamps in -DDPGO_RTR_TRACE builds)
 int dpgo_agent_read_rtr_handoff(dpgo_team_t *t, int id, unsigned long long *out, int n) {
   Agent *a = find_agent(t, id);
@@ -2046,7 +1462,7 @@ int dpgo_agent_read_partials(dpgo_team_t *t, int id, int offset, double *out, in
 
 int dpgo_team_get_counters(dpgo_team_t *t, double *out, int n) {
   for (auto &a : t->ag) if (refresh_rtr_result(t, *a)) return DPGO_ERR;
-  for (int k = 0; k < n && k < 11; ++k) out[k] = t->counters[k];
+  for (int k = 0; k < n && k < CNT_COUNT; ++k) out[k] = t->counters[k];
   return 0;
 }
 
@@ -2074,14 +1490,14 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
     else if (which == 1) launch_eval(c, a->local, n, B_X, B_T1, B_T2, PART_C, eval_opts(t, 0, 0, 0));
     else if (which == 2) launch_hess(c, a->local, n, B_X, B_EGRAD, B_GF, B_T2, PART_C);
     else if (which == 3) launch_retract(c, a->local, n, B_X, B_GF, 0.0, B_X2, -1);
-    else if (which == 4) launch_nest_pre(c, -2, -1, (int)t->ag.size(), t->max_n, t->prm.num_robots, 1 << 30);
+    else if (which == 4) launch_nest_pre(c, SEL_REMOTE, -1, (int)t->ag.size(), t->max_n, t->prm.num_robots, 1 << 30);
     else if (which == 5) launch_noop(c, 1, 64);
     else if (which == 6) launch_noop(c, 256, 256);
-    else if (which == 7) launch_status(c, -3, -1, (int)t->ag.size(), t->max_n);
+    else if (which == 7) launch_status(c, SEL_EVERY, -1, (int)t->ag.size(), t->max_n);
     else if (which == 9)  // the fused step kernel exactly as the pipelined accelerated-RGD loop launches it (state is consumed)
-      launch_precond(c, a->local, n, PM_RGD_, B_X, B_GF, B_Z, 0, 0, t->prm.rgd_stepsize, 1, t->prm.num_robots, 2,
-                     t->prm.restart_interval, 3);
-    else launch_copy(c, -3, -1, (int)t->ag.size(), t->max_n, B_X, B_XPREV, 0);
+      launch_precond(c, a->local, n, PM_RGD_, B_X, B_GF, B_Z, 0, 0, t->prm.rgd_stepsize, 1, t->prm.num_robots, PADV_PIPELINED,
+                     t->prm.restart_interval, PA_LOOKAHEAD);
+    else launch_copy(c, SEL_EVERY, -1, (int)t->ag.size(), t->max_n, B_X, B_XPREV, 0);
   };
   if (which == 0) *algorithmic_bytes = precond_operator_bytes(*a) + 3.0 * vec;  // the operator once, v + X in, z out
   else if (which == 9) {
@@ -2162,9 +1578,10 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
     HIPC(hipEventCreate(&e0)); HIPC(hipEventCreate(&e1));
     LaunchCtx cc = t->ctx();
     cc.bake_desc = true;
-    auto sel_at = [&](int rep) { return t->sched[(size_t)((t->iter + rep) % P)]; };
+    const int it0 = t->iter;
+    auto sel_at = [&](int rep) { return t->sched[(size_t)((it0 + rep) % P)]; };
     NestState *nest_own = t->d_nest_all.p, *nest_fe[2] = {t->d_nest_all.p + na, t->d_nest_all.p + 2 * na};
-    launch_nest_pre(cc, -1, -1, na, mn, p.num_robots, p.restart_interval, 1);
+    launch_nest_pre(cc, SEL_SCHED, -1, na, mn, p.num_robots, p.restart_interval, 1);
     const int total_reps = ((reps + 1) & ~1) + 8;  // (even: the poses end in the primary arrays)
     reps = total_reps - 8;
     const int fd_m0 = fe_deep_m0(t);
@@ -2188,10 +1605,10 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
       if (k == 8) HIPC(hipEventRecord(e0, t->stream));
       launch_step_fe(cc, sel_at(k), sel_at(k + 1), p.rgd_stepsize, p.num_robots, p.restart_interval,
                      k == 0 ? nest_own : nest_fe[k & 1], nest_fe[(k + 1) & 1], k & 1, sel_at(k + 2),
-                     fe_carry_flags(t, k, total_reps, sel_at));
+                     fe_carry_flags(t, k, total_reps, it0));
     }
     HIPC(hipEventRecord(e1, t->stream));
-    launch_eval_stats(cc, mn, 0, 0, 1, p.num_robots, p.restart_interval, -1, sel_at(total_reps - 1), nest_fe[total_reps & 1]);
+    launch_eval_stats(cc, mn, 0, 0, 1, p.num_robots, p.restart_interval, SEL_SCHED, sel_at(total_reps - 1), nest_fe[total_reps & 1]);
     HIPC(hipEventSynchronize(e1));
     HIPC(hipStreamSynchronize(t->stream));
     t->iter += total_reps;
@@ -2221,12 +1638,12 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
     const int P = (int)t->sched.size();
     const bool bake = t->bake_sel && P >= 1 && P <= 8;
     cc.bake_desc = bake && t->bake_desc;
-    auto sel_at = [&](int rep) { return bake ? t->sched[(size_t)((t->iter + rep) % P)] : -1; };
-    launch_nest_pre(cc, -1, -1, na, mn, p.num_robots, p.restart_interval);
+    auto sel_at = [&](int rep) { return bake ? t->sched[(size_t)((t->iter + rep) % P)] : SEL_SCHED; };
+    launch_nest_pre(cc, SEL_SCHED, -1, na, mn, p.num_robots, p.restart_interval);
     for (int k = -8; k < reps; ++k) {
       if (k == 0) HIPC(hipEventRecord(e0, t->stream));
-      launch_eval_stats(cc, mn, k == -8, 1, k > -8, p.num_robots, p.restart_interval, sel_at(k + 8), k > -8 ? sel_at(k + 7) : -1);
-      if (which == 10) launch_precond(cc, sel_at(k + 8), mn, PM_RGD_, B_X, B_GF, B_Z, 0, 0, p.rgd_stepsize, 1, p.num_robots, 2, p.restart_interval, 3);
+      launch_eval_stats(cc, mn, k == -8, 1, k > -8, p.num_robots, p.restart_interval, sel_at(k + 8), k > -8 ? sel_at(k + 7) : SEL_SCHED);
+      if (which == 10) launch_precond(cc, sel_at(k + 8), mn, PM_RGD_, B_X, B_GF, B_Z, 0, 0, p.rgd_stepsize, 1, p.num_robots, PADV_PIPELINED, p.restart_interval, PA_LOOKAHEAD);
     }
     HIPC(hipEventRecord(e1, t->stream));
     HIPC(hipEventSynchronize(e1));

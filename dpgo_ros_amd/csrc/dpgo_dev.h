@@ -195,6 +195,12 @@ struct TeamDev {
   const int *group_members;  // so they may take their block update in the same launches (blockIdx.y)
 };
 
+// agent selectors: what a kernel's `sel` argument means when it is not a local agent index (>= 0)
+constexpr int SEL_SCHED = -1;    // the agent the device-side schedule selects this iteration (captured sequences)
+constexpr int SEL_REMOTE = -2;   // the token holder lives elsewhere: no local agent optimizes
+constexpr int SEL_EVERY = -3;    // every local agent, agent blockIdx.y (k_copy / k_status)
+constexpr int SEL_STATS = -5;    // team->stats_sel: the agent of the iteration that just finished
+constexpr int SEL_NEXT = -6;     // team->next_sel: the agent of iteration k + 1 (pipelined RGD)
 constexpr int SEL_GROUP0 = -16;  // sel <= SEL_GROUP0 selects colour class (SEL_GROUP0 - sel), member blockIdx.y
 constexpr int SEL_ALL = SEL_GROUP0 - 4096;  // every local agent, agent blockIdx.y (the class behind the colouring, without its
                                             // two dependent table look-ups at the head of every kernel of a lockstep tick)

@@ -35,8 +35,8 @@ __device__ __forceinline__ int sel_sched(const TeamDev *team, int sel) {
 
 __device__ __forceinline__ int sel_cur(const TeamDev *team, int sel) {
   if (sel >= 0) return sel;
-  if (sel == -5) return team->stats_sel;
-  if (sel == -6) return team->next_sel;
+  if (sel == SEL_STATS) return team->stats_sel;
+  if (sel == SEL_NEXT) return team->next_sel;
   if (sel > SEL_GROUP0) return team->cur_sel;
   if (sel == SEL_ALL) return (int)blockIdx.y;
   return team->group_members[team->group_ptr[SEL_GROUP0 - sel] + blockIdx.y];  // colour-parallel update
@@ -422,7 +422,7 @@ __device__ __forceinline__ void tile_put(Tile<R> &t, int row, const double *v) {
 //   XPrev = X;  gamma' = (1 + sqrt(1 + 4 N^2 gamma^2)) / 2N;  alpha = 1 / (gamma' N)
 //   Y = proj((1 - alpha) X + alpha V);  X = Y
 // and for the agents that do NOT optimize this iteration (everything but `sel`, or all when
-// sel == -2):  V = proj(V)  [= proj(V + gamma (X - Y))], then the periodic restart X = XPrev,
+// sel == SEL_REMOTE):  V = proj(V)  [= proj(V + gamma (X - Y))], then the periodic restart X = XPrev,
 // V = Y = X; partial [0] of PART_D = |X_new - XPrev|^2.  First kernel of an accelerated iteration:
 // publishes team->cur_sel.
 // `hook` runs once behind the loads of the agent's X and V tiles (k_nest_pre places reads of pinned host memory there: memory
@@ -439,8 +439,8 @@ __device__ __forceinline__ void nest_pre_body(const AgentDev *__restrict__ agent
   // where it is (it does NOT move to Y), while Y and, afterwards, V are updated as in any accelerated iteration
   const int ai = only_agent >= 0 ? only_agent : by;
   const AgentDev &ag = agents[ai];
-  const int selected = (sel == -2) ? -1 : sel_sched(team, sel);
-  if (bx == 0 && by == 0 && threadIdx.x == 0 && sel == -1) team->cur_sel = selected;
+  const int selected = (sel == SEL_REMOTE) ? -1 : sel_sched(team, sel);
+  if (bx == 0 && by == 0 && threadIdx.x == 0 && sel == SEL_SCHED) team->cur_sel = selected;
   const int j0 = bx * 64, tid = threadIdx.x;
   if (j0 >= ag.n) return;
   const int cnt = min(64, ag.n - j0);

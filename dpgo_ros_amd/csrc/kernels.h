@@ -32,6 +32,19 @@ struct LaunchCtx {
 
 // preconditioner kernel modes (see precond.hip)
 constexpr int PM_PLAIN_ = 0, PM_TCG_INIT_ = 1, PM_TCG_STEP_ = 2, PM_RGD_ = 3;
+// `advance` of launch_precond (PM_RGD_): the step kernel takes no bookkeeping; the end-of-iteration bookkeeping of the whole
+// team (3-launch iteration); the hand-over of a pipelined iteration (stats_sel / next_sel, see k_eval_stats)
+constexpr int PADV_NONE = 0, PADV_TEAM = 1, PADV_PIPELINED = 2;
+// `ahead` bits of launch_precond (PM_RGD_): the Nesterov step of iteration k + 1 for the workgroup's own poses / for its share
+// of the other agents' poses; those steps also leave what a status query reads; this step leaves its statistics (pipelined
+// runs: only where asked); this step leaves NO statistics (lockstep ticks, PADV_NONE)
+constexpr int PA_OWN = 1, PA_OTHERS = 2, PA_LA_STATUS = 4, PA_STATS = 8, PA_NO_STATS = 16;
+constexpr int PA_LOOKAHEAD = PA_OWN | PA_OTHERS;  // what every mid-run step of a pipelined run carries
+// `tail` of launch_rtr_solve (any bit: the status partials go to PART_B[2]): Nesterov V update; status + the team's
+// bookkeeping; the bookkeeping stays with the caller's report (per-agent API)
+constexpr int RTR_TAIL_NEST_V = 1, RTR_TAIL_STATUS = 2, RTR_TAIL_NO_ADVANCE = 4;
+// `tail` of launch_ls_apply: status tiles + the team's bookkeeping; Nesterov V update
+constexpr int LS_TAIL_STATUS = 1, LS_TAIL_NEST_V = 2;
 
 struct EvalOpts {
   int gmode = 0;    // 0 G from buffer, 1 assemble from slab, 2 assemble pulling from co-resident agents
@@ -53,7 +66,7 @@ struct ReportTail {
   int ai = 0, advance = 0, accel = 0, num_robots = 1, restart_interval = 1;
 };
 
-// `sel`: local agent index, or -1 = the agent the device-side schedule selects this iteration
+// `sel`: local agent index, or one of the SEL_* selectors (dpgo_dev.h)
 void launch_buildG(const LaunchCtx &c, int sel, int max_npub, int aux, int pull);
 void launch_pull(const LaunchCtx &c, int dst, int nshared);
 void launch_eval(const LaunchCtx &c, int sel, int max_n, int xb, int egb, int gfb, int poff, const EvalOpts &o);
@@ -63,14 +76,14 @@ size_t eval_staged_lds_bytes(int r, int cap);
 constexpr int EVS_STATIC_LDS = 8 * 1024;  // room left for k_eval_staged's static arrays under the device's LDS limit
 void launch_hess(const LaunchCtx &c, int sel, int max_n, int xb, int egb, int vb, int ob, int poff);
 void launch_precond(const LaunchCtx &c, int sel, int max_n, int mode, int xb, int vb, int zb, int sp, int max_inner,
-                    double step, int accel, int num_robots, int advance = 0, int restart_interval = 1, int ahead = 0);
+                    double step, int accel, int num_robots, int advance = PADV_NONE, int restart_interval = 1, int ahead = 0);
 // pipelined accelerated RGD iterations: evaluation of iteration k || statistics of k-1 || bookkeeping of k-1
 // eval_sel / stats_sel >= 0: the local agent of the evaluation / statistics half, known to the host (graphs that bake
-// the schedule in); -1: read from the device-side schedule state
+// the schedule in); SEL_SCHED: read from the device-side schedule state
 // nest_copy: this launch leaves a run of one-launch iterations (step_fused.hip): its bookkeeping workgroup copies the
 // NestStates those launches advanced next to the team's own (iter / cur_sel have moved with them already)
 void launch_eval_stats(const LaunchCtx &c, int max_n, int first, int has_eval, int has_stats, int num_robots,
-                       int restart_interval, int eval_sel = -1, int stats_sel = -1, const NestState *nest_copy = nullptr);
+                       int restart_interval, int eval_sel = SEL_SCHED, int stats_sel = SEL_SCHED, const NestState *nest_copy = nullptr);
 // one launch per pipelined accelerated-RGD iteration (step_fused.hip): evaluation + preconditioned step + look-ahead.
 // sel / next_sel: the agents of this iteration and the next (baked); nest_src / nest_dst: the NestStates [local agent]
 // this launch reads / leaves advanced; parity: which copy of the poses it reads (0: B_X / B_Y, 1: their twins) -- it
@@ -84,13 +97,8 @@ int step_fe_carry_max_poses();
 // dpgo_dev.h).  m0: leading chunks of every agent's order that are private (step_fd_pick_m0 of the team's minimum; 0: the
 // team cannot run it).  pacc_in / pacc_out: the partial sums this launch continues / leaves, [workgroup][r][256]
 int step_fd_pick_m0(int min_private_chunks);
-// step_persist.hip: K deep-carried iterations (and the two producing ones in front of them) in ONE persistent launch.
-// d_sched / sched_len / it0: the team's schedule on the device and where the run starts in it; B, L: the graph's length and
-// the schedule period (which iterations leave their statistics); bar: >= 18 * 16 zeroed 64-bit words; err: the team's
-// pinned error word (5: a hand-off of this kernel timed out)
-constexpr int PD_BAR_WORDS = 18 * 16;
-void launch_step_pd(const LaunchCtx &c, int m0, const int *d_sched, int sched_len, int it0, int K, int B, int L, double step, int num_robots,
-                    int restart_interval, const NestState *nest_src, NestState *nest_dst, unsigned long long *bar, int *err);
+// (K deep-carried iterations in ONE persistent launch was built, measured slower than one launch per iteration, and
+// removed: profiles/r06_deep_carry.md)
 // behind k_fd_prime: the row products of the run's first two agents and the private partial sums of the first
 void launch_fd_open(const LaunchCtx &c, int m0, int s0, int s1, double *pacc_out);
 void launch_fd_prime(const LaunchCtx &c, int s0, int s1, int s2, int max_n, int num_robots, int restart_interval, const NestState *nest_src);
@@ -100,7 +108,7 @@ void launch_step_fd(const LaunchCtx &c, int m0, int sel, int next_sel, int next2
 constexpr int LS_MAX_TRIALS = 8;
 void launch_ls_trials(const LaunchCtx &c, int sel, int max_n, int dirb, double step0, double shrink, int ntrials);
 void launch_ls_cost(const LaunchCtx &c, int sel, int max_n, int dirb, int ntrials);
-// tail: fold the rest of a non-restart team iteration into the launch (bit 1: Nesterov V update; status tiles + advance)
+// tail: fold the rest of a non-restart team iteration into the launch (LS_TAIL_* bits)
 void launch_ls_apply(const LaunchCtx &c, int sel, int max_n, double step0, double shrink, double sigma, int ntrials, int tail = 0,
                      int num_robots = 1, int restart_interval = 1);
 void launch_tcg_hv(const LaunchCtx &c, int sel, int max_n, int sp, int max_inner);

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64) void k_ls_apply(const AgentDev *__restrict__ ag
   __shared__ Tile<R> TX, TV, TY, TP;
   tile_in<R>(TX, ag.buf[chosen < 0 ? B_X : ls_buf(chosen)], j0, cnt, tid);
   tile_in<R>(TP, ag.buf[B_XPREV], j0, cnt, tid);
-  if (tail & 2) {
+  if (tail & LS_TAIL_NEST_V) {
     tile_in<R>(TV, ag.buf[B_V], j0, cnt, tid);
     tile_in<R>(TY, ag.buf[B_Y], j0, cnt, tid);
   }
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(64) void k_ls_apply(const AgentDev *__restrict__ ag
     tile_get<R>(TP, tid, q);
 #pragma unroll
     for (int i = 0; i < 4 * R; ++i) { const double d = x[i] - q[i]; rel += d * d; }
-    if (tail & 2) {
+    if (tail & LS_TAIL_NEST_V) {
       const double gamma = ag.scal[6];
       double v[4 * R];
       tile_get<R>(TV, tid, v);
@@ -205,12 +205,12 @@ __global__ __launch_bounds__(64) void k_ls_apply(const AgentDev *__restrict__ ag
     ag.part[PART_D + (size_t)blockIdx.x * PART_STRIDE] = rel;
     ag.part[PART_E + (size_t)blockIdx.x * PART_STRIDE] = rel;
   }
-  if (tail & 2) {
+  if (tail & LS_TAIL_NEST_V) {
     __syncthreads();
     tile_out<R>(TV, ag.buf[B_V], j0, cnt, tid);
   }
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-    for (int k = 0; k < team->num_agents; ++k) advance_agent(agents[k], (tail & 2) ? 1 : 0, num_robots, restart_interval);
+    for (int k = 0; k < team->num_agents; ++k) advance_agent(agents[k], (tail & LS_TAIL_NEST_V) ? 1 : 0, num_robots, restart_interval);
     team->iter += 1;
   }
 }

@@ -200,10 +200,10 @@ __global__ void k_advance(const AgentDev *__restrict__ agents, TeamDev *team, in
   if (bump_team && ai == 0) team->iter += team_inc;
 }
 
-// PART_D partial [0] = |X - XPrev|_F^2 over a 64-pose tile (blockIdx.y = agent when sel == -3)
+// PART_D partial [0] = |X - XPrev|_F^2 over a 64-pose tile (blockIdx.y = agent when sel == SEL_EVERY)
 template <int R>
 __global__ __launch_bounds__(64) void k_status(const AgentDev *__restrict__ agents, const TeamDev *team, int sel, int only_agent, int opt) {
-  const int ai = only_agent >= 0 ? only_agent : (sel == -3 ? (int)blockIdx.y : sel_cur(team, sel));
+  const int ai = only_agent >= 0 ? only_agent : (sel == SEL_EVERY ? (int)blockIdx.y : sel_cur(team, sel));
   const AgentDev &ag = agents[ai];
   const int j0 = blockIdx.x * 64, tid = threadIdx.x;
   if (j0 >= ag.n) return;
@@ -224,11 +224,11 @@ __global__ __launch_bounds__(64) void k_status(const AgentDev *__restrict__ agen
   }
 }
 
-// buf[to] = buf[from] for one agent or (sel == -3) every agent (blockIdx.y).  As the first kernel of a
+// buf[to] = buf[from] for one agent or (sel == SEL_EVERY) every agent (blockIdx.y).  As the first kernel of a
 // non-accelerated iteration (publish != 0) it also publishes team->cur_sel.
 __global__ void k_copy(const AgentDev *__restrict__ agents, TeamDev *team, int sel, int only_agent, int r, int from, int to,
                        int publish) {
-  const int ai = only_agent >= 0 ? only_agent : (sel == -3 ? (int)blockIdx.y : sel_cur(team, sel));
+  const int ai = only_agent >= 0 ? only_agent : (sel == SEL_EVERY ? (int)blockIdx.y : sel_cur(team, sel));
   if (publish && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     team->cur_sel = team->sched[team->iter % team->sched_len];
   const AgentDev &ag = agents[ai];
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(64) void k_iterate_false(const AgentDev *__restrict
     q = ag.pub_index[j0 + tid];
     if (q >= 0) { p0 = pubpos_ptr[q]; p1 = pubpos_ptr[q + 1]; }
   }
-  nest_pre_body<R>(agents, team, -2, ai, num_robots, restart_interval, (int)blockIdx.x, 0, TX, TV, 0);
+  nest_pre_body<R>(agents, team, SEL_REMOTE, ai, num_robots, restart_interval, (int)blockIdx.x, 0, TX, TV, 0);
   if (q >= 0) {
     double v[4 * R];
     tile_get<R>(TX, tid, v);  // the tile still holds what went to X (and Y)
@@ -566,7 +566,7 @@ void launch_advance(const LaunchCtx &c, int only_agent, int num_agents, int acce
 }
 
 void launch_status(const LaunchCtx &c, int sel, int only_agent, int num_agents, int max_n, int opt) {
-  dim3 grid((max_n + 63) / 64, (sel == -3 && only_agent < 0) ? num_agents : ((sel <= SEL_GROUP0 && only_agent < 0) ? c.ny : 1));
+  dim3 grid((max_n + 63) / 64, (sel == SEL_EVERY && only_agent < 0) ? num_agents : ((sel <= SEL_GROUP0 && only_agent < 0) ? c.ny : 1));
   DPGO_DISPATCH_R(c.r, hipLaunchKernelGGL(k_status<R>, grid, dim3(64), 0, c.stream, c.agents, c.team, sel, only_agent, opt));
 }
 
@@ -673,7 +673,7 @@ void launch_cost(const LaunchCtx &c, int ai) {
 
 void launch_copy(const LaunchCtx &c, int sel, int only_agent, int num_agents, int max_n, int from, int to, int publish) {
   const int len = max_n * 4 * c.r;
-  dim3 grid((len + 255) / 256, (sel == -3 && only_agent < 0) ? num_agents : 1);
+  dim3 grid((len + 255) / 256, (sel == SEL_EVERY && only_agent < 0) ? num_agents : 1);
   hipLaunchKernelGGL(k_copy, grid, dim3(256), 0, c.stream, c.agents, c.team, sel, only_agent, c.r, from, to, publish);
 }
 

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
                                                  int zb, int sp, int max_inner, double step, int accel,
                                                  int num_robots, int advance, int restart_interval, int ahead,
                                                  const NestState *nest_all, const AgentDev agv) {
-  if constexpr (LEAN) { accel = 1; advance = 2; ahead = 3; }
+  if constexpr (LEAN) { accel = 1; advance = PADV_PIPELINED; ahead = PA_LOOKAHEAD; }
   // XCD-aware block order: hardware workgroup h runs on XCD h % 8 (each with its own L2).  Logical block
   // (h % 8) * (grid / 8) + h / 8 gives every XCD one contiguous range of poses, so that the cache lines shared by
   // neighbouring poses (a pose is 4R doubles, not a multiple of a line) are written inside one L2 instead of
@@ -87,13 +87,13 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
   const bool producer = is_tl && hb < ag.tl.nA;
   const int bx = is_tl ? hb - ag.tl.nA : (hb % 8) * ((int)gridDim.x / 8) + hb / 8;
   PC_STAMP(0);
-  if (MODE == PM_RGD_ && advance == 2 && bx == 0 && threadIdx.x == 0) {
+  if (MODE == PM_RGD_ && advance == PADV_PIPELINED && bx == 0 && threadIdx.x == 0) {
     // pipelined iterations: nothing that a workgroup of THIS launch reads is written here (cur_sel, iter and the
     // NestStates move in the next k_eval_stats); the next launch finds its statistics agent and its own agent
     team->stats_sel = team->cur_sel;
     team->next_sel = team->sched[(team->iter + 1) % team->sched_len];
   }
-  if (MODE == PM_RGD_ && advance == 1 && bx == 0 && threadIdx.x == 0) {
+  if (MODE == PM_RGD_ && advance == PADV_TEAM && bx == 0 && threadIdx.x == 0) {
     // end-of-iteration bookkeeping of the whole team, folded here: no workgroup of this kernel reads
     // team->iter (they use cur_sel) or a NestState (gamma' comes from scal[6]), and the next kernel that
     // does (k_nest_pre of the following iteration) is ordered behind this launch
@@ -197,7 +197,8 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
   // ahead bits: 1 look-ahead of this workgroup's poses, 2 look-ahead of the other agents' poses, 4 the look-ahead also
   // leaves what a status query needs (XPrev, |Y' - X|^2 per pose), 8 this step leaves its statistics (X2 snapshot,
   // |X - XPrev|^2).  Only the last two iterations of a run set 4 / 8: nothing reads those values in between.
-  const bool la_status = (ahead & 4) != 0, want_stats = (MODE != PM_RGD_) || (advance != 2 && !(ahead & 16)) || (ahead & 8) != 0;
+  const bool la_status = (ahead & PA_LA_STATUS) != 0,
+             want_stats = (MODE != PM_RGD_) || (advance != PADV_PIPELINED && !(ahead & PA_NO_STATS)) || (ahead & PA_STATS) != 0;
   double pre_x = 0, pre_v = 0, pre_y = 0, pre_p = 0;
   double nest_gamma = 0;
   if (tid < npose * 4 * R) {
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
   double ahead_alpha = 0;
   bool ahead_opt = false, restart_now = false, restart_next = false;
   if (MODE == PM_RGD_ && accel) {
-    if (advance == 2) {
+    if (advance == PADV_PIPELINED) {
       // the NestState describes iteration k-1 (it is advanced by the next k_eval_stats): gamma of this iteration,
       // and gamma / alpha / selected agent of iteration k+1 for the look-ahead Nesterov step of the epilogue
       const NestState ns = nest_all ? nest_all[agent_index] : *ag.nest;  // (one round trip less than through the descriptor)
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   PC_STAMP(6);
-  if (MODE == PM_RGD_ && (ahead & 2) && tid >= 64 && tid < 128) {
+  if (MODE == PM_RGD_ && (ahead & PA_OTHERS) && tid >= 64 && tid < 128) {
     // look-ahead operands of the second wave, requested once its share of the stream is consumed: they arrive while
     // the partial sums are reduced and the first wave starts its tail, and they do not occupy registers during the
     // stream (the tail is register-bound).
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
     }
   }
 
-  if (MODE == PM_RGD_ && (ahead & 2) && tid >= 64 && tid < 128) {
+  if (MODE == PM_RGD_ && (ahead & PA_OTHERS) && tid >= 64 && tid < 128) {
     // look-ahead of the other agents' poses on the second wave (operands prefetched in the prologue)
     if (la_act) {
       const AgentDev &oa = agents[la_agent];
@@ -470,7 +471,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
       }
       // results are stored as soon as they exist: the per-pose arrays of this tail do not fit the register file
       // together (they spill to AGPRs, which costs more than the stores)
-      const bool reset = accel && advance == 2 && restart_now;  // restart iteration: V = Y = X (k_nest_reset)
+      const bool reset = accel && advance == PADV_PIPELINED && restart_now;  // restart iteration: V = Y = X (k_nest_reset)
       double v[4 * R];
       if (accel) {
         if (reset) {
@@ -484,7 +485,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
         }
       }
       PC_STAMP(10);
-      if (accel && (ahead & 1)) {
+      if (accel && (ahead & PA_OWN)) {
         // Nesterov step of iteration k+1 for this pose (what k_nest_pre would do next): XPrev = X, then
         //   k+1 regular:  Y = proj((1 - alpha') X + alpha' V), X = Y (V = proj(V) is the identity: V was just projected)
         //   k+1 restarts: V = Y = X unless this agent is selected again (X does not move)
@@ -586,7 +587,7 @@ void launch_precond(const LaunchCtx &c, int sel, int max_n, int mode, int xb, in
   AgentDev none{};
   const AgentDev &agv = baked ? c.host_agents[sel] : none;
 #define PC_LAUNCH(M, KCV, TLV)                                                                                      \
-    if (baked && M == PM_RGD_ && accel == 1 && advance == 2 && ahead == 3) {                                        \
+    if (baked && M == PM_RGD_ && accel == 1 && advance == PADV_PIPELINED && ahead == PA_LOOKAHEAD) {                                      \
       DPGO_DISPATCH_R(c.r, hipLaunchKernelGGL((k_precond<R, PM_RGD_, KCV, TLV, true, true>), dim3(grid, c.ny), dim3(256), 0, c.stream, \
                                               c.agents, c.team, sel, xb, vb, zb, sp, max_inner, step, accel, num_robots,   \
                                               advance, restart_interval, ahead, c.nest_all, agv));                         \

@@ -360,12 +360,12 @@ int exchange_pairs(dpgo_team_t *t, std::vector<Pair> pairs) {
     for (auto &kv : P.out)
       if (kv.second.len && bad == ncclSuccess) {
         bad = api->Send(x.d_send.p + kv.second.off, kv.second.len, ncclDouble, kv.first, x.comm->comm, t->stream);
-        x.counters[0] += 1; x.counters[2] += 8.0 * kv.second.len;
+        x.counters[x.MSG_SENT] += 1; x.counters[x.BYTES_SENT] += 8.0 * kv.second.len;
       }
     for (auto &kv : P.in)
       if (kv.second.len && bad == ncclSuccess) {
         bad = api->Recv(x.d_recv.p + kv.second.off, kv.second.len, ncclDouble, kv.first, x.comm->comm, t->stream);
-        x.counters[1] += 1; x.counters[3] += 8.0 * kv.second.len;
+        x.counters[x.MSG_RECEIVED] += 1; x.counters[x.BYTES_RECEIVED] += 8.0 * kv.second.len;
       }
     const ncclResult_t end = api->GroupEnd();
     NCCLC(bad);
@@ -443,13 +443,12 @@ int dpgo_team_run_ranks(dpgo_team_t *t, const int *sel_ids, int iters) {
   const unsigned seqs = p.acceleration ? 3u : 1u;
   for (int q = 0; q < iters; ++q) {
     const int sel_id = sel_ids[q];
-    auto it = t->id2local.find(sel_id);
-    const int sel = (it == t->id2local.end()) ? -2 : it->second;
+    const int sel = local_or_remote(t, sel_id);
     const long long k = t->iter;
-    const bool restart = p.acceleration && ((t->iter + 2) % p.restart_interval) == 0;
+    const bool restart = restart_due(t);
     // iterate(false) moves X and Y of everyone but the token holder BEFORE the token holder's neighbours publish them
     if (p.acceleration) for (int a = 0; a < NR; ++a) if (a != sel_id) x.version[a] = k + 1;
-    int rc = enqueue_team_iteration(t, false, restart, sel, 1);
+    int rc = enqueue_team_iteration(t, false, restart, sel, PHASE_BEGIN);
     if (rc) return rc;
     // the neighbours of the token holder that live elsewhere publish to it -- those whose copy there is too old
     Book K = book_of(t);
@@ -457,10 +456,9 @@ int dpgo_team_run_ranks(dpgo_team_t *t, const int *sel_ids, int iters) {
     rc = exchange_pairs(t, v);
     if (rc) return rc;
     if (sel >= 0 && !neighbor_poses_ready(*t->ag[sel], p.acceleration ? 1 : 0)) { set_err("run_ranks: neighbour poses missing (call dpgo_team_exchange_all_ranks once after set_initial)"); return DPGO_NOT_READY; }
-    rc = enqueue_team_iteration(t, false, restart, sel, 2, /* mid_run: no statistics but for the last of the call */ q + 1 < iters);
+    rc = enqueue_team_iteration(t, false, restart, sel, PHASE_END, /* mid_run: no statistics but for the last of the call */ q + 1 < iters);
     if (rc) return rc;
-    const bool fused = p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && !restart && sel >= 0 && !p.rgd_line_search;
-    account_iteration(t, sel, fused || t->last_iteration_folded);
+    account_iteration(t, sel, t->last_update_src);
     x.version[sel_id] = k + 1;
     x.iter_seen = t->iter;
   }

@@ -43,7 +43,7 @@ __device__ __forceinline__ void solve_tail(const AgentDev *__restrict__ agents, 
       double x[4 * R], xp[4 * R];
 #pragma unroll
       for (int i = 0; i < 4 * R; ++i) { x[i] = ag.buf[B_X][o + i]; xp[i] = ag.buf[B_XPREV][o + i]; }
-      if (tail & 1) {
+      if (tail & RTR_TAIL_NEST_V) {
         const double gamma = ag.scal[6];
         double v[4 * R], y[4 * R];
 #pragma unroll
@@ -60,8 +60,8 @@ __device__ __forceinline__ void solve_tail(const AgentDev *__restrict__ agents, 
     rel = wave_sum(rel);
     if (tid == 0) ag.part[PART_B + (size_t)bx * PART_STRIDE + 2] = rel;
   }
-  if (bx == 0 && tid == 0 && !(tail & 4)) {  // (bit 2: the per-agent API -- the caller's report advances this agent alone)
-    for (int k = 0; k < team->num_agents; ++k) advance_agent(agents[k], tail & 1, num_robots, restart_interval);
+  if (bx == 0 && tid == 0 && !(tail & RTR_TAIL_NO_ADVANCE)) {  // (bit 2: the per-agent API -- the caller's report advances this agent alone)
+    for (int k = 0; k < team->num_agents; ++k) advance_agent(agents[k], tail & RTR_TAIL_NEST_V, num_robots, restart_interval);
     team->iter += 1;
   }
 }

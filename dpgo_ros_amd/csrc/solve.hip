@@ -1,5 +1,5 @@
 // solve.hip -- launch sequencing: one agent's local solve (RTR with tCG / fused RGD), PGOAgent::iterate,
-// the synchronous team iteration and the colour-parallel group update.  The host enqueues blind launch
+// one synchronous team iteration with its host-side books, and the colour-parallel group update (team_run.hip drives them).  The host enqueues blind launch
 // patterns; every decision (accept/reject, tCG termination, schedule) is taken on the device.
 #include <fcntl.h>
 #include <sys/file.h>
@@ -71,7 +71,7 @@ bool neighbor_poses_ready(const Agent &a, int aux) {
 }
 
 // ---- the local solve (QuadraticOptimizer::optimize), enqueued on the team stream -------------
-// sel >= 0: that local agent (host-driven), sel == -1: device-selected (graph capture).
+// sel >= 0: that local agent (host-driven), SEL_SCHED: device-selected (graph capture).
 // RGD returns after enqueueing; the RTR path synchronises once per tCG chunk to read the
 // device-side solver state.
 //   fused: the iteration's tail (Nesterov V update, |X - XPrev|^2, end-of-iteration bookkeeping)
@@ -88,6 +88,18 @@ int ls_trials(const dpgo_params_t &p) { return std::max(1, std::min(p.rgd_ls_max
 
 double spmm_bytes_of(const dpgo_team *t, const Agent &a) {
   return 8.0 * (16.0 * a.col.size() + 3.0 * t->prm.r * 4 * a.n) + 4.0 * (a.col.size() + a.n + 1);
+}
+
+// roofline counters: preconditioner applies and sparse evaluations of agent `a`, each with the bytes of its operator
+void count_work(dpgo_team *t, const Agent &a, double precond_applies, double evals) {
+  t->counters[CNT_PRECOND] += precond_applies; t->counters[CNT_PRECOND_BYTES] += precond_applies * precond_operator_bytes(a);
+  t->counters[CNT_EVALS] += evals; t->counters[CNT_EVAL_BYTES] += evals * spmm_bytes_of(t, a);
+}
+
+// the block update is the fused RGD step (k_precond<PM_RGD>: step, Nesterov V update and |X - XPrev|^2 in one launch, its
+// status partials in PART_B[2]); a restart iteration and the line search take the un-fused sequence
+bool fused_rgd_step(const dpgo_params_t &p, bool restart) {
+  return p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && !restart && !p.rgd_line_search;
 }
 
 int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl) {
@@ -116,9 +128,8 @@ int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl) {
       if (!fl.skip_stats) launch_eval(c, sel, mn, B_X, B_EGRAD, B_GF, PART_A, eval_opts(t, 0, 0, 0));
       if (sel >= 0 && !fl.capture) {
         Agent &a = *t->ag[sel];
-        if (p.rgd_use_preconditioner) { t->counters[0] += 1; t->counters[1] += precond_operator_bytes(a); }
         const int passes = (fl.skip_stats ? 1 : 2) + (ntr + 3) / 4;  // passes over the sparse operator
-        t->counters[2] += passes; t->counters[3] += passes * spmm_bytes_of(t, a);
+        count_work(t, a, p.rgd_use_preconditioner ? 1 : 0, passes);
         // (without the closing evaluation PART_A holds the trial costs of k_ls_cost, not f_opt / |grad|^2: nothing may
         // read them as the solve's result)
         a.opt_pending_rgd = !fl.skip_stats;
@@ -129,7 +140,7 @@ int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl) {
       // K3: preconditioner + RGD step + Nesterov V + |dX|^2 (+ the team's end-of-iteration bookkeeping);
       // K5: f_opt / gradnorm_opt on the snapshot B_X2 that K3 leaves behind
       launch_precond(c, sel, mn, PM_RGD_, B_X, B_GF, B_Z, 0, 0, p.rgd_stepsize, p.acceleration, p.num_robots,
-                     fl.last_advances ? 1 : 0, p.restart_interval);
+                     fl.last_advances ? PADV_TEAM : PADV_NONE, p.restart_interval);
       // (mid-run iterations of a run of many -- dpgo_team_run_ranks -- leave the statistics out: nobody reads them)
       if (!fl.skip_stats) {
         if (fl.report_tail && t->rep_offer.valid && sel >= 0 && !fl.capture) {
@@ -138,7 +149,8 @@ int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl) {
           ReportTail rt = t->rep_offer.rt;
           const int ppb = 64 / p.r;
           rt.ai = sel;
-          rt.stat_off = PART_B + 2; rt.stat_cnt = precond_nblk(a); rt.stat_stride = PART_STRIDE;
+          const StatusSpan sp = status_span(a, REL_FUSED_B);
+          rt.stat_off = sp.off; rt.stat_cnt = sp.cnt; rt.stat_stride = sp.stride;
           rt.opt_nb = (a.n + ppb - 1) / ppb;
           rt.advance = 1; rt.accel = p.acceleration; rt.num_robots = p.num_robots; rt.restart_interval = p.restart_interval;
           launch_eval_report(c, sel, mn, B_X2, B_EGRAD2, B_GF2, PART_A, eval_opts(t, 0, 0, 0), rt);
@@ -158,9 +170,8 @@ int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl) {
     }
     if (sel >= 0 && !fl.capture) {
       Agent &a = *t->ag[sel];
-      if (p.rgd_use_preconditioner) { t->counters[0] += 1; t->counters[1] += precond_operator_bytes(a); }
       const bool stats = !(fl.skip_stats && fl.fused && p.rgd_use_preconditioner);
-      t->counters[2] += stats ? 2 : 1; t->counters[3] += (stats ? 2 : 1) * spmm_bytes_of(t, a);
+      count_work(t, a, p.rgd_use_preconditioner ? 1 : 0, stats ? 2 : 1);
       a.opt_pending_rgd = stats;  // (without them PART_A still holds an older solve's sums: nothing may read it as this one's)
     }
     return 0;
@@ -184,8 +195,6 @@ int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl) {
     a.opt.rtr_outer_iters = hs->outer_count; a.opt.tcg_iters_total = hs->tcg_total;
     a.opt.hessvec_count = hs->hv_count; a.opt.precond_count = hs->pc_count; a.opt.accepted = hs->accepted;
     a.opt_pending_rgd = false;
-    t->counters[2] += hs->hv_count + 1 + hs->outer_count;
-    t->counters[3] += (hs->hv_count + 1 + hs->outer_count) * spmm_bytes_of(t, a);
   };
   const bool tl_fused = a.precond == DPGO_PRECOND_TWO_LEVEL && a.tl_plan.prod_post &&
                         rtr_fused_tl_eligible(p.r, a.tl_plan.nwg - a.tl_plan.nS2, tl_max_pre_poses(a.tl_plan), a.tl_plan.ns, t->num_cus, t->max_lds);
@@ -282,7 +291,7 @@ per_step:
   if (hs->outer_count > 0) a.tcg_hint = std::max(2, std::min(8, (hs->tcg_total + hs->outer_count - 1) / hs->outer_count + 1));
   for (int o = 0; o < 4; ++o) a.tcg_hint_o[o] = (o < hs->outer_count) ? hs->tcg_o[o] : 0;
   account();
-  t->counters[0] += hs->pc_count; t->counters[1] += hs->pc_count * precond_operator_bytes(a);
+  count_work(t, a, hs->pc_count, hs->hv_count + 1 + hs->outer_count);
   return 0;
 }
 
@@ -294,7 +303,7 @@ int enqueue_iterate(dpgo_team *t, int li, int do_opt, bool defer_advance) {
   LaunchCtx c = t->ctx();
   const dpgo_params_t &p = t->prm;
   const bool restart = p.acceleration && ((a.iter + 2) % p.restart_interval) == 0;
-  const bool fused = do_opt && p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && !restart && !p.rgd_line_search;
+  const bool fused = do_opt && fused_rgd_step(p, restart);
   OptFlags fl;
   fl.fused = fused;
   // (a fused step's statistics evaluation is the last launch of the call when the caller's report takes the bookkeeping)
@@ -303,7 +312,7 @@ int enqueue_iterate(dpgo_team *t, int li, int do_opt, bool defer_advance) {
   // iterate reads every neighbour that is readable in place (imported or co-resident) in place, like the team schedule
   fl.pull = t->peers.empty() ? 0 : 1;
   int rc = 0;
-  a.rel_src = 0;
+  a.rel_src = REL_TILES_D;
   if (t->pend_up.n0 + t->pend_up.n1 > 0) {  // (dpgo_agent_iterate: the first launch below also scatters the staged poses)
     c.up_slots = t->pend_up.slots; c.up_in = t->pend_up.in; c.up_n0 = t->pend_up.n0; c.up_n1 = t->pend_up.n1;
     t->pend_up = dpgo_team::PendingUpload();
@@ -319,19 +328,19 @@ int enqueue_iterate(dpgo_team *t, int li, int do_opt, bool defer_advance) {
     } else {
       launch_copy(c, li, li, 1, a.n, B_X, B_XPREV, 0);
     }
-    a.rel_src = 2;
+    a.rel_src = REL_NONE;
     if (!defer_advance) launch_advance(c, li, 1, p.acceleration, p.num_robots, p.restart_interval, 0);
     return 0;
   }
   if (p.acceleration) {
-    launch_nest_pre(c, do_opt ? li : -2, li, 1, a.n, p.num_robots, p.restart_interval);
+    launch_nest_pre(c, do_opt ? li : SEL_REMOTE, li, 1, a.n, p.num_robots, p.restart_interval);
     c.up_n0 = c.up_n1 = 0;
     if (do_opt) {
       fl.aux = 1;
       // RTR, non-restart iteration: the one-launch solve also takes the Nesterov V update and the status partials (what the
       // team schedule folds, enqueue_team_iteration; bit 2: this agent's bookkeeping stays with the caller's report) -- two
       // launches less in front of the host's wait; enqueue_optimize says whether that solve ran
-      if (p.method == DPGO_METHOD_RTR && !restart && defer_advance) fl.rtr_tail = 3 | 4;
+      if (p.method == DPGO_METHOD_RTR && !restart && defer_advance) fl.rtr_tail = RTR_TAIL_NEST_V | RTR_TAIL_STATUS | RTR_TAIL_NO_ADVANCE;
       rc = enqueue_optimize(t, li, fl);
       if (rc) return rc;
       const bool folded = p.method == DPGO_METHOD_RTR && fl.rtr_tail != 0 && t->last_rtr_folded;
@@ -342,18 +351,18 @@ int enqueue_iterate(dpgo_team *t, int li, int do_opt, bool defer_advance) {
         if (rc) return rc;
         launch_nest_reset(c, li, a.n);
       }
-      if (fused || folded) a.rel_src = 1; else launch_status(c, li, li, 1, a.n, 1);
+      if (fused || folded) a.rel_src = REL_FUSED_B; else launch_status(c, li, li, 1, a.n, 1);
     }
   } else {
     launch_copy(c, li, li, 1, a.n, B_X, B_XPREV, 0);
     bool folded = false;
     if (do_opt) {
-      if (p.method == DPGO_METHOD_RTR && defer_advance) fl.rtr_tail = 2 | 4;
+      if (p.method == DPGO_METHOD_RTR && defer_advance) fl.rtr_tail = RTR_TAIL_STATUS | RTR_TAIL_NO_ADVANCE;
       rc = enqueue_optimize(t, li, fl);
       if (rc) return rc;
       folded = p.method == DPGO_METHOD_RTR && fl.rtr_tail != 0 && t->last_rtr_folded;
     }
-    if (fused || folded) a.rel_src = 1; else launch_status(c, li, li, 1, a.n, do_opt ? 1 : 0);
+    if (fused || folded) a.rel_src = REL_FUSED_B; else launch_status(c, li, li, 1, a.n, do_opt ? 1 : 0);
   }
   if (!defer_advance) launch_advance(c, li, 1, p.acceleration, p.num_robots, p.restart_interval, 0);
   return 0;
@@ -383,10 +392,9 @@ int refresh_rtr_result(dpgo_team *t, Agent &a, bool drained) {
   a.opt.hessvec_count = hs->hv_count; a.opt.precond_count = hs->pc_count; a.opt.accepted = hs->accepted;
   unsigned long long d[4];
   for (int k = 0; k < 4; ++k) { d[k] = a.h_rtr_cum.p[k] - a.rtr_seen[k]; a.rtr_seen[k] = a.h_rtr_cum.p[k]; }
-  t->counters[0] += (double)d[2];
-  t->counters[1] += (double)d[0] * precond_operator_bytes(a);  // the operator leaves HBM once per solve
-  t->counters[2] += (double)(d[1] + d[0] + d[3]);
-  t->counters[3] += (double)(d[1] + d[0] + d[3]) * spmm_bytes_of(t, a);
+  t->counters[CNT_PRECOND] += (double)d[2];
+  t->counters[CNT_PRECOND_BYTES] += (double)d[0] * precond_operator_bytes(a);  // the operator leaves HBM once per solve
+  count_work(t, a, 0, (double)(d[1] + d[0] + d[3]));
   return 0;
 }
 
@@ -448,35 +456,36 @@ int compute_residuals(dpgo_team *t, Agent &a, std::vector<double> &res) {
 }
 
 // One global RBCD iteration over the agents of this team.
-//   sel: local index of the agent that optimizes, -1 = device-selected (graph capture), -2 = the
+//   sel: local index of the agent that optimizes, SEL_SCHED = device-selected (graph capture), SEL_REMOTE = the
 //        selected agent lives on another rank (every local agent runs iterate(false)).
-//   phase: 0 whole iteration; 1 = begin (everything before the neighbour exchange: Nesterov Y/X/V of all
-//          local agents); 2 = end (local solve of `sel` + bookkeeping).
+//   phase: PHASE_WHOLE; PHASE_BEGIN (everything before the neighbour exchange: Nesterov Y/X/V of all
+//          local agents); PHASE_END (local solve of `sel` + bookkeeping).
+// Leaves in t->last_update_src where the status partials of the block update lie.
 int enqueue_team_iteration(dpgo_team *t, bool capture, bool restart, int sel, int phase, bool mid_run) {
   LaunchCtx c = t->ctx();
   const dpgo_params_t &p = t->prm;
   const int na = (int)t->ag.size();
   const int mn = t->max_n;
-  const bool fused = p.method == DPGO_METHOD_RGD && p.rgd_use_preconditioner && !restart && sel != -2 && !p.rgd_line_search;
+  const bool fused = sel != SEL_REMOTE && fused_rgd_step(p, restart);
   OptFlags fl;
   fl.pull = 1; fl.capture = capture; fl.fused = fused; fl.last_advances = fused;
   int rc = 0;
-  if (phase != 2) {
+  if (phase != PHASE_END) {
     if (p.acceleration) launch_nest_pre(c, sel, -1, na, mn, p.num_robots, p.restart_interval);  // K1 (+ publishes cur_sel)
-    else launch_copy(c, -3, -1, na, mn, B_X, B_XPREV, capture ? 1 : 0);
+    else launch_copy(c, SEL_EVERY, -1, na, mn, B_X, B_XPREV, capture ? 1 : 0);
   }
-  if (phase == 1) return 0;
+  if (phase == PHASE_BEGIN) return 0;
   bool folded = false;
-  if (sel != -2) {
+  if (sel != SEL_REMOTE) {
     fl.aux = p.acceleration ? 1 : 0;
     // RTR, non-restart iteration: the one-launch solve also takes the Nesterov V update, the status partials and the
     // end-of-iteration bookkeeping (three launches less); enqueue_optimize reports whether that solve ran
-    if (p.method == DPGO_METHOD_RTR && sel >= 0 && !capture && !restart) fl.rtr_tail = p.acceleration ? 3 : 2;
+    if (p.method == DPGO_METHOD_RTR && sel >= 0 && !capture && !restart) fl.rtr_tail = RTR_TAIL_STATUS | (p.acceleration ? RTR_TAIL_NEST_V : 0);
     // RGD with the line search, non-restart iteration: k_ls_apply also takes the Nesterov V update, the status tiles and
     // the end-of-iteration bookkeeping; mid-run iterations of a graph leave out the statistics nobody reads
-    const bool ls_folded = p.method == DPGO_METHOD_RGD && p.rgd_line_search && !restart && phase == 0;
-    if (ls_folded) { fl.ls_tail = p.acceleration ? 3 : 1; fl.skip_stats = mid_run; }
-    if (fused && phase == 2) fl.skip_stats = mid_run;  // (the split iteration of the multi-rank runs)
+    const bool ls_folded = p.method == DPGO_METHOD_RGD && p.rgd_line_search && !restart && phase == PHASE_WHOLE;
+    if (ls_folded) { fl.ls_tail = LS_TAIL_STATUS | (p.acceleration ? LS_TAIL_NEST_V : 0); fl.skip_stats = mid_run; }
+    if (fused && phase == PHASE_END) fl.skip_stats = mid_run;  // (the split iteration of the multi-rank runs)
     rc = enqueue_optimize(t, sel, fl);
     if (rc) return rc;
     folded = (p.method == DPGO_METHOD_RTR && t->last_rtr_folded) || ls_folded;
@@ -495,26 +504,33 @@ int enqueue_team_iteration(dpgo_team *t, bool capture, bool restart, int sel, in
     }
   }
   if (!fused && !folded) launch_advance(c, -1, na, p.acceleration, p.num_robots, p.restart_interval, 1);
-  t->last_iteration_folded = folded && p.method == DPGO_METHOD_RTR;  // (status source: PART_B[2] for the folded RTR solve only)
+  // the fused step and the one-launch RTR solve that took the tail leave PART_B[2]; everything else (the un-fused sequence's
+  // k_status, k_ls_apply with its tail) the tiles
+  t->last_update_src = (fused || (folded && p.method == DPGO_METHOD_RTR)) ? REL_FUSED_B : REL_TILES_E;
   return 0;
 }
 
-// host-side bookkeeping after one global iteration in which local agent `sel` (or nobody: -2) optimized
-void account_iteration(dpgo_team *t, int sel, bool fused) {
+// host-side books of `n` iterations that every local agent took part in; the team's own counter moves by team_n
+void count_iterations(dpgo_team *t, int n, int team_n) {
+  for (auto &a : t->ag) { a->iter += n; if (t->prm.robust_cost_type != DPGO_COST_L2) a->robust_inner_iter += n; }
+  t->iter += team_n;
+  t->counters[CNT_ITERATIONS] += team_n;
+}
+
+// host-side bookkeeping after one global iteration in which local agent `sel` (or nobody: SEL_REMOTE) optimized, its status
+// partials left at `src` (t->last_update_src)
+void account_iteration(dpgo_team *t, int sel, int src) {
   const dpgo_params_t &p = t->prm;
   for (auto &a : t->ag) {
-    a->rel_src = p.acceleration ? 0 : 2;  // non-accelerated iterate(false) leaves X untouched
-    a->iter += 1;
-    if (p.robust_cost_type != DPGO_COST_L2) a->robust_inner_iter += 1;
+    a->rel_src = p.acceleration ? REL_TILES_D : REL_NONE;  // non-accelerated iterate(false) leaves X untouched
     if (p.acceleration) a->publish_requested = true;
   }
   if (sel >= 0) {
-    t->ag[sel]->rel_src = fused ? 1 : 0;
+    t->ag[sel]->rel_src = src == REL_FUSED_B ? REL_FUSED_B : REL_TILES_D;  // (k_status / k_ls_apply leave the tiles in PART_D too)
     t->ag[sel]->publish_requested = true;
-    mark_optimized(t, *t->ag[sel], fused ? 1 : 5, true);
+    mark_optimized(t, *t->ag[sel], src, true);
   }
-  t->iter += 1;
-  t->counters[4] += 1;
+  count_iterations(t, 1, 1);
 }
 
 // ---- colour-parallel sweeps: the agents of one colour class share no edge, so their block
@@ -543,8 +559,7 @@ int enqueue_optimize_group(dpgo_team *t, int g) {
     launch_eval(c, sel, mn, B_X, B_EGRAD, B_GF, PART_A, eval_opts(t, 0, 0, 0));
     for (int k : mem) {
       Agent &a = *t->ag[k];
-      if (p.rgd_use_preconditioner) { t->counters[0] += 1; t->counters[1] += precond_operator_bytes(a); }
-      t->counters[2] += 2; t->counters[3] += 2 * spmm_bytes_of(t, a);
+      count_work(t, a, p.rgd_use_preconditioner ? 1 : 0, 2);
       a.opt_pending_rgd = true;
     }
     return 0;
@@ -614,9 +629,7 @@ int enqueue_optimize_group(dpgo_team *t, int g) {
     a.opt.hessvec_count = hs.hv_count; a.opt.precond_count = hs.pc_count; a.opt.accepted = hs.accepted;
     a.opt_pending_rgd = false;
     if (hs.outer_count > 0) a.tcg_hint = std::max(2, std::min(8, (hs.tcg_total + hs.outer_count - 1) / hs.outer_count + 1));
-    t->counters[0] += hs.pc_count; t->counters[1] += hs.pc_count * precond_operator_bytes(a);
-    t->counters[2] += hs.hv_count + 1 + hs.outer_count;
-    t->counters[3] += (hs.hv_count + 1 + hs.outer_count) * spmm_bytes_of(t, a);
+    count_work(t, a, hs.pc_count, hs.hv_count + 1 + hs.outer_count);
   }
   return 0;
 }

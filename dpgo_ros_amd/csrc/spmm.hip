@@ -342,9 +342,9 @@ __global__ __launch_bounds__(64) void k_stats_nest(const AgentDev *__restrict__ 
   const int nb_nest = nest_tiles * num_agents;
   const int b = (int)blockIdx.x;
   if (b < nb_nest) {
-    nest_pre_body<R>(agents, team, -1, -1, num_robots, restart_interval, b % nest_tiles, b / nest_tiles, TX, TV);
+    nest_pre_body<R>(agents, team, SEL_SCHED, -1, num_robots, restart_interval, b % nest_tiles, b / nest_tiles, TX, TV);
   } else {
-    eval_body<R>(agents, team, -5, B_X2, B_EGRAD2, B_GF2, PART_A, 0, 0, b - nb_nest, TX.d, TV.d, agents[0]);
+    eval_body<R>(agents, team, SEL_STATS, B_X2, B_EGRAD2, B_GF2, PART_A, 0, 0, b - nb_nest, TX.d, TV.d, agents[0]);
   }
 }
 
@@ -379,9 +379,9 @@ __global__ __launch_bounds__(64) void k_eval_stats(const AgentDev *__restrict__ 
     return;
   }
   if (has_eval && b < nb_eval) {
-    eval_body<R, false, BAKED>(agents, team, eval_sel >= 0 ? eval_sel : (first ? -1 : -6), B_X, B_EGRAD, B_GF, PART_C, 2, 1, b, Ysh, Wsh, agv);
+    eval_body<R, false, BAKED>(agents, team, eval_sel >= 0 ? eval_sel : (first ? SEL_SCHED : SEL_NEXT), B_X, B_EGRAD, B_GF, PART_C, 2, 1, b, Ysh, Wsh, agv);
   } else if (has_stats) {
-    eval_body<R>(agents, team, stats_sel >= 0 ? stats_sel : -5, B_X2, B_EGRAD2, B_GF2, PART_A, 0, 0,
+    eval_body<R>(agents, team, stats_sel >= 0 ? stats_sel : SEL_STATS, B_X2, B_EGRAD2, B_GF2, PART_A, 0, 0,
                  b - (has_eval ? nb_eval : 0), Ysh, Wsh, agents[0]);
   }
 }

@@ -1,5 +1,6 @@
 // team_internal.h -- host-side state of libdpgo_hip.so shared by assembly.hip (structure + data matrices),
-// solve.hip (launch sequencing of the local solves and the team schedule) and capi.hip (the C-ABI).
+// solve.hip (launch sequencing of the local solves and of one team iteration), team_run.hip (the drivers of the team
+// schedule) and capi.hip (the rest of the C-ABI).
 // Mirrors the DPGO::PGOAgent call surface consumed by src/PGOAgentROS.cpp.  All state
 // (X, XPrev, Y, V, Q, G, dense preconditioner, neighbour slabs, solver scalars) lives in HBM; the host only
 // sequences launches.  There is no CPU fallback: every entry point that computes fails with DPGO_ERR when
@@ -12,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -131,6 +133,28 @@ struct PinnedBuf {
   }
 };
 
+// where the |X - XPrev|^2 partials of an agent lie (AgentDev::part): Agent::rel_src -- left by the last kernel that moved X --
+// and Agent::opt_rel_src -- left by its last block update, iterate(true); status_span() turns one into offset / count / stride
+enum StatusSrc {
+  REL_NEVER = -1,   // (opt_rel_src only) the agent has not optimized yet
+  REL_TILES_D = 0,  // PART_D, one partial per 64-pose tile (k_nest_pre, k_status)
+  REL_FUSED_B = 1,  // PART_B[2], one per workgroup of the fused RGD step -- or of a one-launch RTR solve that took the iteration's tail
+  REL_NONE = 2,     // X untouched: nothing to sum
+  REL_POSE_D = 4,   // PART_D, one double per pose (look-ahead Nesterov step of a pipelined run)
+  REL_TILES_E = 5,  // PART_E, the tiles of the last iterate(true) (k_status with opt != 0, k_ls_apply with a tail)
+};
+
+// indices of dpgo_team::counters: the positions dpgo_team_get_counters documents (include/dpgo_hip.h)
+enum Counter {
+  CNT_PRECOND = 0, CNT_PRECOND_BYTES, CNT_EVALS, CNT_EVAL_BYTES, CNT_ITERATIONS, CNT_REPORT_WAIT_US, CNT_REPORTS,
+  CNT_ONE_LAUNCH, CNT_CARRIED, CNT_DEEP, CNT_REPORT_TAILS, CNT_COUNT
+};
+static_assert(CNT_ITERATIONS == 4 && CNT_ONE_LAUNCH == 7 && CNT_REPORT_TAILS == 10 && CNT_COUNT == 11, "positions are part of the C-ABI");
+
+// `phase` of enqueue_team_iteration: the whole iteration; everything in front of the neighbour exchange (the Nesterov step of
+// every local agent); the rest (the token holder's block update and the bookkeeping)
+constexpr int PHASE_WHOLE = 0, PHASE_BEGIN = 1, PHASE_END = 2;
+
 struct Agent {
   int id = 0, local = 0;
   std::vector<dpgo_measurement_t> odom, priv, shared;
@@ -190,10 +214,9 @@ struct Agent {
   PinnedBuf<dpgo::RtrState> h_rtr;
   unsigned long long rtr_seen[4] = {0, 0, 0, 0};
   bool opt_pending_rtr = false;  // a.opt / the team counters lag behind the device: refresh_rtr_result() catches up
-  int rel_src = 0;  // where the last |X - XPrev|^2 partials live: 0 PART_D (per 64-pose tile), 1 PART_B[2] (fused RGD),
-                    // 2 none (X untouched), 4 PART_D one double per pose (look-ahead Nesterov step)
+  int rel_src = REL_TILES_D;  // where the last |X - XPrev|^2 partials live (StatusSrc)
   // status of the last iterate(true) (a9; refreshed only when the agent optimizes unless status_every_iterate):
-  // where its |X - XPrev|^2 partials live (-1 never optimized, 1 PART_B[2], 2 X untouched, 5 PART_E tiles), whether
+  // where its |X - XPrev|^2 partials live (opt_rel_src: REL_NEVER, REL_FUSED_B, REL_NONE or REL_TILES_E), whether
   // the solve ran, the share of converged GNC weights at that moment, and the host copy once it has been read
   // host-boundary batching (the per-agent API a ROS wrapper drives): public poses of all neighbours and both sequences
   // are fetched with ONE copy and served from this cache until the team launches anything again; neighbour poses
@@ -217,7 +240,7 @@ struct Agent {
     unsigned long long expect = 0, epoch = 0;
     std::chrono::steady_clock::time_point t_launch{};
   } rep;
-  int opt_rel_src = -1;
+  int opt_rel_src = REL_NEVER;
   bool opt_success = false, opt_cached = false;
   double opt_ratio = 1.0, opt_rel_change = 0.0;
   DevBuf<SharedEdgeDev> d_se;
@@ -269,7 +292,7 @@ struct dpgo_team {
   std::map<int, hipGraphExec_t> graphs;            // key: see dpgo_team_run
   std::map<int, int> graph_flip;
   bool graph_valid = false;
-  double counters[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double counters[dpgo_host::CNT_COUNT] = {};  // (dpgo_host::Counter)
   // X / Y arrays of robots that live in other processes, imported through HIP IPC (dpgo_team_import_peer): their
   // public poses are read in place over peer access instead of travelling as messages
   struct Peer { double *base = nullptr; size_t off_x = 0, off_y = 0; int n = 0; };
@@ -292,9 +315,7 @@ struct dpgo_team {
   int use_fe_deep = 1;     // DPGO_FE_DEEP=0: no deep-carried one-launch iterations (step_deep.hip): k_step_fe serves every run
   int prefetch_reports = 1;  // DPGO_REPORT_PREFETCH=0: the host does not prefetch an arrived report's image
   int use_report_tail = 1;  // DPGO_REPORT_TAIL=0: the report of an RGD iterate(true) stays a launch of its own (k_report)
-  int use_fe_persist = 0;  // DPGO_FE_PERSIST=1: a run of deep-carried iterations is ONE persistent launch (step_persist.hip)
-  dpgo_host::DevBuf<unsigned long long> d_pd_bar;  // its hand-off counters (zeroed in front of every launch)
-  dpgo_host::DevBuf<double> d_fd_pacc;  // their partial sums: two alternating buffers of [workgroup][r][256] doubles
+  dpgo_host::DevBuf<double> d_fd_pacc;  // partial sums of the deep-carried iterations: two alternating buffers of [workgroup][r][256] doubles
   int fe_min_n = 0;        // smallest agent the one-launch iteration serves (DPGO_FE_MIN_N; any n >= 32 works, bitwise).  0 = by
                            // measurement: 32 where every iteration finds carried rows (round 5), else 449 -- without carried rows:
                            // measured per iteration, two-launch | one-launch (profiles/experiments/fe_small.py, sphere2500, r = 5):
@@ -320,7 +341,7 @@ struct dpgo_team {
   int stage_cap = 0;            // k_eval_staged: most shared edges a 64 / r-pose tile of any agent carries (0: the plain k_eval)
   int bake_sel = 1;  // DPGO_BAKE_SEL=0: the graphs of the pipelined iteration select their agent on the device only
   int bake_desc = 1; // DPGO_BAKE_DESC=0: ... and find its descriptor in the device array instead of in their arguments
-  bool last_iteration_folded = false;  // ... and enqueue_team_iteration skipped k_nest_post / k_status / k_advance for it
+  int last_update_src = dpgo_host::REL_TILES_E;  // what the last enqueue_team_iteration left as the status of its block update (StatusSrc)
   bool last_rtr_folded = false;  // the last enqueue_optimize ran the one-launch solve WITH the iteration's tail
   bool rtr_validated = false;  // a one-launch solve has completed on this device (its grid is resident at once)
   int use_fused_rtr = 1;  // DPGO_FUSED_RTR=0 keeps the launch-per-step RTR sequence (solve.hip) for every agent
@@ -343,7 +364,8 @@ struct dpgo_team {
     dpgo_host::DevBuf<double> d_send, d_recv;                 // staging of one batch of messages
     long long iter_seen = -1;                                 // team iteration this bookkeeping is valid for (anything else that
                                                               // advanced the team in between invalidates `sent`)
-    double counters[4] = {0, 0, 0, 0};                        // messages sent / received, bytes sent / received (this rank)
+    enum { MSG_SENT = 0, MSG_RECEIVED, BYTES_SENT, BYTES_RECEIVED, NUM_COUNTERS };  // (dpgo_team_comm_counters)
+    double counters[NUM_COUNTERS] = {};
   } rx;
   // per-iteration log: one CSV per local robot in the reference's column order (src/PGOAgentROS.cpp:863-864,
   // 883-891) + global_cost; written by dpgo_team_run_schedule, which then runs one iteration per host round trip
@@ -386,6 +408,17 @@ inline double precond_operator_bytes(const Agent &a) {
   return 8.0 * 16.0 * (double)a.n * (double)a.n;
 }
 inline int precond_nblk(const Agent &a) { return a.precond == DPGO_PRECOND_TWO_LEVEL ? a.tl_plan.nwg - a.tl_plan.nA : (4 * a.n + 7) / 8; }
+// the partials a status source names: first double (from AgentDev::part), how many, how far apart
+struct StatusSpan { int off, cnt, stride; };
+inline StatusSpan status_span(const Agent &a, int src) {
+  switch (src) {
+    case REL_FUSED_B: return {PART_B + 2, precond_nblk(a), PART_STRIDE};
+    case REL_POSE_D: return {PART_D, a.n, 1};
+    case REL_TILES_D: return {PART_D, (a.n + 63) / 64, PART_STRIDE};
+    case REL_TILES_E: return {PART_E, (a.n + 63) / 64, PART_STRIDE};
+    default: return {PART_B + 2, 0, PART_STRIDE};  // REL_NONE / REL_NEVER: nothing to read
+  }
+}
 
 // ---- assembly.hip
 Agent *find_agent(dpgo_team *t, int id);
@@ -398,6 +431,18 @@ int sync_descs(dpgo_team *t);          // structure / data matrices / descriptor
 int sync_descs_noflush(dpgo_team *t);  // the same without the upload (used while poses are being staged)
 int flush_stage(dpgo_team *t);
 int stage_to_pinned(dpgo_team *t, Agent &a, int *n0, int *n1);
+
+// local index of a robot, SEL_REMOTE if it lives elsewhere; the team's next iteration is a periodic restart of the acceleration
+inline int local_or_remote(const dpgo_team *t, int robot) { auto it = t->id2local.find(robot); return it == t->id2local.end() ? SEL_REMOTE : it->second; }
+inline bool restart_due(const dpgo_team *t) { return t->prm.acceleration && ((t->iter + 2) % t->prm.restart_interval) == 0; }
+
+// ---- team_run.hip (the drivers of the team schedule) and what capi.hip shares with them
+void drop_graphs(dpgo_team *t);          // every captured graph of the team, destroyed and forgotten
+int check_exchange_error(dpgo_team *t);  // DPGO_ERR (once) if an in-kernel exchange has timed out since the last look
+int ensure_mailbox(dpgo_team *t);        // capi.hip: the team's mailbox of the device-side UPDATE token
+bool fused_eval_eligible(dpgo_team *t);  // the one-launch iteration (step_fused.hip) may serve this team
+int fe_deep_m0(dpgo_team *t);            // > 0: ... in the deep-carried form (step_deep.hip)
+int fe_carry_flags(dpgo_team *t, int rep, int nfe, int iter0);  // FE_CARRY_* of launch `rep` of a one-launch run from iteration iter0
 
 // ---- chordal.hip
 // every end point inside [0, n) and every pose joined to pose 0 by edges of positive weight, else DPGO_ERR with a message
@@ -412,8 +457,8 @@ void mark_optimized(dpgo_team *t, Agent &a, int rel_src, bool success);
 struct OptFlags {
   int aux = 0, pull = 0;
   bool capture = false, fused = false, last_advances = false;
-  int rtr_tail = 0;  // one-launch RTR solve: fold the rest of the iteration into it (bit 0: Nesterov V update; status + advance)
-  int ls_tail = 0;   // RGD line search: fold the rest of the iteration into k_ls_apply (1: status + advance, 3: + Nesterov V)
+  int rtr_tail = 0;  // one-launch RTR solve: fold the rest of the iteration into it (RTR_TAIL_* bits, kernels.h)
+  int ls_tail = 0;   // RGD line search: fold the rest of the iteration into k_ls_apply (LS_TAIL_* bits)
   bool skip_stats = false;  // ... and leave out the closing statistics evaluation (mid-run iterations of a graph: nobody reads them)
   bool report_tail = false;  // the closing statistics evaluation is the call's last launch: it may carry the team's rep_offer
 };
@@ -422,8 +467,12 @@ EvalOpts eval_opts(const dpgo_team *t, int gmode, int aux, int advance);
 double spmm_bytes_of(const dpgo_team *t, const Agent &a);
 int enqueue_optimize(dpgo_team *t, int sel, const OptFlags &fl);
 int enqueue_iterate(dpgo_team *t, int li, int do_opt, bool defer_advance = false);
+bool fused_rgd_step(const dpgo_params_t &p, bool restart);
+// (leaves the status source of the token holder's block update in t->last_update_src, which account_iteration takes)
 int enqueue_team_iteration(dpgo_team *t, bool capture, bool restart, int sel, int phase, bool mid_run = false);
-void account_iteration(dpgo_team *t, int sel, bool fused);
+void count_work(dpgo_team *t, const Agent &a, double precond_applies, double evals);
+void count_iterations(dpgo_team *t, int n, int team_n);
+void account_iteration(dpgo_team *t, int sel, int src);
 int enqueue_optimize_group(dpgo_team *t, int g);
 int fetch_scal(dpgo_team *t, Agent &a);
 int refresh_rgd_result(dpgo_team *t, Agent &a);

@@ -102,3 +102,28 @@ def test_agent_api_and_colour_classes():
         assert (rh.ls_backoffs, rh.accepted) == (ro.ls_backoffs, ro.accepted)
     assert np.abs(th.global_X() - to.global_X()).max() < 1e-10
     th.close()
+
+
+@pytest.mark.parametrize("accel", [0, 1])
+def test_split_iteration_reports_the_status_tiles_it_wrote(accel):
+    """dpgo_team_step_begin / dpgo_team_step_end with the line search: a split iteration runs the un-fused sequence, whose
+    k_status leaves the |X - XPrev|^2 tiles of the block update in PART_E -- that is where the token holder's status has to
+    be read from, on restart iterations (iterations 5 and 12 here: (k + 2) % 7 == 0) and on the others alike.  The twin
+    is driven by dpgo_team_run, which the tests above hold to the oracle; the bound is theirs for the status."""
+    kw = dict(method=capi.METHOD_RGD, rgd_stepsize=1.6 if accel else 1.0, rgd_use_preconditioner=1, acceleration=accel,
+              restart_interval=7, rgd_line_search=1)
+    ts, _, _ = make_pair("smallGrid3D", 2, **kw)
+    tr, _, _ = make_pair("smallGrid3D", 2, **kw)
+    for k in range(16):
+        sel = k % 2  # (the default schedule: the local agents in turn)
+        ts.step_begin(sel)
+        ts.step_end(sel)
+        tr.run(1)
+        ss, sr = ts.agents[sel].status(), tr.agents[sel].status()
+        print("split iteration %2d agent %d: relative_change %.17g (split) %.17g (run), iteration_number %d %d"
+              % (k, sel, ss.relative_change, sr.relative_change, ss.iteration_number, sr.iteration_number))
+        assert ss.iteration_number == sr.iteration_number == k + 1, k
+        assert abs(ss.relative_change - sr.relative_change) < 1e-9, (k, sel)
+    assert np.abs(ts.global_X() - tr.global_X()).max() < 1e-9
+    ts.close()
+    tr.close()
