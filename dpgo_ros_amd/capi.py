@@ -98,6 +98,7 @@ WEIGHT_LIBRARY, WEIGHT_WRAPPER = 0, 1
 OK, NOT_READY, ERR = 0, 1, -1
 CERT_NO_DEFLATION, CERT_NO_PRECONDITIONER, CERT_ETA_RELATIVE = 1, 2, 4
 ROUND_REFINE_TRANSLATIONS = 1
+COV_SCHUR = 1  # DPGO_COV_SCHUR
 PRECOND_AUTO, PRECOND_DENSE, PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL = 0, 1, 2, 3
 
 # every symbol include/dpgo_hip.h declares (checked by tests/test_abi.py)
@@ -124,7 +125,7 @@ dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_
 dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
 dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
-dpgo_team_marginal_covariances""".split()
+dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across""".split()
 
 
 class DpgoError(RuntimeError):
@@ -967,24 +968,45 @@ class Team:
                  "round_across")
         return res, T
 
-    def covariances(self, T=None, pairs=None):
+    def covariances(self, T=None, pairs=None, method=None, transport=None, owner_of_robot=None):
         """Marginal pose covariances at the trajectory T (12 doubles per pose in team order; None: the rounding of the
         current iterate, self.round()): (Covariance, diag[N, 6, 6], cross[len(pairs), 6, 6]).  Pose i is perturbed by
         (phi, delta), rotation first: R_i <- R_i Exp(phi) (body frame), t_i <- t_i + delta (world frame); pose 0 is held
         fixed (its blocks are zero).  The blocks are those of the inverse of the cost's Hessian at the measurements' current
-        weights; cross[k] is the block of the pose pair pairs[k] = (a, b).  Raises DpgoError when T is not in SE(3), the
-        weighted graph is disconnected, the dense Hessian does not fit the device, or T is not a minimum (a non-positive
-        pivot).  Changes no solver state."""
+        weights; cross[k] is the block of the pose pair pairs[k] = (a, b).  method: "dense" (the default of one team) inverts
+        the whole reduced Hessian, "schur" eliminates the poses without shared edges robot by robot and inverts only the Schur
+        complement on the public poses -- the same blocks to round-off, in a fraction of the memory and time when the robots
+        share few poses.  Raises DpgoError when T is not in SE(3), the weighted graph is disconnected, the matrices do not fit
+        the device, or T is not a minimum (a non-positive pivot).  Changes no solver state.
+        With a transport (a team split across participants, owner_of_robot as for certify / round): the Schur path is the
+        only method ("dense" raises ValueError; the default means "schur").  T and diag are this team's poses in team order,
+        pairs name poses of the whole problem (robots by id, then poses; pose 0 is robot 0's first pose), the same list on
+        every participant, and cross is complete on every participant; the scalars are identical everywhere."""
+        if method not in (None, "dense", "schur"):
+            raise ValueError("covariances: method must be \"dense\" or \"schur\", not %r" % (method,))
+        if transport is not None and method == "dense":
+            raise ValueError("covariances: a team split across participants has no dense path (method=\"dense\" with a "
+                             "transport)")
+        if method is None:
+            method = "dense" if transport is None else "schur"
         N = int(sum(self.agents[i].n for i in self.ids))
         if T is None:
-            T = self.round()[1]
+            T = (self.round() if transport is None else self.round(transport=transport, owner_of_robot=owner_of_robot))[1]
         T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
         if T.size != 12 * N:
             raise ValueError("covariances: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
         pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
         res, diag, cross = Covariance(), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
-        _chk(lib().dpgo_team_marginal_covariances(self.h, _d(T), 0, len(pr), _d(pr) if len(pr) else None, _d(diag),
-                                                  _d(cross) if len(pr) else None, C.byref(res)), "marginal_covariances")
+        flags = COV_SCHUR if method == "schur" else 0
+        if transport is None:
+            _chk(lib().dpgo_team_marginal_covariances(self.h, _d(T), flags, len(pr), _d(pr) if len(pr) else None, _d(diag),
+                                                      _d(cross) if len(pr) else None, C.byref(res)), "marginal_covariances")
+        else:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_marginal_covariances_across(self.h, C.byref(transport.struct), _d(own), _d(T), flags, len(pr),
+                                                             _d(pr) if len(pr) else None, _d(diag),
+                                                             _d(cross) if len(pr) else None, C.byref(res)),
+                 "marginal_covariances_across")
         return res, diag, cross
 
 
@@ -1084,16 +1106,17 @@ def _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, 
 
 
 def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None,
-                    refine_translations=True, certify_kw=None, device=0, covariances=False):
+                    refine_translations=True, certify_kw=None, device=0, covariances=False, covariance_method="dense"):
     """End to end: the Riemannian staircase, then the SE-Sync rounding of its final point (Team.round on the final team).
     Returns dict(T=trajectory, 12 doubles per pose in team order anchored at the first pose, r=final rank, ranks,
     certificate, rounding=Rounding, f_relaxed, f_rounded, gap_rel, escape_costs).  gap_rel = (f_rounded - f_relaxed) /
     f_relaxed bounds the relative suboptimality of T (up to the certificate's eta) when the point is certified; it is None
-    otherwise.  covariances=True adds covariances=(Covariance, diag[N, 6, 6]): Team.covariances of the final team at T."""
+    otherwise.  covariances=True adds covariances=(Covariance, diag[N, 6, 6]): Team.covariances of the final team at T by
+    covariance_method ("dense" or "schur")."""
     def round_final(team, out):
         out["rounding"], out["T"] = team.round(refine_translations=refine_translations)
         if covariances:
-            out["covariances"] = team.covariances(out["T"])[:2]
+            out["covariances"] = team.covariances(out["T"], method=covariance_method)[:2]
 
     out = _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, None, 30, certify_kw, device,
                      on_final=round_final)

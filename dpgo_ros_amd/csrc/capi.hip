@@ -1678,7 +1678,7 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
     set_err(std::string(what) + ": null argument");
     return DPGO_ERR;
   }
-  if (flags != 0) { set_err(std::string(what) + ": flags must be 0"); return DPGO_ERR; }
+  if (flags != 0 && flags != DPGO_COV_SCHUR) { set_err(std::string(what) + ": flags must be 0 or DPGO_COV_SCHUR"); return DPGO_ERR; }
   if (dpgo_cert::check_team_local(t, what)) return DPGO_ERR;
   const int na = (int)t->ag.size();
   std::vector<int> offs(na + 1, 0);
@@ -1720,6 +1720,20 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
     return DPGO_OK;
   }
   HIPC(hipSetDevice(t->device));
+  if (flags == DPGO_COV_SCHUR) {
+    // by robot-wise Schur complement (covariance_schur.hip): its own memory accounting, from the partition
+    int fail[3] = {0, 0, 0};
+    const int rc = dpgo_cert::covariance_schur_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail);
+    if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
+    if (rc > 0) {
+      const std::string where = fail[0] < 0 ? "the Schur complement on the public poses"
+                                            : "the interior Hessian of robot " + std::to_string(t->ag[fail[0]]->id);
+      set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(fail[2]) + " of " + where + " (pose " +
+              std::to_string(fail[1]) + "): the Hessian is not positive definite at this T: not a minimum");
+      return DPGO_ERR;
+    }
+    return rc;
+  }
   {
     // three dense matrices of order 6 (N - 1); idle pooled buffers count as used memory but are one flush away from free
     // (the accounting of the preconditioner budget, assembly.hip)
@@ -1728,8 +1742,10 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
     HIPC(hipMemGetInfo(&free_b, &total_b));
     const double avail = (double)free_b + (double)pool_held(t->device);
     if (need > avail) {
-      char buf[240];
-      std::snprintf(buf, sizeof buf, "%s: the dense Hessian of order %.0f and its inverse need %.0f bytes, %.0f are available on the device",
+      char buf[400];
+      std::snprintf(buf, sizeof buf,
+                    "%s: the dense Hessian of order %.0f and its inverse need %.0f bytes, %.0f are available on the device.  "
+                    "flags = DPGO_COV_SCHUR (method=\"schur\") eliminates one robot's interior at a time and needs far less",
                     what, n, need, avail);
       set_err(buf);
       return DPGO_ERR;
@@ -1745,4 +1761,11 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
   }
   if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
   return rc;
+}
+
+// the same call over a split team (covariance_schur.hip): the Schur path is its only method
+extern "C" int dpgo_team_marginal_covariances_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
+                                                     const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
+                                                     double *cov_pairs, dpgo_covariance_t *res) {
+  return dpgo_cert::covariance_schur_across(t, tr, owner_rank_of_robot, T, flags, num_pairs, pairs, cov_diag, cov_pairs, res);
 }

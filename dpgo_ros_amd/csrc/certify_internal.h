@@ -155,5 +155,15 @@ int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flag
 // DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian was not positive
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
                       dpgo_covariance_t *res);
+// k_cov_logdet on a Cholesky factor left in A: out[0 .. 2] = 2 sum log L_kk, min L_kk^2, max L_kk^2
+int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out);
+// the same call by robot-wise Schur complement (covariance_schur.hip; flags = DPGO_COV_SCHUR): DPGO_OK, DPGO_ERR with a message,
+// or 1 when a pivot was not positive -- fail[0] the local index of the robot whose interior block failed (-1: the separator),
+// fail[1] the team pose of the pivot, fail[2] its row in that factor
+int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
+                            dpgo_covariance_t *res, int *fail);
+// the same over a split team (dpgo_team_marginal_covariances_across; covariance_schur.hip)
+int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
+                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
 
 }  // namespace dpgo_cert

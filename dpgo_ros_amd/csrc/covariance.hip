@@ -18,20 +18,9 @@
 // neighbour is pose i -- holds Q_ij[cp][c] at [cp + 4 c] (the record: its negative).
 // Nothing here writes a solver vector: the buffers come from the device pool and go back to it.
 #include "certify_internal.h"
+#include "covariance_block.h"
 
 namespace dpgo {
-
-// one block of H_red: block row bi, block column bj (team poses, both >= 1); its S block is the sum of `count` stored blocks
-// src[first ..] in list order (parallel edges between two robots are separate shared-edge records)
-struct CovItem {
-  int bi, bj, first, count;
-};
-// where a stored block lives: idx >= 0 entry idx of the agent's block-CSR, idx < 0 shared-edge record ~idx
-struct CovSrc {
-  int agent, idx;
-};
-
-__device__ __forceinline__ int cov_eps(int a, int b, int c) { return ((a - b) * (b - c) * (c - a)) / 2; }
 
 // One work item per thread.  Both blocks of a symmetric pair are formed by the same arithmetic: the thread always forms
 // H_lo,hi (lo = min(bi, bj)) from S_lo,hi and the two rotations and stores it or its transpose, so H is bitwise symmetric
@@ -46,100 +35,10 @@ __global__ __launch_bounds__(256) void k_cov_assemble(const AgentDev *__restrict
   typedef int v4i_t __attribute__((ext_vector_type(4)));
   const v4i_t wi = *(const __attribute__((address_space(1))) v4i_t *)(items + it);
   const CovItem w{wi.x, wi.y, wi.z, wi.w};
-  // S_bi,bj[cp][c] at s[cp + 4 c]
-  double s[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) s[u] = 0.0;
-  for (int k = 0; k < w.count; ++k) {
-    const int *qs = (const int *)(src + w.first + k);
-    const CovSrc q{gp(qs)[0], gp(qs)[1]};
-    const AgentDev &ag = agents[q.agent];
-    const double *bp = q.idx >= 0 ? ag.qval + (size_t)16 * q.idx : ag.se[~q.idx].coef;
-    const double sg = q.idx >= 0 ? 1.0 : -1.0;
-#pragma unroll
-    for (int u = 0; u < 16; u += 2) {
-      const double2 v = ld2(bp + u);
-      s[u] += sg * v.x;
-      s[u + 1] += sg * v.y;
-    }
-  }
-  const bool diag = w.bi == w.bj, flip = w.bi > w.bj;
-  const int lo = flip ? w.bj : w.bi, hi = flip ? w.bi : w.bj;
-  // S_lo,hi[cp][c]
-  double S[4][4];
-#pragma unroll
-  for (int cp = 0; cp < 4; ++cp)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) S[cp][c] = flip ? s[c + 4 * cp] : s[cp + 4 * c];
-  if (diag) {
-    const double *L = lam + (size_t)9 * lo;
-#pragma unroll
-    for (int cp = 0; cp < 3; ++cp)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) S[cp][c] -= gp(L)[3 * cp + c];
-  }
-  double Rl[3][3], Rh[3][3];  // [b][c]
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      Rl[b][c] = gp(T)[((size_t)4 * lo + c) * 3 + b];
-      Rh[b][c] = gp(T)[((size_t)4 * hi + c) * 3 + b];
-    }
-  double M[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int l = 0; l < 3; ++l) M[k][l] = Rl[0][k] * Rh[0][l] + Rl[1][k] * Rh[1][l] + Rl[2][k] * Rh[2][l];
   double Hc[6][6];  // H_lo,hi
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      double rr = 0.0, rt = 0.0, tr = 0.0;
-#pragma unroll
-      for (int cp = 0; cp < 3; ++cp) {
-        if (cp == a) continue;
-        const int k = 3 - a - cp;
-        const double ea = (double)cov_eps(a, cp, k);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          if (c == b) continue;
-          const int l = 3 - b - c;
-          rr += S[cp][c] * (ea * (double)cov_eps(b, c, l)) * M[k][l];
-        }
-        rt += S[cp][3] * ea * Rl[b][k];
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (c == b) continue;
-        const int l = 3 - b - c;
-        tr += S[3][c] * (double)cov_eps(b, c, l) * Rh[a][l];
-      }
-      Hc[a][b] = rr;
-      Hc[a][3 + b] = rt;
-      Hc[3 + a][b] = tr;
-      Hc[3 + a][3 + b] = a == b ? S[3][3] : 0.0;
-    }
-  if (diag) {
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int b = 0; b < a; ++b) Hc[a][b] = Hc[b][a];
-  }
+  cov_form_block(agents, src, w, T, lam, Hc, w.bi > w.bj);
   // H_bi,bj[a][b] at H[(6 (bj - 1) + b) n + 6 (bi - 1) + a]: 48 contiguous, 16-byte aligned bytes per column
-  double *base = H + (size_t)6 * (w.bj - 1) * n + (size_t)6 * (w.bi - 1);
-#pragma unroll
-  for (int b = 0; b < 6; ++b) {
-    v2d_t *col = (v2d_t *)(base + (size_t)b * n);
-#pragma unroll
-    for (int a = 0; a < 6; a += 2) {
-      v2d_t v;
-      v.x = flip ? Hc[b][a] : Hc[a][b];
-      v.y = flip ? Hc[b][a + 1] : Hc[a + 1][b];
-      gp(col)[a / 2] = v;
-    }
-  }
+  cov_store_block(H + (size_t)6 * (w.bj - 1) * n + (size_t)6 * (w.bi - 1), (size_t)n, Hc, w.bi > w.bj);
 }
 
 // out[0] = 2 sum_k log L_kk, out[1] / out[2] = the smallest / largest L_kk^2, L the Cholesky factor left in A (n x n
@@ -189,6 +88,12 @@ __global__ __launch_bounds__(256) void k_cov_extract(const double *__restrict__ 
 }  // namespace dpgo
 
 namespace dpgo_cert {
+
+int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out) {
+  k_cov_logdet<<<1, 256, 0, s>>>(A, n, out);
+  HIPC(hipGetLastError());
+  return DPGO_OK;
+}
 
 // The device part of dpgo_team_marginal_covariances (capi.hip has made every host-side refusal): descriptors synchronised,
 // T on the device, Lambda, H_red, its inverse, the requested blocks.  The outputs are written only when the factorisation

@@ -1,0 +1,1280 @@
+// covariance_schur.hip -- the marginal pose covariances of covariance.hip by robot-wise Schur complement.
+//
+// A pose that no shared-edge record names (an INTERIOR pose) couples only to poses of its own robot.  Ordered as
+// [interior of robot 0 | ... | interior of robot A-1 | all PUBLIC poses (the separator S, team order)], H_red is block
+// arrowhead:
+//     H_II,a   the interior block of robot a (order 6 |I_a|),   B_a = H_IS,a  (6 |I_a| x 6 s_a: an interior pose touches only
+//     the s_a public poses of its own robot),   H_SS (order 6 |S|).
+// Per robot, one after another:  C_a = H_II,a^-1 (dense_spd_inverse),  W_a = C_a B_a,  H_SS[s_a, s_a] -= B_a^T W_a.  The
+// contribution lands inside the robot's own diagonal block of the separator: nothing is summed across robots.  Then
+// Sigma_SS = S_c^-1 and
+//     Sigma_ii = C_a[ii] + (Z_a W_a^T)[ii],  Z_a = W_a Sigma_SS[s_a, s_a]                 (i interior of a)
+//     Sigma_ij = C_a[ij] + Z_a[i,:] W_a[j,:]^T                                           (i, j interior of a)
+//     Sigma_ij = W_a[i,:] Sigma_SS[s_a, s_b] W_b[j,:]^T                                  (interior of a, interior of b != a)
+//     Sigma_is = -W_a[i,:] Sigma_SS[s_a, s]                                              (interior, public)
+//     Sigma_st = the block of Sigma_SS                                                   (public, public)
+//     log det H_red = sum_a log det H_II,a + log det S_c      (summed on the host in robot order, the separator last).
+// Kept per robot: W_a, the diagonal blocks of C_a and its blocks of requested pairs, log det and pivots; C_a is dropped.
+//
+// THE ROW-OWNER RULE.  A symmetric target (H_II,a, H_SS) is filled from the stored blocks S_ij with i <= j (team order)
+// alone: the thread forms H_ij and writes it and its transpose.  A stored block S_ij lives with the robot that holds pose
+// j -- entry (row j, column i) of its block-CSR, or a shared-edge record of its pose j.  So the lower-triangle block (row
+// pose j, column pose i, j > i) of H_SS between two robots is formed from the record of the robot that holds ROW j, and a
+// participant that holds only some robots can form the block rows of its own robots from what it stores.
+//
+// The products run on the fp64 matrix cores (k_dgemm below), one workgroup per 64 x 64 tile of the result with the K
+// loop in one fixed order: no split-K, no atomics, the same bits in every call.
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <tuple>
+
+#include "certify_internal.h"
+#include "covariance_block.h"
+
+namespace dpgo {
+
+// where an item's block goes: block (r, c) of the launch's column-major target (leading dimension ld).  Hc = H_lo,hi is
+// formed with bi as lo, or bj when CD_FLIP is set; the target receives Hc, or its transpose with CD_TRANS; with CD_MIRROR
+// the other one goes to block (c, r) as well (symmetric targets list every pair of poses once)
+struct CovDst {
+  int r, c, f, pad_;
+};
+constexpr int CD_FLIP = 1, CD_TRANS = 2, CD_MIRROR = 4;
+
+// k_cov_assemble's work item, written where the host's list says instead of at the global position.  The same per-block
+// arithmetic (cov_form_block), the same merged parallel edges, one writer per block.  bi, bj: rows of T (and of lam)
+__global__ __launch_bounds__(256) void k_cov_assemble_map(const AgentDev *__restrict__ agents, const CovItem *__restrict__ items,
+                                                          const CovSrc *__restrict__ src, const CovDst *__restrict__ dst, int nitems,
+                                                          const double *__restrict__ T, const double *__restrict__ lam,
+                                                          double *__restrict__ H, int ld) {
+  const int it = blockIdx.x * 256 + threadIdx.x;
+  if (it >= nitems) return;
+  typedef int v4i_t __attribute__((ext_vector_type(4)));
+  const v4i_t wi = *(const __attribute__((address_space(1))) v4i_t *)(items + it);
+  const v4i_t di = *(const __attribute__((address_space(1))) v4i_t *)(dst + it);
+  const CovItem w{wi.x, wi.y, wi.z, wi.w};
+  double Hc[6][6];  // H_lo,hi
+  cov_form_block(agents, src, w, T, lam, Hc, (di.z & CD_FLIP) != 0);
+  const size_t r = (size_t)6 * di.x, c = (size_t)6 * di.y;
+  const bool tr = (di.z & CD_TRANS) != 0;
+  cov_store_block(H + c * ld + r, (size_t)ld, Hc, tr);
+  if ((di.z & CD_MIRROR) && di.x != di.y) cov_store_block(H + r * ld + c, (size_t)ld, Hc, !tr);
+}
+
+// ---- C = op(A) B (sub: C -= op(A) B), column-major, op(A) m x k (TA: A is k x m and transposed), B k x n, any m, n, k >= 1
+// and leading dimensions.  One workgroup of 256 threads = 4 waves per 64 x 64 tile of C; a K slab of 32 is staged in LDS
+// (zero padded past the edges), the next slab's loads are in flight under the products.  v_mfma_f64_16x16x4_f64: operands
+// A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], result D[row = (lane >> 4) + 4 reg][col = lane & 15]
+// (the f64 map, not the f32 one).  As in dense_inverse.hip the instruction's ROW index carries the matrix COLUMN j and its
+// column index the matrix row i, so the 16 lanes that share a result register store 16 consecutive rows of one column.
+// Wave w owns the quadrant rows 32 (w & 1), columns 32 (w >> 1) as 2 x 2 blocks of 16 x 16.  An element's sum runs over k in
+// index order whatever tile it lies in.
+constexpr int GK = 32;
+typedef double v4f64_t __attribute__((ext_vector_type(4)));
+
+template <bool TA>
+__global__ __launch_bounds__(256) void k_dgemm(const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb,
+                                               double *__restrict__ C, int ldc, int m, int n, int k, int sub) {
+  __shared__ double As[GK][65], Bs[GK][65];
+  const int tid = threadIdx.x, i0 = 64 * blockIdx.x, j0 = 64 * blockIdx.y;
+  double ra[8], rb[8];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t = tid + 256 * q;
+      const int kb = t & 31, jb = t >> 5;  // B: consecutive threads run down a column of B
+      const double vb = gp(B)[(size_t)min(j0 + jb, n - 1) * ldb + min(k0 + kb, k - 1)];
+      rb[q] = (k0 + kb < k && j0 + jb < n) ? vb : 0.0;
+      if (TA) {
+        const double va = gp(A)[(size_t)min(i0 + jb, m - 1) * lda + min(k0 + kb, k - 1)];
+        ra[q] = (k0 + kb < k && i0 + jb < m) ? va : 0.0;
+      } else {
+        const int ia = t & 63, ka = t >> 6;
+        const double va = gp(A)[(size_t)min(k0 + ka, k - 1) * lda + min(i0 + ia, m - 1)];
+        ra[q] = (k0 + ka < k && i0 + ia < m) ? va : 0.0;
+      }
+    }
+  };
+  v4f64_t acc[2][2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int v = 0; v < 2; ++v) acc[u][v] = v4f64_t{0.0, 0.0, 0.0, 0.0};
+  const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int ib = 32 * (wave & 1), jbase = 32 * (wave >> 1);
+  load(0);
+  for (int k0 = 0; k0 < k; k0 += GK) {
+    __syncthreads();  // (the products of the slab before this one have read LDS)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t = tid + 256 * q;
+      Bs[t & 31][t >> 5] = rb[q];
+      if (TA) As[t & 31][t >> 5] = ra[q];
+      else As[t >> 6][t & 63] = ra[q];
+    }
+    __syncthreads();
+    if (k0 + GK < k) load(k0 + GK);
+#pragma unroll
+    for (int kk = 0; kk < GK; kk += 4) {
+      double a[2], b[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) { a[u] = Bs[kk + lk][jbase + 16 * u + li]; b[u] = As[kk + lk][ib + 16 * u + li]; }
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[v], b[u], acc[u][v], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = i0 + ib + 16 * u + li, j = j0 + jbase + 16 * v + lk + 4 * q;
+        if (i < m && j < n) {
+          double *c = C + (size_t)j * ldc + i;
+          gp(c)[0] = sub ? gp(c)[0] - acc[u][v][q] : acc[u][v][q];
+        }
+      }
+}
+
+// the upper triangle of the n x n column-major A from its lower one (the Schur complement B^T W is symmetric to round-off
+// only; the factorisation is handed a bitwise symmetric matrix)
+__global__ __launch_bounds__(256) void k_schur_mirror(double *__restrict__ A, int n) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)n * n) return;
+  const int i = (int)(e % n), j = (int)(e / n);
+  if (i > j) gp(A)[(size_t)i * n + j] = gp(A)[e];
+}
+
+// sum_k Z[rz, k] W[rw, k], k in index order, one fused multiply-add per term: EVERY row product of the extraction goes
+// through here, so a diagonal block and the pair (i, i) agree bitwise
+__device__ __forceinline__ double schur_row_dot(const double *__restrict__ Z, size_t ldz, int rz, const double *__restrict__ W,
+                                                size_t ldw, int rw, int K) {
+  double s = 0.0;
+  for (int k = 0; k < K; ++k) s = __builtin_fma(gp(Z)[(size_t)k * ldz + rz], gp(W)[(size_t)k * ldw + rw], s);
+  return s;
+}
+
+// a list entry of the extraction kernels: output block blk, two indices inside the launch's sets, one flag
+struct SchurBlk {
+  int blk, i, j, f;
+};
+// an interior pose in a pair across sets: output block, robot and interior index of the left pose, then the right one
+// (robot b and interior index, or b < 0 and the separator index), f: store the transpose
+struct SchurCross {
+  int blk, a, li, b, lj, f;
+};
+// robot a on the device: W_a (6 |I_a| x K, ld = 6 |I_a|), K = 6 s_a, soff = 6 x its first separator index
+struct SchurRobot {
+  const double *W;
+  int ld, K, soff, pad_;
+};
+
+// keep[36 blk + 6 a + b] = C[6 i + a, 6 j + b] of the n x n column-major C, one thread per element
+__global__ __launch_bounds__(256) void k_schur_keep(const double *__restrict__ Cm, int n, const SchurBlk *__restrict__ list, int count,
+                                                    double *__restrict__ keep) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)36 * count) return;
+  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
+  const int *lp = (const int *)(list + e / 36);
+  const int blk = gp(lp)[0], i = gp(lp)[1], j = gp(lp)[2];
+  gp(keep)[(size_t)36 * blk + q] = gp(Cm)[((size_t)6 * j + b) * n + (size_t)6 * i + a];
+}
+
+// the diagonal blocks of the interior poses of one robot: X = C_ii + Z[i,:] W[i,:]^T, out = (X + X^T) / 2 (both operands of an
+// element and of its mirror are the same two numbers: bitwise symmetric).  Thread e: row r = e mod nrows of Z (pose r / 6,
+// a = r mod 6: consecutive threads read consecutive rows), b = e / nrows.  ipose: team pose of interior index li
+__global__ __launch_bounds__(256) void k_schur_diag(const double *__restrict__ Z, const double *__restrict__ W, int nrows, int K,
+                                                    const int *__restrict__ ipose, const double *__restrict__ keep,
+                                                    double *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)6 * nrows) return;
+  const int r = (int)(e % nrows), b = (int)(e / nrows), li = r / 6, a = r - 6 * li;
+  const double sab = schur_row_dot(Z, nrows, r, W, nrows, 6 * li + b, K), sba = schur_row_dot(Z, nrows, 6 * li + b, W, nrows, r, K);
+  const size_t o = (size_t)36 * gp(ipose)[li];
+  gp(out)[o + 6 * a + b] = 0.5 * ((gp(keep)[o + 6 * a + b] + sab) + (gp(keep)[o + 6 * b + a] + sba));
+}
+
+// pairs of two interior poses of one robot: out = C_ij + Z[i,:] W[j,:]^T
+__global__ __launch_bounds__(256) void k_schur_pair_same(const double *__restrict__ Z, const double *__restrict__ W, int nrows, int K,
+                                                         const SchurBlk *__restrict__ list, int count, const double *__restrict__ keep,
+                                                         double *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)36 * count) return;
+  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
+  const int *lp = (const int *)(list + e / 36);
+  const int blk = gp(lp)[0], i = gp(lp)[1], j = gp(lp)[2];
+  const size_t o = (size_t)36 * blk + q;
+  gp(out)[o] = gp(keep)[o] + schur_row_dot(Z, nrows, 6 * i + a, W, nrows, 6 * j + b, K);
+}
+
+// blocks of Sigma_SS (M, order n): f = 1 a diagonal block, symmetrised as k_cov_extract does; f = 0 the block (i, j)
+__global__ __launch_bounds__(256) void k_schur_public(const double *__restrict__ M, int n, const SchurBlk *__restrict__ list, int count,
+                                                      double *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)36 * count) return;
+  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
+  const int *lp = (const int *)(list + e / 36);
+  const int blk = gp(lp)[0], i = gp(lp)[1], j = gp(lp)[2], f = gp(lp)[3];
+  const size_t oi = (size_t)6 * i, oj = (size_t)6 * j;
+  double v = gp(M)[(oj + b) * n + oi + a];
+  if (f) v = 0.5 * (v + gp(M)[(oi + a) * n + oi + b]);
+  gp(out)[(size_t)36 * blk + q] = v;
+}
+
+// interior pose i of robot a with public pose s: -W_a[i,:] Sigma_SS[s_a, s] (f: its transpose, the pair was (s, i))
+__global__ __launch_bounds__(256) void k_schur_pair_ip(const SchurRobot *__restrict__ robots, const double *__restrict__ M, int n,
+                                                       const SchurCross *__restrict__ list, int count, double *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)36 * count) return;
+  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
+  const int *lp = (const int *)(list + e / 36);
+  const int blk = gp(lp)[0], ra = gp(lp)[1], li = gp(lp)[2], s = gp(lp)[4], f = gp(lp)[5];
+  const SchurRobot R = robots[ra];
+  const double *col = M + ((size_t)6 * s + b) * n + R.soff;
+  double acc = 0.0;
+  for (int k = 0; k < R.K; ++k) acc = __builtin_fma(gp(R.W)[(size_t)k * R.ld + 6 * li + a], gp(col)[k], acc);
+  gp(out)[(size_t)36 * blk + (f ? 6 * b + a : 6 * a + b)] = -acc;
+}
+
+// interior poses of two different robots, first half: t[p][c][a] = sum_k W_a[6 li + a, k] Sigma_SS[s_a + k, s_b + c] for
+// the K_b columns c.  blockIdx.y: the pair of this chunk; a thread per column, the six rows at once (Sigma_SS is bitwise
+// symmetric: the element is read at [s_b + c, s_a + k], consecutive threads consecutive addresses)
+__global__ __launch_bounds__(256) void k_schur_cross_t(const SchurRobot *__restrict__ robots, const double *__restrict__ M, int n,
+                                                       const SchurCross *__restrict__ list, int kmax, double *__restrict__ tbuf) {
+  const int *lp = (const int *)(list + blockIdx.y);
+  const int ra = gp(lp)[1], li = gp(lp)[2], rb = gp(lp)[3];
+  const SchurRobot A = robots[ra], B = robots[rb];
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= B.K) return;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double *w = A.W + 6 * li, *sg = M + (size_t)A.soff * n + B.soff + c;
+  for (int k = 0; k < A.K; ++k) {
+    const double sv = gp(sg)[(size_t)k * n];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) acc[a] = __builtin_fma(gp(w)[(size_t)k * A.ld + a], sv, acc[a]);
+  }
+  double *o = tbuf + ((size_t)blockIdx.y * kmax + c) * 6;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) gp(o)[a] = acc[a];
+}
+
+// second half: out[a][b] = sum_c t[p][c][a] W_b[6 lj + b, c], c in index order
+__global__ __launch_bounds__(256) void k_schur_cross_out(const SchurRobot *__restrict__ robots, const SchurCross *__restrict__ list, int count,
+                                                         int kmax, const double *__restrict__ tbuf, double *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)36 * count) return;
+  const int p = (int)(e / 36), q = (int)(e % 36), a = q / 6, b = q - 6 * a;
+  const int *lp = (const int *)(list + p);
+  const int blk = gp(lp)[0], rb = gp(lp)[3], lj = gp(lp)[4];
+  const SchurRobot B = robots[rb];
+  const double *t = tbuf + (size_t)p * kmax * 6 + a;
+  double acc = 0.0;
+  for (int c = 0; c < B.K; ++c) acc = __builtin_fma(gp(t)[(size_t)6 * c], gp(B.W)[(size_t)c * B.ld + 6 * lj + b], acc);
+  gp(out)[(size_t)36 * blk + q] = acc;
+}
+
+}  // namespace dpgo
+
+namespace dpgo_cert {
+
+// C = op(A) B or C -= op(A) B on stream s (k_dgemm); nothing to do when a dimension is 0
+static void launch_dgemm(hipStream_t s, bool ta, const double *A, int lda, const double *B, int ldb, double *C, int ldc, int m, int n,
+                         int k, bool sub) {
+  if (m <= 0 || n <= 0 || k <= 0) return;
+  const dim3 grid((m + 63) / 64, (n + 63) / 64, 1);
+  if (ta) hipLaunchKernelGGL(k_dgemm<true>, grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, m, n, k, sub ? 1 : 0);
+  else hipLaunchKernelGGL(k_dgemm<false>, grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, m, n, k, sub ? 1 : 0);
+}
+
+// who is public, who is interior among a team's poses; the fixed pose (team index `zero`, -1: not in this
+// team) belongs to neither set
+struct SchurPartition {
+  int na = 0, N = 0, nS = 0, max_int = 0;
+  std::vector<int> offs, robot_of, pos, sep, sep_off;  // pos: index inside the pose's own set; sep: team pose of separator index
+  std::vector<char> pub;
+  std::vector<std::vector<int>> interior;              // team poses of robot a's interior, in order
+};
+
+static void schur_partition(dpgo_team_t *t, int zero, SchurPartition &P) {
+  P.na = (int)t->ag.size();
+  P.offs.assign(P.na + 1, 0);
+  for (int k = 0; k < P.na; ++k) P.offs[k + 1] = P.offs[k] + t->ag[k]->n;
+  P.N = P.offs[P.na];
+  P.robot_of.assign(P.N, 0);
+  P.pub.assign(P.N, 0);
+  P.pos.assign(P.N, 0);
+  for (int k = 0; k < P.na; ++k) {
+    for (int j = 0; j < t->ag[k]->n; ++j) P.robot_of[P.offs[k] + j] = k;
+    // an edge of weight 0 counts: the pattern does not depend on the weights
+    for (const SharedEdgeDev &se : t->ag[k]->se_host)
+      if (se.lpose >= 0 && se.lpose < t->ag[k]->n) P.pub[P.offs[k] + se.lpose] = 1;
+  }
+  P.interior.assign(P.na, {});
+  P.sep_off.assign(P.na + 1, 0);
+  for (int k = 0; k < P.na; ++k) {
+    for (int g = P.offs[k]; g < P.offs[k + 1]; ++g) {
+      if (g == zero) continue;
+      if (P.pub[g]) { P.pos[g] = (int)P.sep.size(); P.sep.push_back(g); }
+      else { P.pos[g] = (int)P.interior[k].size(); P.interior[k].push_back(g); }
+    }
+    P.sep_off[k + 1] = (int)P.sep.size();
+    P.max_int = std::max(P.max_int, (int)P.interior[k].size());
+  }
+  P.nS = (int)P.sep.size();
+}
+
+// pairs between interiors of two robots handled by one launch pair: the scratch t (6 kmax doubles each) stays within 64 MB
+// and the pair index, which rides on gridDim.y, within its limit of 65 535
+static size_t schur_cross_chunk(size_t pairs, int kmax) {
+  if (pairs == 0) return 0;
+  return std::max<size_t>(1, std::min<size_t>({pairs, (size_t)65535, ((size_t)8 << 20) / ((size_t)6 * std::max(kmax, 1))}));
+}
+
+// the device bytes of the call.  The large buffers: three square ones of order M = max(6 max_a |I_a|, 6 |S|),
+// the separator, every kept W_a, one more of the largest W_a (B_a, later Z_a).  The small ones: T, T Q, Lambda, the
+// Gershgorin scratch, the factors' statistics, the kept and the output blocks (2 x 36 (N + P) doubles, P pairs), the scratch
+// of the pairs between two robots' interiors (every pair counted as one), the block and pair lists, the work list (40 bytes per
+// stored block of Q), the maps, and the Linv blocks of dense_spd_inverse.  nS: the separator of the WHOLE problem (a split
+// team inverts it too); `who` names what sets M
+static double schur_bytes(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax, int num_pairs, std::string &who) {
+  int big = -1, max_n = 0;
+  size_t stored = 0;
+  for (int k = 0; k < P.na; ++k) {
+    if (big < 0 || P.interior[k].size() > P.interior[big].size()) big = k;
+    max_n = std::max(max_n, t->ag[k]->n);
+    stored += t->ag[k]->col.size() + t->ag[k]->se_host.size();
+  }
+  const double mi = 6.0 * P.max_int, ms = 6.0 * nS, M = std::max(mi, ms);
+  double w_all = 0.0, w_max = 0.0;
+  for (int k = 0; k < P.na; ++k) {
+    const double w = 36.0 * (double)P.interior[k].size() * (double)(P.sep_off[k + 1] - P.sep_off[k]);
+    w_all += w;
+    w_max = std::max(w_max, w);
+  }
+  who = ms >= mi ? "the separator of " + std::to_string(nS) + " public poses"
+                 : "the " + std::to_string(P.max_int) + " interior poses of robot " + std::to_string(t->ag[big]->id);
+  const double N = P.N, np = num_pairs, A = P.na;
+  const double small = 8.0 * (33.0 * N + A * ((max_n + 255) / 256) + 4.0 * (A + 1.0) + 72.0 * (N + np)) +
+                       8.0 * 6.0 * std::max(kmax, 1) * (double)schur_cross_chunk((size_t)num_pairs, kmax) + 16.0 * (N + np) + 24.0 * np +
+                       40.0 * (double)stored + 4.0 * (A + 1.0 + 2.0 * N) + 20.0 * (A + 2.0 * np) + 8.0 * 1024.0 * std::ceil(M / 32.0);
+  return 8.0 * (3.0 * M * M + ms * ms + w_all + w_max) + small;
+}
+
+static int schur_fits(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax, int num_pairs, const char *what, std::string &msg) {
+  std::string who;
+  const double need = schur_bytes(t, P, nS, kmax, num_pairs, who);
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { msg = std::string(what) + ": hipMemGetInfo failed"; return -1; }
+  const double avail = (double)free_b + (double)pool_held(t->device);
+  if (need <= avail) return 0;
+  char buf[400];
+  std::snprintf(buf, sizeof buf,
+                "%s: the Schur path needs %.0f bytes, set by %s, %.0f are available on the device; a team of more robots has "
+                "smaller interiors and needs less",
+                what, need, who.c_str(), avail);
+  msg = buf;
+  return -1;
+}
+
+// the work lists of the assembly: raw stored blocks, sorted by (list, block column, block row) and merged where they name
+// the same pose pair (parallel edges, in record order)
+struct SchurItems {
+  struct Raw { int bi, bj, agent, idx, list; CovDst d; };
+  std::vector<Raw> raw;
+  std::vector<CovItem> items;
+  std::vector<CovSrc> srcs;
+  std::vector<CovDst> dsts;
+  std::vector<int> lbeg;
+  void add(int list, int bi, int bj, int agent, int idx, int r, int c, int f) { raw.push_back({bi, bj, agent, idx, list, {r, c, f, 0}}); }
+  void finish(int nlists) {
+    std::stable_sort(raw.begin(), raw.end(), [](const Raw &x, const Raw &y) {
+      return x.list != y.list ? x.list < y.list : x.bj != y.bj ? x.bj < y.bj : x.bi < y.bi;
+    });
+    lbeg.assign(nlists + 1, 0);
+    int cur = -1;
+    for (const Raw &q : raw) {
+      if (q.list == cur && items.back().bi == q.bi && items.back().bj == q.bj) ++items.back().count;
+      else {
+        while (cur < q.list) lbeg[++cur] = (int)items.size();
+        items.push_back({q.bi, q.bj, (int)srcs.size(), 1});
+        dsts.push_back(q.d);
+      }
+      srcs.push_back({q.agent, q.idx});
+    }
+    while (cur < nlists) lbeg[++cur] = (int)items.size();
+  }
+  int count(int list) const { return lbeg[list + 1] - lbeg[list]; }
+};
+
+// events: a mark per phase boundary; phase of the interval that ENDS at a mark: 0 assembly, 1 interior factorisations,
+// 2 products, 3 separator inverse, 4 extraction, -1 not counted
+struct SchurMarks {
+  std::vector<hipEvent_t> ev;
+  std::vector<int> phase;
+  std::vector<std::string> note;  // products: the shapes, for the DPGO_TIMING report
+  std::vector<double> flops;
+  ~SchurMarks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+  int mark(int ph, hipStream_t s) {
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) { set_err("marginal_covariances: event failed"); return DPGO_ERR; }
+    ev.push_back(e);
+    phase.push_back(ph);
+    note.emplace_back();
+    flops.push_back(0.0);
+    if (hipEventRecord(e, s) != hipSuccess) { set_err("marginal_covariances: event failed"); return DPGO_ERR; }
+    return 0;
+  }
+};
+#define MARK(ph) do { if (marks.mark(ph, s)) return DPGO_ERR; } while (0)
+
+// the device side of one call: what a single team and a participant of a split team share
+struct SchurDev {
+  hipStream_t s = nullptr;
+  const AgentDev *agents = nullptr;
+  const double *Td = nullptr, *lam = nullptr;  // T rows (a participant: its halo behind its own poses), Lambda of the own poses
+  DevBuf<double> A, Wk, M, B;
+  DevBuf<CovItem> items;
+  DevBuf<CovSrc> src;
+  DevBuf<CovDst> dst;
+  DevBuf<SchurBlk> blk;
+  const SchurItems *L = nullptr;
+  void assemble(int list, double *H, int ld) const {
+    const int cnt = L->count(list);
+    if (cnt > 0)
+      k_cov_assemble_map<<<(unsigned)((cnt + 255) / 256), 256, 0, s>>>(agents, items.p + L->lbeg[list], src.p, dst.p + L->lbeg[list], cnt, Td,
+                                                                        lam, H, ld);
+  }
+};
+
+// One robot: H_II and B assembled (lists `lii`, `lb`), C = H_II^-1 into D.M, W = C B, Sd -= B^T W (Sd: the
+// robot's diagonal block of the separator, leading dimension lds), the statistics of the factor into stat[0 .. 2], the blocks
+// of C named by `keep` into keepd.  DPGO_OK, DPGO_ERR (message set), or row + 1 of a non-positive pivot.  A single team and
+// every participant of a split team come through here with the same shapes: the same bits.
+static int schur_robot_step(SchurDev &D, SchurMarks &marks, int robot_id, int lii, int lb, int ni, int K, double *W, double *Sd, int lds,
+                            const std::vector<SchurBlk> &keep, double *keepd, double *stat) {
+  hipStream_t s = D.s;
+  HIPC(hipMemsetAsync(D.A.p, 0, sizeof(double) * (size_t)ni * ni, s));
+  D.assemble(lii, D.A.p, ni);
+  if (K > 0) {
+    HIPC(hipMemsetAsync(D.B.p, 0, sizeof(double) * (size_t)ni * K, s));
+    D.assemble(lb, D.B.p, ni);
+  }
+  HIPC(hipGetLastError());
+  MARK(0);
+  const int f = dense_spd_inverse(s, D.A.p, D.Wk.p, D.M.p, ni);  // (synchronises the stream)
+  HIPC(hipGetLastError());
+  if (f < 0) { set_err("marginal_covariances: scratch allocation of the inverse failed"); return DPGO_ERR; }
+  if (f > 0) return f;
+  if (launch_cov_logdet(s, D.A.p, ni, stat)) return DPGO_ERR;
+  MARK(1);
+  launch_dgemm(s, false, D.M.p, ni, D.B.p, ni, W, ni, ni, K, ni, false);  // W_a = C_a B_a
+  launch_dgemm(s, true, D.B.p, ni, W, ni, Sd, lds, K, K, ni, true);       // S[s_a, s_a] -= B_a^T W_a
+  HIPC(hipGetLastError());
+  MARK(2);
+  marks.note.back() = "robot " + std::to_string(robot_id) + ": W = C B (" + std::to_string(ni) + " x " + std::to_string(K) + " x " +
+                      std::to_string(ni) + ") and B^T W (" + std::to_string(K) + " x " + std::to_string(K) + " x " + std::to_string(ni) + ")";
+  marks.flops.back() = 2.0 * ni * (double)ni * K + 2.0 * K * (double)K * ni;
+  // (keep is never empty: the diagonal blocks)
+  HIPC(hipMemcpyAsync(D.blk.p, keep.data(), sizeof(SchurBlk) * keep.size(), hipMemcpyHostToDevice, s));
+  k_schur_keep<<<(unsigned)((36 * keep.size() + 255) / 256), 256, 0, s>>>(D.M.p, ni, D.blk.p, (int)keep.size(), keepd);
+  HIPC(hipGetLastError());
+  MARK(4);
+  return DPGO_OK;
+}
+
+// The same robot once Sigma_SS (order nS) is known: Z = W Sigma_SS[s, s] into D.B, the diagonal blocks of its interior
+// poses and its pairs of two interior poses
+static int schur_robot_blocks(SchurDev &D, SchurMarks &marks, int robot_id, int ni, int K, const double *W, const double *Sss, int nS,
+                              const int *ipose_d, const std::vector<SchurBlk> &same, const double *keepd, double *outd) {
+  hipStream_t s = D.s;
+  launch_dgemm(s, false, W, ni, Sss, nS, D.B.p, ni, ni, K, K, false);
+  HIPC(hipGetLastError());
+  MARK(2);
+  marks.note.back() = "robot " + std::to_string(robot_id) + ": Z = W Sigma_SS[s, s] (" + std::to_string(ni) + " x " + std::to_string(K) + " x " +
+                      std::to_string(K) + ")";
+  marks.flops.back() = 2.0 * ni * (double)K * K;
+  k_schur_diag<<<(unsigned)(((size_t)6 * ni + 255) / 256), 256, 0, s>>>(D.B.p, W, ni, K, ipose_d, keepd, outd);
+  if (!same.empty()) {
+    HIPC(hipMemcpyAsync(D.blk.p, same.data(), sizeof(SchurBlk) * same.size(), hipMemcpyHostToDevice, s));
+    k_schur_pair_same<<<(unsigned)((36 * same.size() + 255) / 256), 256, 0, s>>>(D.B.p, W, ni, K, D.blk.p, (int)same.size(), keepd, outd);
+  }
+  HIPC(hipGetLastError());  // (D.blk and D.B serve the next robot: its copy and its product are ordered behind these on the stream)
+  MARK(4);
+  return DPGO_OK;
+}
+
+// pairs of interior poses of two robots: list entries name rows of the robot table (k_schur_cross_t / _out), in chunks
+static int schur_cross_pairs(hipStream_t s, const SchurRobot *rob_d, const double *Sss, int nS, const std::vector<SchurCross> &list,
+                             SchurCross *list_d, int kmax, double *tbuf, size_t chunk, double *outd) {
+  if (list.empty()) return DPGO_OK;
+  HIPC(hipMemcpyAsync(list_d, list.data(), sizeof(SchurCross) * list.size(), hipMemcpyHostToDevice, s));
+  for (size_t c0 = 0; c0 < list.size(); c0 += chunk) {
+    const int cnt = (int)std::min<size_t>(chunk, list.size() - c0);
+    k_schur_cross_t<<<dim3((kmax + 255) / 256, cnt, 1), 256, 0, s>>>(rob_d, Sss, nS, list_d + c0, kmax, tbuf);
+    k_schur_cross_out<<<(unsigned)((36 * (size_t)cnt + 255) / 256), 256, 0, s>>>(rob_d, list_d + c0, cnt, kmax, tbuf, outd);
+  }
+  HIPC(hipGetLastError());
+  return DPGO_OK;
+}
+
+static void schur_report(const SchurMarks &marks, double ms[5]) {
+  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+  for (int k = 0; k < 5; ++k) ms[k] = 0.0;
+  for (size_t k = 1; k < marks.ev.size(); ++k) {
+    float v = 0.f;
+    if (hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) != hipSuccess) continue;
+    if (marks.phase[k] >= 0) ms[marks.phase[k]] += v;
+    if (timing && marks.flops[k] > 0.0)
+      std::fprintf(stderr, "marginal_covariances (Schur): products, %s: %.3f ms, %.2f TFLOP/s\n", marks.note[k].c_str(), v,
+                   marks.flops[k] / (1e9 * v));
+  }
+}
+
+// The device part of dpgo_team_marginal_covariances with DPGO_COV_SCHUR (capi.hip has made the refusals that need no
+// partition).  DPGO_OK, DPGO_ERR (message set), or 1: a pivot was not positive -- fail[0] the robot's local index (-1: the
+// separator), fail[1] the team pose, fail[2] the row of that factor.  The outputs are written only when every factorisation
+// succeeded.
+int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
+                            dpgo_covariance_t *res, int *fail) {
+  const char *what = "marginal_covariances";
+  if (check_team(t, what)) return DPGO_ERR;
+  SchurPartition P;
+  schur_partition(t, 0, P);
+  const int na = P.na, N = P.N, nS = 6 * P.nS;
+  int max_n = 0, kmax = 0;
+  for (int k = 0; k < na; ++k) {
+    max_n = std::max(max_n, t->ag[k]->n);
+    kmax = std::max(kmax, 6 * (P.sep_off[k + 1] - P.sep_off[k]));
+  }
+  {
+    std::string msg;
+    if (schur_fits(t, P, P.nS, kmax, num_pairs, what, msg)) { set_err(msg); return DPGO_ERR; }
+  }
+  // ---- the work lists.  Every stored block of the team-wide Q outside pose 0's row and column is one of: interior x
+  // interior of one robot, interior x public of one robot (B_a, or its mirror, dropped), public x public.  Symmetric
+  // targets keep bi <= bj (the row-owner rule above).  Lists: [0, na) H_II,a, [na, 2 na) B_a, 2 na: H_SS.
+  SchurItems L;
+  auto classify = [&](int bi, int bj, int agent, int idx) -> int {
+    if (bi == 0 || bj == 0) return 0;
+    if (bi < 0 || bi >= N || bj >= N) return -1;
+    const bool pi = P.pub[bi], pj = P.pub[bj];
+    if (pi && pj) { if (bi <= bj) L.add(2 * na, bi, bj, agent, idx, P.pos[bi], P.pos[bj], CD_MIRROR); }
+    else if (!pi && !pj) {
+      if (P.robot_of[bi] != P.robot_of[bj]) return -1;
+      if (bi <= bj) L.add(P.robot_of[bi], bi, bj, agent, idx, P.pos[bi], P.pos[bj], CD_MIRROR);
+    } else if (!pi && pj) {
+      if (P.robot_of[bi] != P.robot_of[bj]) return -1;
+      L.add(na + P.robot_of[bi], bi, bj, agent, idx, P.pos[bi], P.pos[bj] - P.sep_off[P.robot_of[bi]], bi > bj ? (CD_FLIP | CD_TRANS) : 0);
+    }
+    return 0;
+  };
+  for (int k = 0; k < na; ++k) {
+    const Agent &a = *t->ag[k];
+    for (int j = 0; j < a.n; ++j)
+      for (int p = a.rowptr[j]; p < a.rowptr[j + 1]; ++p)
+        if (classify(P.offs[k] + a.col[p], P.offs[k] + j, k, p)) { set_err(std::string(what) + ": a stored block lies outside the team"); return DPGO_ERR; }
+    for (size_t e = 0; e < a.se_host.size(); ++e) {
+      const SharedEdgeDev &se = a.se_host[e];
+      if (se.src_agent_local < 0 || se.src_agent_local >= na ||
+          classify(P.offs[se.src_agent_local] + se.src_frame, P.offs[k] + se.lpose, k, ~(int)e)) {
+        set_err(std::string(what) + ": a stored block lies outside the team");
+        return DPGO_ERR;
+      }
+    }
+  }
+  L.finish(2 * na + 1);
+  // ---- the outputs asked for, by case.  Block numbers: [0, N) the diagonal blocks, N + k pair k.
+  std::vector<std::vector<SchurBlk>> keep_list(na), same_list(na);
+  std::vector<SchurBlk> pub_list;
+  std::vector<SchurCross> ip_list, cross_list;
+  for (int g = 1; g < N; ++g) {
+    if (P.pub[g]) pub_list.push_back({g, P.pos[g], P.pos[g], 1});
+    else keep_list[P.robot_of[g]].push_back({g, P.pos[g], P.pos[g], 0});
+  }
+  for (int k = 0; k < num_pairs; ++k) {
+    const int a = pairs[2 * k], b = pairs[2 * k + 1], blk = N + k;
+    if (a == 0 || b == 0) continue;  // zeros
+    const int ra = P.robot_of[a], rb = P.robot_of[b];
+    if (P.pub[a] && P.pub[b]) pub_list.push_back({blk, P.pos[a], P.pos[b], 0});
+    else if (!P.pub[a] && !P.pub[b]) {
+      if (ra == rb) { keep_list[ra].push_back({blk, P.pos[a], P.pos[b], 0}); same_list[ra].push_back({blk, P.pos[a], P.pos[b], 0}); }
+      else cross_list.push_back({blk, ra, P.pos[a], rb, P.pos[b], 0});
+    } else if (!P.pub[a]) ip_list.push_back({blk, ra, P.pos[a], -1, P.pos[b], 0});
+    else ip_list.push_back({blk, rb, P.pos[b], -1, P.pos[a], 1});
+  }
+  // ---- device storage
+  const int M = std::max(6 * P.max_int, nS);
+  const size_t MM = (size_t)M * M, L3 = (size_t)12 * N, nout = (size_t)36 * (N + num_pairs);
+  size_t w_max = 0;
+  for (int k = 0; k < na; ++k) w_max = std::max(w_max, (size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k]));
+  // scratch of the pairs between interiors of two robots: at most 64 MB at a time
+  const size_t cross_chunk = schur_cross_chunk(cross_list.size(), kmax);
+  SchurDev D;
+  DevBuf<double> d_S, d_small, d_t;
+  std::vector<DevBuf<double>> d_W(na);
+  DevBuf<int> d_int;
+  DevBuf<SchurCross> d_cross;
+  DevBuf<SchurRobot> d_rob;
+  const int gstride = (max_n + 255) / 256;
+  // d_small: T, E = T Q, Lambda, the Gershgorin scratch of k_cert_lambda, [logdet, min, max] per factor, the kept blocks of the
+  // C_a, the output blocks
+  const size_t small = 2 * L3 + (size_t)9 * N + (size_t)na * gstride + 4 * (size_t)(na + 1) + 2 * nout;
+  size_t nblk = pub_list.size();
+  for (int k = 0; k < na; ++k) nblk = std::max(nblk, keep_list[k].size() + same_list[k].size());
+  bool bad = D.A.alloc(MM) || D.Wk.alloc(MM) || D.M.alloc(MM) || d_S.alloc((size_t)nS * nS) || D.B.alloc(w_max) || d_small.alloc(small) ||
+             d_int.alloc((size_t)na + 1 + (size_t)N) || D.items.upload(L.items, t->stream) || D.src.upload(L.srcs, t->stream) ||
+             D.dst.upload(L.dsts, t->stream) || D.blk.alloc(nblk) || d_cross.alloc(std::max(ip_list.size(), cross_list.size())) ||
+             d_rob.alloc(na) || d_t.alloc(cross_chunk * 6 * std::max(kmax, 1));
+  for (int k = 0; k < na && !bad; ++k) bad = d_W[k].alloc((size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k])) != 0;
+  if (bad) {
+    std::string who;
+    set_err(std::string(what) + ": device allocation failed (the Schur path needs " +
+            std::to_string((long long)schur_bytes(t, P, P.nS, kmax, num_pairs, who)) + " bytes)");
+    return DPGO_ERR;
+  }
+  double *Td = d_small.p, *E = Td + L3, *lam = E + L3, *gmax = lam + (size_t)9 * N, *stat = gmax + (size_t)na * gstride,
+         *keepd = stat + 4 * (size_t)(na + 1), *outd = keepd + nout;
+  int *off = d_int.p, *ipose_d = off + na + 1;
+  hipStream_t s = t->stream;
+  D.s = s; D.agents = t->d_agents.p; D.Td = Td; D.lam = lam; D.L = &L;
+  SchurMarks marks;
+  std::vector<int> ipose_h;
+  std::vector<int> ipose_off(na + 1, 0);
+  for (int k = 0; k < na; ++k) {
+    ipose_h.insert(ipose_h.end(), P.interior[k].begin(), P.interior[k].end());
+    ipose_off[k + 1] = (int)ipose_h.size();
+  }
+  std::vector<SchurRobot> rob(na);
+  for (int k = 0; k < na; ++k)
+    rob[k] = {d_W[k].p, 6 * (int)P.interior[k].size(), 6 * (P.sep_off[k + 1] - P.sep_off[k]), 6 * P.sep_off[k], 0};
+  HIPC(hipMemcpyAsync(off, P.offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, s));
+  if (!ipose_h.empty()) HIPC(hipMemcpyAsync(ipose_d, ipose_h.data(), sizeof(int) * ipose_h.size(), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(d_rob.p, rob.data(), sizeof(SchurRobot) * na, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(Td, T, sizeof(double) * L3, hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(keepd, 0, sizeof(double) * 2 * nout, s));
+  MARK(-1);
+  launch_cert_apply3(s, t->d_agents.p, off, na, max_n, Td, E, nullptr);
+  launch_cert_lambda3(s, t->d_agents.p, off, na, max_n, Td, E, lam, gmax);
+  if (nS > 0) {
+    HIPC(hipMemsetAsync(d_S.p, 0, sizeof(double) * (size_t)nS * nS, s));
+    D.assemble(2 * na, d_S.p, nS);
+  }
+  HIPC(hipGetLastError());
+  MARK(0);
+  // ---- the robots, one after another: the three square buffers and B serve each in turn
+  for (int k = 0; k < na; ++k) {
+    const int ni = rob[k].ld;
+    if (ni == 0) continue;
+    const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_S.p + (size_t)rob[k].soff * nS + rob[k].soff, nS,
+                                   keep_list[k], keepd, stat + 4 * k);
+    if (f < 0) return DPGO_ERR;
+    if (f > 0) { fail[0] = k; fail[1] = P.interior[k][(f - 1) / 6]; fail[2] = f - 1; return 1; }
+  }
+  // ---- the separator
+  if (nS > 0) {
+    k_schur_mirror<<<(unsigned)(((size_t)nS * nS + 255) / 256), 256, 0, s>>>(d_S.p, nS);
+    HIPC(hipGetLastError());
+    const int f = dense_spd_inverse(s, d_S.p, D.Wk.p, D.M.p, nS);
+    HIPC(hipGetLastError());
+    if (f < 0) { set_err(std::string(what) + ": scratch allocation of the inverse failed"); return DPGO_ERR; }
+    if (f > 0) { fail[0] = -1; fail[1] = P.sep[(f - 1) / 6]; fail[2] = f - 1; return 1; }
+    if (launch_cov_logdet(s, d_S.p, nS, stat + 4 * na)) return DPGO_ERR;
+    MARK(3);
+    if (!pub_list.empty()) {
+      HIPC(hipMemcpyAsync(D.blk.p, pub_list.data(), sizeof(SchurBlk) * pub_list.size(), hipMemcpyHostToDevice, s));
+      k_schur_public<<<(unsigned)((36 * pub_list.size() + 255) / 256), 256, 0, s>>>(D.M.p, nS, D.blk.p, (int)pub_list.size(), outd);
+      HIPC(hipGetLastError());
+    }
+    MARK(4);
+  }
+  // ---- the interior blocks
+  for (int k = 0; k < na; ++k) {
+    if (rob[k].ld == 0) continue;
+    if (schur_robot_blocks(D, marks, t->ag[k]->id, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)rob[k].soff * nS + rob[k].soff, nS,
+                           ipose_d + ipose_off[k], same_list[k], keepd, outd))
+      return DPGO_ERR;
+  }
+  if (!ip_list.empty()) {
+    HIPC(hipMemcpyAsync(d_cross.p, ip_list.data(), sizeof(SchurCross) * ip_list.size(), hipMemcpyHostToDevice, s));
+    k_schur_pair_ip<<<(unsigned)((36 * ip_list.size() + 255) / 256), 256, 0, s>>>(d_rob.p, D.M.p, nS, d_cross.p, (int)ip_list.size(), outd);
+    HIPC(hipGetLastError());
+  }
+  if (schur_cross_pairs(s, d_rob.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
+  MARK(4);
+  std::vector<double> host(4 * (size_t)(na + 1) + 2 * nout);
+  HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  double ms[5];
+  schur_report(marks, ms);
+  // log det and pivots: the robots in order, the separator last
+  double logdet = 0.0, mn = INFINITY, mx = 0.0;
+  for (int k = 0; k <= na; ++k) {
+    if (k < na ? rob[k].ld == 0 : nS == 0) continue;
+    logdet += host[4 * k];
+    mn = std::fmin(mn, host[4 * k + 1]);
+    mx = std::fmax(mx, host[4 * k + 2]);
+  }
+  res->n = 6 * (N - 1);
+  res->logdet = logdet;
+  res->min_pivot = mn;
+  res->max_pivot = mx;
+  res->seconds_assemble = 1e-3 * ms[0];
+  res->seconds_invert = 1e-3 * (ms[1] + ms[2] + ms[3]);
+  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+  if (timing)
+    std::fprintf(stderr,
+                 "marginal_covariances (Schur): n %d, separator %d, largest interior %d, %zu blocks, assemble %.3f ms, factorisations %.3f ms, "
+                 "products %.3f ms, separator inverse %.3f ms, extract %.3f ms\n",
+                 6 * (N - 1), nS, 6 * P.max_int, L.items.size(), ms[0], ms[1], ms[2], ms[3], ms[4]);
+  const double *o = host.data() + 4 * (size_t)(na + 1) + nout;
+  std::memcpy(cov_diag, o, sizeof(double) * 36 * (size_t)N);
+  if (num_pairs > 0) std::memcpy(cov_pairs, o + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
+  return DPGO_OK;
+}
+
+// ---- the same call over a split team ("across teams"; the conventions of certify_across.hip)
+//
+// A participant holds some robots.  Poses are numbered globally, robots by id, then poses; pose 0 is robot 0's first pose.
+// Transport calls, the same on every participant: the two allgathers and the exchange of Across::begin and Cert::setup,
+// the exchange of the T halo, then
+//   A  sizes: per robot its public poses, its interior poses and the cross blocks it holds (the payload lengths follow);
+//   B  per robot: a failure record, the frames of its public poses, its diagonal block of the Schur complement
+//      H_SS[s_a, s_a] - B_a^T W_a, the statistics of its factor, and the blocks of H_SS below the diagonal in the rows it holds
+//      (the row-owner rule), padded to the longest;
+//   C  the pair blocks a participant owns (two interior poses of one of its robots; an interior pose of one of its robots
+//      with a public pose) and, for every pair of interior poses of two robots, the two rows W_a[i,:], W_b[j,:] from their
+//      holders;
+// and the closing status word.  Every participant builds the same S_c from B, inverts it itself (deterministic: no
+// broadcast) and forms the pairs of two robots itself from the rows of C.  No sum crosses a robot boundary except the
+// host's log det in robot order, so every block, log det and pivot is bitwise the single team's.
+namespace {
+
+double pair_hash(const int *pairs, int num_pairs) {
+  unsigned long long h = 1469598103934665603ull;
+  for (int k = 0; k < 2 * num_pairs; ++k)
+    for (int i = 0; i < 4; ++i) {
+      h ^= (unsigned long long)((unsigned)pairs[k] >> (8 * i)) & 0xffull;
+      h *= 1099511628211ull;
+    }
+  return (double)(h & ((1ull << 52) - 1));
+}
+
+// "" or why pose g of T (12 doubles each, R column-major first) is not in SE(3)
+std::string se3_defect(const double *T, int N) {
+  for (int g = 0; g < N; ++g) {
+    const double *R = T + (size_t)12 * g;
+    double orth = 0.0;
+    for (int p = 0; p < 3; ++p)
+      for (int q = 0; q < 3; ++q) {
+        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
+        orth = std::max(orth, std::fabs(d));
+      }
+    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
+    bool finite = true;
+    for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(R[k]);
+    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "pose %d of T (team order) is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", g, orth, det);
+      return buf;
+    }
+  }
+  return "";
+}
+
+enum { XF_OK = 0, XF_PIVOT = 1, XF_MEMORY = 2, XF_LOCAL = 3 };
+
+}  // namespace
+
+int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
+                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
+  const char *what = "marginal_covariances_across";
+  if (res) std::memset(res, 0, sizeof *res);
+  std::string argerr;
+  if (!T || !cov_diag || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))) argerr = "null argument";
+  else if (flags != DPGO_COV_SCHUR) argerr = "flags must be DPGO_COV_SCHUR";
+  else if (t) {
+    int n = 0;
+    for (auto &a : t->ag) n += a->n;
+    argerr = se3_defect(T, n);
+  }
+  Across x;
+  if (x.begin(t, tr, owner, what, 3, 3, flags, (double)num_pairs, argerr.empty() ? pair_hash(pairs, num_pairs) : 0.0, 0,
+              argerr.empty() ? nullptr : argerr.c_str()))
+    return DPGO_ERR;
+  // (from here on the participants agree on the owner table, the robots' sizes and the pair list)
+  const int nr = x.num_robots, na = (int)t->ag.size(), world = x.world;
+  const long long NG = x.nglob;
+  for (int k = 0; k < 2 * num_pairs; ++k)
+    if (pairs[k] < 0 || pairs[k] >= NG) {  // (the same on every participant: nobody goes on)
+      set_err(std::string(what) + ": pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " +
+              std::to_string(NG) + ")");
+      return DPGO_ERR;
+    }
+  SchurPartition P;
+  {
+    int z = -1;  // team pose of the fixed pose, robot 0's first, when robot 0 lives here
+    if (t->id2local.count(0)) {
+      z = 0;
+      for (int k = 0; k < t->id2local.at(0); ++k) z += t->ag[k]->n;
+    }
+    schur_partition(t, z, P);
+  }
+  const int N = P.N;
+  if (NG < 2) {
+    std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
+    if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
+    return x.finish() ? DPGO_ERR : DPGO_OK;
+  }
+  x.note(hipSetDevice(t->device), __LINE__);
+  hipStream_t s = t->stream;
+  // ---- Lambda of T from the across operator at K = 3; the T halo stays on the device
+  Cert c;
+  c.t = t;
+  c.x = &x;
+  c.setup(3);
+  CERT_CK(c, hipMemcpyAsync(c.T, T, sizeof(double) * 12 * (size_t)N, hipMemcpyHostToDevice, s));
+  c.apply(3, c.T, 3, c.T2, 3, false);
+  if (!c.halted()) launch_cert_lambda3(s, t->d_agents.p, c.off, na, c.max_n, c.T, c.T2, c.lam, c.gmax);
+  CERT_CK(c, hipGetLastError());
+  if (x.dead) return x.fail();
+
+  // ---- the work lists of this participant.  Lists: [0, na) H_II,a, [na, 2 na) B_a, [2 na, 3 na) the diagonal block of H_SS of
+  // robot a, 3 na: the blocks of H_SS between two robots in the rows this participant holds, one 6 x 6 slot each
+  std::vector<int> hoffs(na, 0);
+  int halo_slots = 0;
+  for (int k = 0; k < na; ++k) { hoffs[k] = halo_slots; halo_slots += (int)t->ag[k]->np.size(); }
+  struct CrossBlk { int lrobot, lrow, crobot, cframe; };  // row: local robot and index among its public poses; column: robot id, frame
+  std::vector<CrossBlk> xb;
+  std::vector<int> ncross(na, 0);
+  SchurItems L;
+  bool outside = false;
+  {
+    std::map<std::tuple<int, int, int>, int> slot_of;  // (team pose of the row, column robot, column frame) -> slot
+    for (int k = 0; k < na; ++k) {
+      const Agent &a = *t->ag[k];
+      const int so = P.sep_off[k];
+      for (int j = 0; j < a.n; ++j)
+        for (int p = a.rowptr[j]; p < a.rowptr[j + 1]; ++p) {
+          const int bi = P.offs[k] + a.col[p], bj = P.offs[k] + j;
+          if (a.col[p] < 0 || a.col[p] >= a.n) { outside = true; continue; }
+          if (a.id == 0 && (a.col[p] == 0 || j == 0)) continue;  // the fixed pose
+          const bool pi = P.pub[bi], pj = P.pub[bj];
+          if (pi && pj) { if (bi <= bj) L.add(2 * na + k, bi, bj, k, p, P.pos[bi] - so, P.pos[bj] - so, CD_MIRROR); }
+          else if (!pi && !pj) { if (bi <= bj) L.add(k, bi, bj, k, p, P.pos[bi], P.pos[bj], CD_MIRROR); }
+          else if (!pi && pj) L.add(na + k, bi, bj, k, p, P.pos[bi], P.pos[bj] - so, bi > bj ? (CD_FLIP | CD_TRANS) : 0);
+        }
+      for (size_t e = 0; e < a.se_host.size(); ++e) {
+        const SharedEdgeDev &se = a.se_host[e];
+        const int cr = se.src_robot, cf = se.src_frame;
+        if (cr < 0 || cr >= nr || cf < 0 || cf >= x.robot_n[cr] || se.lpose < 0 || se.lpose >= a.n) { outside = true; continue; }
+        if (cr >= a.id) continue;             // the row-owner rule: the block (row own pose, column the LOWER robot's pose)
+        if (cr == 0 && cf == 0) continue;     // the fixed pose
+        if (a.id == 0 && se.lpose == 0) continue;
+        const int bj = P.offs[k] + se.lpose;
+        // the column pose's row of T: its own when the neighbour lives here, else its halo slot behind this team's poses
+        const int bi = se.src_agent_local >= 0 ? P.offs[se.src_agent_local] + cf : N + hoffs[k] + se.slot;
+        const auto key = std::make_tuple(bj, cr, cf);
+        auto it = slot_of.find(key);
+        if (it == slot_of.end()) {
+          it = slot_of.emplace(key, (int)xb.size()).first;
+          xb.push_back({k, P.pos[bj] - so, cr, cf});
+          ++ncross[k];
+        }
+        L.add(3 * na, bi, bj, k, ~(int)e, 0, it->second, CD_TRANS);
+      }
+    }
+  }
+  L.finish(3 * na + 1);
+  if (outside) x.fail_local("a stored block lies outside the problem");
+
+  // ---- allgather A: the sizes
+  std::vector<double> ga(1 + 3 * (size_t)nr, 0.0), gall;
+  for (int k = 0; k < na; ++k) {
+    const int id = t->ag[k]->id;
+    ga[1 + 3 * id] = P.sep_off[k + 1] - P.sep_off[k];
+    ga[2 + 3 * id] = (double)P.interior[k].size();
+    ga[3 + 3 * id] = ncross[k];
+  }
+  if (x.gather(ga, gall)) return x.fail();
+  std::vector<int> gs(nr), gi(nr), gc(nr), gsoff(nr + 1, 0);
+  for (int i = 0; i < nr; ++i) {
+    const double *q = gall.data() + (size_t)x.robot_holder[i] * ga.size();
+    gs[i] = (int)q[1 + 3 * i]; gi[i] = (int)q[2 + 3 * i]; gc[i] = (int)q[3 + 3 * i];
+    gsoff[i + 1] = gsoff[i] + gs[i];
+  }
+  const int nSp = gsoff[nr], nS = 6 * nSp;
+  int kmax = 0;
+  for (int i = 0; i < nr; ++i) kmax = std::max(kmax, 6 * gs[i]);
+  auto robot_len = [&](int i) { return (size_t)gs[i] + 36 * (size_t)gs[i] * gs[i] + 4 + (size_t)gc[i] * 39; };
+  constexpr size_t HDR = 6;  // status, failure code, robot, pose, row, spare
+  std::vector<size_t> plen(world, HDR);
+  for (int i = 0; i < nr; ++i) plen[x.robot_holder[i]] += robot_len(i);
+  const size_t pmax = *std::max_element(plen.begin(), plen.end());
+  // the local robots in id order
+  std::vector<int> byid;
+  for (int i = 0; i < nr; ++i)
+    if (x.robot_holder[i] == x.rank) byid.push_back(t->id2local.at(i));
+
+  // ---- the pairs, by case, from what every participant knows so far; the remote poses' sets come with allgather B
+  std::vector<int> grobot((size_t)NG), gframe((size_t)NG);
+  for (int i = 0; i < nr; ++i)
+    for (int f = 0; f < x.robot_n[i]; ++f) { grobot[x.robot_goff[i] + f] = i; gframe[x.robot_goff[i] + f] = f; }
+  auto local_pose = [&](int g) { return P.offs[t->id2local.at(grobot[g])] + gframe[g]; };
+  auto here = [&](int g) { return x.robot_holder[grobot[g]] == x.rank; };
+  // pairs of two interior poses of one local robot must be known before the robot's step (its blocks of C_a are kept)
+  std::vector<std::vector<SchurBlk>> keep_list(na), same_list(na);
+  for (int k = 0; k < na; ++k)
+    for (int g : P.interior[k]) keep_list[k].push_back({g, P.pos[g], P.pos[g], 0});
+  for (int k = 0; k < num_pairs; ++k) {
+    const int a = pairs[2 * k], b = pairs[2 * k + 1];
+    if (a == 0 || b == 0 || grobot[a] != grobot[b] || !here(a)) continue;
+    const int la = local_pose(a), lb = local_pose(b);
+    if (P.pub[la] || P.pub[lb]) continue;
+    const int lk = t->id2local.at(grobot[a]);
+    keep_list[lk].push_back({N + k, P.pos[la], P.pos[lb], 0});
+    same_list[lk].push_back({N + k, P.pos[la], P.pos[lb], 0});
+  }
+
+  // ---- device storage (as the single team's, the separator that of the whole problem)
+  const int M = std::max(6 * P.max_int, nS);
+  const size_t MM = (size_t)M * M, nout = (size_t)36 * (N + num_pairs);
+  size_t w_max = 0, d_all = 0;
+  std::vector<size_t> doff(na + 1, 0);
+  for (int k = 0; k < na; ++k) {
+    const size_t sk = (size_t)(P.sep_off[k + 1] - P.sep_off[k]);
+    w_max = std::max(w_max, (size_t)36 * P.interior[k].size() * sk);
+    doff[k + 1] = doff[k] + 36 * sk * sk;
+  }
+  d_all = doff[na];
+  int fcode = XF_OK, frobot = 0, fpose = 0, frow = 0;
+  std::string fmsg;
+  if (!x.bad && schur_fits(t, P, nSp, kmax, num_pairs, what, fmsg)) { fcode = XF_MEMORY; }
+  SchurDev D;
+  DevBuf<double> d_S, d_small, d_t, d_T, d_D, d_X, d_rows;
+  std::vector<DevBuf<double>> d_W(na);
+  DevBuf<int> d_int;
+  DevBuf<SchurCross> d_cross;
+  DevBuf<SchurRobot> d_rob;
+  size_t ncrosspairs = 0;
+  for (int k = 0; k < num_pairs; ++k) ncrosspairs += (pairs[2 * k] && pairs[2 * k + 1] && grobot[pairs[2 * k]] != grobot[pairs[2 * k + 1]]);
+  const size_t cross_chunk = schur_cross_chunk(ncrosspairs, kmax);
+  const size_t small = 4 * (size_t)(na + 1) + 2 * nout;
+  size_t nblk = (size_t)N + num_pairs;
+  SchurMarks marks;
+  std::vector<int> ipose_h, ipose_off(na + 1, 0);
+  for (int k = 0; k < na; ++k) {
+    ipose_h.insert(ipose_h.end(), P.interior[k].begin(), P.interior[k].end());
+    ipose_off[k + 1] = (int)ipose_h.size();
+  }
+  double *stat = nullptr, *keepd = nullptr, *outd = nullptr;
+  std::vector<SchurRobot> rob(na);
+  std::vector<double> hD, hX, hstat;
+  // phase 1 on the device: this participant's robots.  DPGO_ERR: a local failure (message set)
+  auto phase1 = [&]() -> int {
+    bool bad = D.A.alloc(MM) || D.Wk.alloc(MM) || D.M.alloc(MM) || d_S.alloc((size_t)nS * nS) || D.B.alloc(w_max) || d_small.alloc(small) ||
+               d_int.alloc((size_t)N + 1) || D.items.upload(L.items, s) || D.src.upload(L.srcs, s) || D.dst.upload(L.dsts, s) ||
+               D.blk.alloc(nblk) || d_cross.alloc(std::max<size_t>(num_pairs, 1)) || d_rob.alloc((size_t)na + 2 * ncrosspairs) ||
+               d_t.alloc(cross_chunk * 6 * std::max(kmax, 1)) || d_T.alloc((size_t)12 * (N + halo_slots)) || d_D.alloc(d_all) ||
+               d_X.alloc(36 * xb.size());
+    for (int k = 0; k < na && !bad; ++k) bad = d_W[k].alloc((size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k])) != 0;
+    if (bad) { set_err("device allocation failed"); return DPGO_ERR; }
+    stat = d_small.p; keepd = stat + 4 * (size_t)(na + 1); outd = keepd + nout;
+    HIPC(hipMemcpyAsync(d_T.p, c.T, sizeof(double) * 12 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    if (halo_slots > 0) HIPC(hipMemcpyAsync(d_T.p + (size_t)12 * N, x.d_halo, sizeof(double) * 12 * (size_t)halo_slots, hipMemcpyDeviceToDevice, s));
+    D.s = s; D.agents = t->d_agents.p; D.Td = d_T.p; D.lam = c.lam; D.L = &L;
+    for (int k = 0; k < na; ++k)
+      rob[k] = {d_W[k].p, 6 * (int)P.interior[k].size(), 6 * (P.sep_off[k + 1] - P.sep_off[k]), 6 * gsoff[t->ag[k]->id], 0};
+    if (!ipose_h.empty()) HIPC(hipMemcpyAsync(d_int.p, ipose_h.data(), sizeof(int) * ipose_h.size(), hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(stat, 0, sizeof(double) * small, s));
+    if (d_all) HIPC(hipMemsetAsync(d_D.p, 0, sizeof(double) * d_all, s));
+    MARK(-1);
+    for (int k = 0; k < na; ++k) D.assemble(2 * na + k, d_D.p + doff[k], rob[k].K);
+    D.assemble(3 * na, d_X.p, 6);
+    HIPC(hipGetLastError());
+    MARK(0);
+    for (int k : byid) {
+      const int ni = rob[k].ld;
+      if (ni == 0) continue;
+      const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_D.p + doff[k], rob[k].K, keep_list[k], keepd,
+                                     stat + 4 * k);
+      if (f < 0) return DPGO_ERR;
+      if (f > 0) {
+        fcode = XF_PIVOT; frobot = t->ag[k]->id; frow = f - 1;
+        const int g = P.interior[k][(f - 1) / 6];
+        fpose = (int)(x.robot_goff[frobot] + (g - P.offs[k]));
+        return DPGO_OK;
+      }
+    }
+    hD.resize(d_all); hX.resize(36 * xb.size()); hstat.resize(4 * (size_t)(na + 1));
+    if (d_all) HIPC(hipMemcpyAsync(hD.data(), d_D.p, sizeof(double) * d_all, hipMemcpyDeviceToHost, s));
+    if (!xb.empty()) HIPC(hipMemcpyAsync(hX.data(), d_X.p, sizeof(double) * hX.size(), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(hstat.data(), stat, sizeof(double) * hstat.size(), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return DPGO_OK;
+  };
+  if (!x.bad && fcode == XF_OK && phase1()) { fcode = XF_LOCAL; fmsg = g_err; }
+
+  // ---- allgather B
+  std::vector<double> gb(pmax, 0.0);
+  gb[1] = fcode; gb[2] = frobot; gb[3] = fpose; gb[4] = frow;
+  if (fcode == XF_OK && !x.bad) {
+    size_t o = HDR;
+    for (int k : byid) {
+      const int id = t->ag[k]->id, sk = gs[id];
+      for (int q = 0; q < sk; ++q) gb[o++] = P.sep[P.sep_off[k] + q] - P.offs[k];
+      std::memcpy(gb.data() + o, hD.data() + doff[k], sizeof(double) * 36 * (size_t)sk * sk);
+      o += 36 * (size_t)sk * sk;
+      gb[o] = hstat[4 * k]; gb[o + 1] = hstat[4 * k + 1]; gb[o + 2] = hstat[4 * k + 2]; gb[o + 3] = rob[k].ld > 0 ? 1.0 : 0.0;
+      o += 4;
+      for (size_t b = 0; b < xb.size(); ++b) {
+        if (xb[b].lrobot != k) continue;
+        gb[o] = xb[b].lrow; gb[o + 1] = xb[b].crobot; gb[o + 2] = xb[b].cframe;
+        std::memcpy(gb.data() + o + 3, hX.data() + 36 * b, sizeof(double) * 36);
+        o += 39;
+      }
+    }
+  }
+  if (x.gather(gb, gall)) return x.fail();
+  // a failure of any participant, told by all in the same words
+  for (int q = 0; q < world; ++q) {
+    const double *h = gall.data() + (size_t)q * pmax;
+    if (h[1] == XF_OK) continue;
+    std::string m = std::string(what) + ": rank " + std::to_string(q) + ": ";
+    if (h[1] == XF_PIVOT)
+      m += "non-positive pivot at row " + std::to_string((long long)h[4]) + " of the interior Hessian of robot " + std::to_string((long long)h[2]) +
+           " (pose " + std::to_string((long long)h[3]) + "): the Hessian is not positive definite at this T: not a minimum";
+    else if (h[1] == XF_MEMORY) m += "the Schur path does not fit its device (its own error names the bytes)";
+    else m += "local failure (its own error names the cause)";
+    if (q == x.rank && !fmsg.empty() && h[1] != XF_PIVOT) m += " [" + fmsg + "]";
+    set_err(m);
+    return DPGO_ERR;
+  }
+  // ---- S_c of the whole problem, the same on every participant
+  std::vector<std::vector<int>> pubf(nr);
+  std::vector<double> rstat(4 * (size_t)nr, 0.0);
+  std::vector<double> hS((size_t)nS * nS, 0.0);
+  std::vector<size_t> rstart(nr, 0);
+  for (int q = 0; q < world; ++q) {
+    size_t o = (size_t)q * pmax + HDR;
+    for (int i = 0; i < nr; ++i) {
+      if (x.robot_holder[i] != q) continue;
+      rstart[i] = o;
+      pubf[i].resize(gs[i]);
+      for (int k = 0; k < gs[i]; ++k) pubf[i][k] = (int)gall[o + k];
+      o += robot_len(i);
+    }
+  }
+  auto sep_index = [&](int robot, int frame) -> int {
+    const auto &v = pubf[robot];
+    const auto it = std::lower_bound(v.begin(), v.end(), frame);
+    return (it != v.end() && *it == frame) ? gsoff[robot] + (int)(it - v.begin()) : -1;
+  };
+  bool torn = false;
+  for (int i = 0; i < nr; ++i) {
+    size_t o = rstart[i] + gs[i];
+    const size_t w = 6 * (size_t)gs[i], so = 6 * (size_t)gsoff[i];
+    for (size_t cc = 0; cc < w; ++cc) std::memcpy(hS.data() + (so + cc) * nS + so, gall.data() + o + cc * w, sizeof(double) * w);
+    o += w * w;
+    for (int k = 0; k < 4; ++k) rstat[4 * i + k] = gall[o + k];
+    o += 4;
+    for (int b = 0; b < gc[i]; ++b, o += 39) {
+      const int row = gsoff[i] + (int)gall[o], col = sep_index((int)gall[o + 1], (int)gall[o + 2]);
+      if (col < 0) { torn = true; continue; }
+      const double *blk = gall.data() + o + 3;  // 6 x 6 column-major: H[row pose, column pose]
+      for (int bb = 0; bb < 6; ++bb)
+        for (int aa = 0; aa < 6; ++aa) {
+          hS[((size_t)6 * col + bb) * nS + (size_t)6 * row + aa] = blk[6 * bb + aa];
+          hS[((size_t)6 * row + aa) * nS + (size_t)6 * col + bb] = blk[6 * bb + aa];
+        }
+    }
+  }
+  if (torn) {  // (the same on every participant)
+    set_err(std::string(what) + ": a shared edge names a pose its robot does not list as public (the measurement sets differ)");
+    return DPGO_ERR;
+  }
+  // every pose of the problem: its set and its index there
+  std::vector<char> gpub((size_t)NG, 0);
+  std::vector<int> gpos((size_t)NG, 0);
+  for (int i = 0; i < nr; ++i) {
+    for (int k = 0; k < gs[i]; ++k) { gpub[x.robot_goff[i] + pubf[i][k]] = 1; gpos[x.robot_goff[i] + pubf[i][k]] = gsoff[i] + k; }
+    int cnt = 0;
+    for (int f = (i == 0 ? 1 : 0); f < x.robot_n[i]; ++f)
+      if (!gpub[x.robot_goff[i] + f]) gpos[x.robot_goff[i] + f] = cnt++;
+  }
+  // ---- the pair lists.  Owner of a pair: the holder of the (left) interior pose's robot; pairs of two public poses and
+  // of two robots' interiors are formed by everyone
+  std::vector<SchurBlk> pub_list;
+  std::vector<SchurCross> ip_list, cross_list;
+  std::vector<int> pair_owner(num_pairs, -1);  // -1: everyone (or zeros)
+  struct RowReq { int pair, robot, li; };
+  std::vector<RowReq> rows;  // two per pair of two robots, in pair order
+  for (int k = 0; k < na; ++k)
+    for (int q = P.sep_off[k]; q < P.sep_off[k + 1]; ++q) {
+      const int gsx = gsoff[t->ag[k]->id] + (q - P.sep_off[k]);
+      pub_list.push_back({P.sep[q], gsx, gsx, 1});
+    }
+  for (int k = 0; k < num_pairs; ++k) {
+    const int a = pairs[2 * k], b = pairs[2 * k + 1], blk = N + k;
+    if (a == 0 || b == 0) continue;
+    const int ra = grobot[a], rb = grobot[b];
+    if (gpub[a] && gpub[b]) pub_list.push_back({blk, gpos[a], gpos[b], 0});
+    else if (!gpub[a] && !gpub[b]) {
+      if (ra == rb) pair_owner[k] = x.robot_holder[ra];
+      else { rows.push_back({k, ra, gpos[a]}); rows.push_back({k, rb, gpos[b]}); }
+    } else if (!gpub[a]) {
+      pair_owner[k] = x.robot_holder[ra];
+      if (pair_owner[k] == x.rank) ip_list.push_back({blk, t->id2local.at(ra), gpos[a], -1, gpos[b], 0});
+    } else {
+      pair_owner[k] = x.robot_holder[rb];
+      if (pair_owner[k] == x.rank) ip_list.push_back({blk, t->id2local.at(rb), gpos[b], -1, gpos[a], 1});
+    }
+  }
+  std::vector<size_t> clen(world, 1), rowoff(rows.size(), 0);
+  for (int k = 0; k < num_pairs; ++k)
+    if (pair_owner[k] >= 0) clen[pair_owner[k]] += 36;
+  for (size_t r = 0; r < rows.size(); ++r) {
+    const int q = x.robot_holder[rows[r].robot];
+    rowoff[r] = clen[q];
+    clen[q] += 36 * (size_t)gs[rows[r].robot];
+  }
+  const size_t cmax = *std::max_element(clen.begin(), clen.end());
+  std::vector<double> hout, hrows;
+  std::vector<double> sstat(4, 0.0);
+  int sfail = 0;
+  // phase 2 on the device: the separator's inverse and this participant's blocks
+  auto phase2 = [&]() -> int {
+    if (nS > 0) {
+      HIPC(hipMemcpyAsync(d_S.p, hS.data(), sizeof(double) * hS.size(), hipMemcpyHostToDevice, s));
+      k_schur_mirror<<<(unsigned)(((size_t)nS * nS + 255) / 256), 256, 0, s>>>(d_S.p, nS);
+      HIPC(hipGetLastError());
+      const int f = dense_spd_inverse(s, d_S.p, D.Wk.p, D.M.p, nS);
+      HIPC(hipGetLastError());
+      if (f < 0) { set_err("scratch allocation of the inverse failed"); return DPGO_ERR; }
+      if (f > 0) { sfail = f; return DPGO_OK; }
+      if (launch_cov_logdet(s, d_S.p, nS, stat + 4 * na)) return DPGO_ERR;
+      MARK(3);
+      if (!pub_list.empty()) {
+        HIPC(hipMemcpyAsync(D.blk.p, pub_list.data(), sizeof(SchurBlk) * pub_list.size(), hipMemcpyHostToDevice, s));
+        k_schur_public<<<(unsigned)((36 * pub_list.size() + 255) / 256), 256, 0, s>>>(D.M.p, nS, D.blk.p, (int)pub_list.size(), outd);
+        HIPC(hipGetLastError());
+      }
+      MARK(4);
+    }
+    HIPC(hipMemcpyAsync(d_rob.p, rob.data(), sizeof(SchurRobot) * na, hipMemcpyHostToDevice, s));
+    for (int k : byid) {
+      if (rob[k].ld == 0) continue;
+      if (schur_robot_blocks(D, marks, t->ag[k]->id, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)rob[k].soff * nS + rob[k].soff, nS,
+                             d_int.p + ipose_off[k], same_list[k], keepd, outd))
+        return DPGO_ERR;
+    }
+    if (!ip_list.empty()) {
+      HIPC(hipMemcpyAsync(d_cross.p, ip_list.data(), sizeof(SchurCross) * ip_list.size(), hipMemcpyHostToDevice, s));
+      k_schur_pair_ip<<<(unsigned)((36 * ip_list.size() + 255) / 256), 256, 0, s>>>(d_rob.p, D.M.p, nS, d_cross.p, (int)ip_list.size(), outd);
+      HIPC(hipGetLastError());
+    }
+    hout.resize(nout);
+    HIPC(hipMemcpyAsync(hout.data(), outd, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
+    if (nS > 0) HIPC(hipMemcpyAsync(sstat.data(), stat + 4 * na, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+    // the rows W_a[i,:] this participant holds, 6 x 6 s_a column-major each
+    hrows.assign(cmax, 0.0);
+    for (size_t r = 0; r < rows.size(); ++r) {
+      if (x.robot_holder[rows[r].robot] != x.rank) continue;
+      const int lk = t->id2local.at(rows[r].robot);
+      if (rob[lk].K > 0)
+        HIPC(hipMemcpy2DAsync(hrows.data() + rowoff[r], 48, d_W[lk].p + (size_t)6 * rows[r].li, sizeof(double) * rob[lk].ld, 48, rob[lk].K,
+                              hipMemcpyDeviceToHost, s));
+    }
+    HIPC(hipStreamSynchronize(s));
+    return DPGO_OK;
+  };
+  if (!x.bad && phase2()) x.fail_local(g_err);
+  // ---- allgather C: the owned pair blocks and the rows
+  std::vector<double> gcv(cmax, 0.0);
+  if (!x.bad && sfail == 0) {
+    size_t o = 1;
+    for (int k = 0; k < num_pairs; ++k)
+      if (pair_owner[k] == x.rank) { std::memcpy(gcv.data() + o, hout.data() + 36 * (size_t)(N + k), sizeof(double) * 36); o += 36; }
+    for (size_t r = 0; r < rows.size(); ++r)
+      if (x.robot_holder[rows[r].robot] == x.rank)
+        std::memcpy(gcv.data() + rowoff[r], hrows.data() + rowoff[r], sizeof(double) * 36 * (size_t)gs[rows[r].robot]);
+  }
+  if (x.gather(gcv, gall)) return x.fail();
+  if (sfail > 0) {  // (deterministic: the same on every participant, and behind the allgather that would have told of a failure)
+    const int sp = (sfail - 1) / 6;
+    int robot = 0;
+    while (robot + 1 < nr && gsoff[robot + 1] <= sp) ++robot;
+    const long long pose = x.robot_goff[robot] + pubf[robot][sp - gsoff[robot]];
+    set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(sfail - 1) + " of the Schur complement on the public poses (pose " +
+            std::to_string(pose) + "): the Hessian is not positive definite at this T: not a minimum");
+    return DPGO_ERR;
+  }
+  {
+    std::vector<size_t> o(world, 1);
+    for (int k = 0; k < num_pairs; ++k)
+      if (pair_owner[k] >= 0) {
+        const int q = pair_owner[k];
+        std::memcpy(hout.data() + 36 * (size_t)(N + k), gall.data() + (size_t)q * cmax + o[q], sizeof(double) * 36);
+        o[q] += 36;
+      }
+  }
+  // the pairs of two robots' interiors, from the gathered rows: each row a robot of its own in the table
+  auto phase3 = [&]() -> int {
+    if (rows.empty()) return DPGO_OK;
+    size_t total = 0;
+    std::vector<size_t> ro(rows.size());
+    for (size_t r = 0; r < rows.size(); ++r) { ro[r] = total; total += 36 * (size_t)gs[rows[r].robot]; }
+    if (d_rows.alloc(total)) { set_err("device allocation failed"); return DPGO_ERR; }
+    std::vector<double> hr(total);
+    std::vector<SchurRobot> prob(rows.size());
+    for (size_t r = 0; r < rows.size(); ++r) {
+      const int q = x.robot_holder[rows[r].robot];
+      std::memcpy(hr.data() + ro[r], gall.data() + (size_t)q * cmax + rowoff[r], sizeof(double) * 36 * (size_t)gs[rows[r].robot]);
+      prob[r] = {d_rows.p + ro[r], 6, 6 * gs[rows[r].robot], 6 * gsoff[rows[r].robot], 0};
+    }
+    for (size_t r = 0; r + 1 < rows.size(); r += 2) cross_list.push_back({N + rows[r].pair, na + (int)r, 0, na + (int)r + 1, 0, 0});
+    HIPC(hipMemcpyAsync(d_rows.p, hr.data(), sizeof(double) * total, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(d_rob.p + na, prob.data(), sizeof(SchurRobot) * prob.size(), hipMemcpyHostToDevice, s));
+    if (schur_cross_pairs(s, d_rob.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
+    std::vector<double> hc(36 * (size_t)num_pairs);
+    HIPC(hipMemcpyAsync(hc.data(), outd + 36 * (size_t)N, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (const SchurCross &e : cross_list) std::memcpy(hout.data() + 36 * (size_t)e.blk, hc.data() + 36 * (size_t)(e.blk - N), sizeof(double) * 36);
+    return DPGO_OK;
+  };
+  if (!x.bad && phase3()) x.fail_local(g_err);
+  if (x.finish()) return DPGO_ERR;
+  // ---- the results: log det and pivots in robot order, the separator last
+  double logdet = 0.0, mn = INFINITY, mx = 0.0;
+  for (int i = 0; i < nr; ++i) {
+    if (rstat[4 * i + 3] == 0.0) continue;
+    logdet += rstat[4 * i];
+    mn = std::fmin(mn, rstat[4 * i + 1]);
+    mx = std::fmax(mx, rstat[4 * i + 2]);
+  }
+  if (nS > 0) { logdet += sstat[0]; mn = std::fmin(mn, sstat[1]); mx = std::fmax(mx, sstat[2]); }
+  double ms[5];
+  schur_report(marks, ms);
+  res->n = (int)(6 * (NG - 1));
+  res->logdet = logdet;
+  res->min_pivot = mn;
+  res->max_pivot = mx;
+  res->seconds_assemble = 1e-3 * ms[0];
+  res->seconds_invert = 1e-3 * (ms[1] + ms[2] + ms[3]);
+  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+  if (timing)
+    std::fprintf(stderr,
+                 "marginal_covariances_across: rank %d of %d, n %lld, separator %d, largest interior here %d, assemble %.3f ms, factorisations "
+                 "%.3f ms, products %.3f ms, separator inverse %.3f ms, extract %.3f ms, %lld allgathers, %lld exchanges\n",
+                 x.rank, world, 6 * (NG - 1), nS, 6 * P.max_int, ms[0], ms[1], ms[2], ms[3], ms[4], x.n_allgather, x.n_exchange);
+  std::memcpy(cov_diag, hout.data(), sizeof(double) * 36 * (size_t)N);
+  if (num_pairs > 0) std::memcpy(cov_pairs, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
+  return DPGO_OK;
+}
+#undef MARK
+
+
+}  // namespace dpgo_cert

@@ -604,11 +604,14 @@ class TorchTransport(_Transport):
 
 
 def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8, max_iters=1000, block=0,
-                      refine_translations=True, certify_kw=None):
+                      refine_translations=True, certify_kw=None, covariances=False, pairs=None):
     """The certificate and the SE-Sync rounding of an iterate split across ranks (one team per rank), with global results on
     every rank that owns a robot: dict(T = the rounded poses of all robots in global order (robots by id), certificate,
     rounding, f_relaxed, f_rounded, gap_rel as in capi.solve_certified).  Every rank of the world calls (ranks that own no
-    robot are left out through a sub-group, whose creation is collective) and gets None back when it owns none."""
+    robot are left out through a sub-group, whose creation is collective) and gets None back when it owns none.
+    covariances=True adds covariances=(Covariance, diag[N, 6, 6] of all poses in global order[, cross[len(pairs), 6, 6]]):
+    Team.covariances of the split team at T (pairs: global pose indices, the same list on every rank), the diagonal blocks
+    gathered the way T is."""
     owners = sorted(set(int(o) for o in owner_of_robot))
     group = None
     if dist.get_world_size() != len(owners):
@@ -639,4 +642,21 @@ def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8,
             o += 12 * n
     Tg = np.concatenate([blocks[i] for i in sorted(blocks)])
     gap = (rd.f_rounded - rd.f_relaxed) / rd.f_relaxed if cert.certified == 1 else None
-    return dict(T=Tg, certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed, f_rounded=rd.f_rounded, gap_rel=gap)
+    out = dict(T=Tg, certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed, f_rounded=rd.f_rounded, gap_rel=gap)
+    if covariances:
+        cres, diag, cross = team.covariances(T, pairs, transport=tr, owner_of_robot=own)
+        # (T holds 12 doubles per pose, a diagonal block 36: the same record, three times as long at most)
+        mine = np.zeros(3 * L)
+        mine[:head.size], mine[head.size:head.size + diag.size] = head, diag.reshape(-1)
+        alld = tr.allgather(mine).reshape(tr.world, mine.size)
+        dblocks = {}
+        for q in range(tr.world):
+            k = int(alld[q, 0])
+            rid, rn = alld[q, 1:1 + k].astype(int), alld[q, 1 + k:1 + 2 * k].astype(int)
+            o = 1 + 2 * k
+            for i, n in zip(rid, rn):
+                dblocks[int(i)] = alld[q, o:o + 36 * n]
+                o += 36 * n
+        dg = np.concatenate([dblocks[i] for i in sorted(dblocks)]).reshape(-1, 6, 6)
+        out["covariances"] = (cres, dg) if pairs is None else (cres, dg, cross)
+    return out

@@ -319,21 +319,30 @@ int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, i
  * cost 1/2 <T, T Q> (current weights) in these 6N coordinates; pose 0 (the anchor of dpgo_team_round) is held fixed:
  * H_red = H without its first 6 rows and columns, Sigma = H_red^-1 (the Laplace approximation of the posterior under the
  * cost's own noise model).  H is assembled on the device from S = Q - Lambda(T) (the certificate's operator at rank 3) and
- * inverted there by the blocked fp64 Cholesky of the dense preconditioner: three square matrices of 6(N-1) doubles a side. */
+ * inverted there by the blocked fp64 Cholesky of the dense preconditioner: three square matrices of 6(N-1) doubles a side.
+ * DPGO_COV_SCHUR (csrc/covariance_schur.hip) computes the same blocks by robot-wise Schur complement: a pose that no shared
+ * edge names (edges of weight 0 included) is interior to its robot; the interiors are eliminated one robot at a time and only
+ * the Schur complement on the public poses is inverted as a whole.  Exact and deterministic; the device holds three square
+ * matrices of order M = max(6 x the largest interior, 6 x the public poses), the separator, and per robot a matrix of
+ * 6 |I_a| x 6 s_a doubles (s_a: the robot's public poses) -- bytes = 8 (3 M^2 + (6 |S|)^2 + sum_a 36 |I_a| s_a + max_a 36 |I_a| s_a)
+ * for these large buffers, plus the small ones (outputs, 72 doubles per requested block; lists; scratch: DESIGN.md 5e has every term). */
+#define DPGO_COV_SCHUR 1
 typedef struct {
   int n;                 /* 6 (N - 1): the order of H_red */
-  double logdet;         /* log det H_red = 2 sum_k log L_kk, summed in index order */
-  double min_pivot;      /* smallest and largest L_kk^2 of the Cholesky factor */
+  double logdet;         /* log det H_red = 2 sum_k log L_kk, summed in index order (DPGO_COV_SCHUR: per factor, the factors
+                          * summed on the host in robot order, the separator last) */
+  double min_pivot;      /* smallest and largest L_kk^2 of the Cholesky factor (DPGO_COV_SCHUR: over all factors) */
   double max_pivot;
-  double seconds_assemble; /* device time (events on the team's stream): Lambda, clearing and filling H_red */
-  double seconds_invert;   /* ... Cholesky, triangular inverse, W^T W */
+  double seconds_assemble; /* device time (events on the team's stream): Lambda, clearing and filling H_red (every assembly) */
+  double seconds_invert;   /* ... Cholesky, triangular inverse, W^T W (DPGO_COV_SCHUR: every factorisation and product) */
 } dpgo_covariance_t;
 /* cov_diag: the N diagonal 6 x 6 blocks of Sigma, 36 doubles each, row-major, bitwise symmetric (pose 0: zeros);
  * cov_pairs (may be NULL when num_pairs is 0): the blocks Sigma_ab for pairs[2k] = a, pairs[2k + 1] = b (a pair that names
- * pose 0: zeros).  flags: 0.  All robots local and INITIALIZED.  Refused with DPGO_ERR and a message before any device work:
+ * pose 0: zeros).  flags: 0 (the dense inverse) or DPGO_COV_SCHUR; any other bit is refused.  All robots local and INITIALIZED.  Refused with DPGO_ERR and a message before any device work:
  * T outside SE(3) (|R^T R - I| or |det R - 1| above 1e-8), a pair index outside [0, N), positive-weight edges that do not
- * join every pose to pose 0, 3 x n^2 x 8 bytes above the free device memory.  Refused after the factorisation: a
- * non-positive pivot (T is not a minimum).  A refused call leaves cov_diag / cov_pairs untouched and *res all zero.
+ * join every pose to pose 0, 3 x n^2 x 8 bytes (DPGO_COV_SCHUR: the bytes above; the message names what sets them) above the
+ * free device memory.  Refused after the factorisation: a non-positive pivot (T is not a minimum; DPGO_COV_SCHUR names the
+ * robot whose interior block, or the separator, and the pose).  A refused call leaves cov_diag / cov_pairs untouched and *res all zero.
  * Changes no solver state; two calls give the same bits. */
 int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
                                    double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
@@ -368,6 +377,22 @@ int dpgo_team_certify_across(dpgo_team_t *t, const dpgo_transport_t *tr, const i
  * keeps its own poses' translations */
 int dpgo_team_round_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, int flags, double *T,
                            dpgo_rounding_t *out);
+/* dpgo_team_marginal_covariances over a split team (csrc/covariance_schur.hip): the Schur path is its only
+ * method, flags = DPGO_COV_SCHUR.  T and cov_diag: this team's poses in team order.  pairs: poses of the whole problem
+ * (robots by id, then poses; pose 0, the fixed one, is robot 0's first pose), the same list on every participant; cov_pairs is
+ * complete on every participant.  The agreement record of the calls above also carries num_pairs and a hash of the pair list; a
+ * participant whose arguments are invalid (a T outside SE(3), flags) makes every participant refuse.  Then three allgathers:
+ * the robots' sizes; per robot its public frames, its diagonal block of the Schur complement, the statistics of its factor and
+ * the blocks of H_SS below the diagonal in the rows it holds, together with a failure record (a non-positive pivot with robot,
+ * pose and row; a device that is too small); the pair blocks a participant owns and the rows W_a[i,:] of pairs between two
+ * robots' interiors.  Every participant inverts the same Schur complement itself.  Every participant returns DPGO_ERR with a
+ * message that names the failing rank, and a refused call leaves cov_diag / cov_pairs untouched everywhere.  Every block, log
+ * det and pivot equals the single team's DPGO_COV_SCHUR call bit for bit, whatever the split, and the scalars of *res are
+ * identical on every participant (seconds_*: this participant's).  The connectivity of the weighted graph is NOT checked
+ * here (no participant sees all edges): a graph cut in two ends in a non-positive pivot. */
+int dpgo_team_marginal_covariances_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
+                                          const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
+                                          double *cov_pairs, dpgo_covariance_t *res);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
