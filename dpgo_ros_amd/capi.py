@@ -99,6 +99,7 @@ OK, NOT_READY, ERR = 0, 1, -1
 CERT_NO_DEFLATION, CERT_NO_PRECONDITIONER, CERT_ETA_RELATIVE = 1, 2, 4
 ROUND_REFINE_TRANSLATIONS = 1
 COV_SCHUR = 1  # DPGO_COV_SCHUR
+COV_NESTED_DEFAULT_BLOCK = 256  # DPGO_COV_NESTED_DEFAULT_BLOCK
 PRECOND_AUTO, PRECOND_DENSE, PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL = 0, 1, 2, 3
 
 # every symbol include/dpgo_hip.h declares (checked by tests/test_abi.py)
@@ -125,7 +126,8 @@ dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_
 dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
 dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
-dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across""".split()
+dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
+dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested""".split()
 
 
 class DpgoError(RuntimeError):
@@ -173,6 +175,28 @@ def two_level_plan(rowptr, col, max_sub=0):
     _chk(lib().dpgo_two_level_plan(n, _d(rowptr), _d(col), int(max_sub), _d(sub_of), _d(info)), "two_level_plan")
     return sub_of, dict(subdomains=int(info[0]), separator_poses=int(info[1]), workgroups=int(info[2]),
                         producer_workgroups=int(info[3]), bytes_per_apply=info[4], worthwhile=bool(info[5]))
+
+
+def _nested_plan_info(info):
+    return dict(blocks=int(info[0]), separator_poses=int(info[1]), promoted_poses=int(info[2]), largest_block=int(info[3]),
+                largest_coupling=int(info[4]), coupling_total=int(info[5]))
+
+
+def covariance_nested_plan(robot_of, rowptr, col, max_block=None):
+    """the sets of Team.covariances(method="nested") for a global block-CSR pattern in team order (host arithmetic only):
+    (block_of[n] with the block index, -1 = separator pose, -2 = pose 0; info dict).  robot_of[n]: the robot of every pose,
+    non-decreasing from 0; a pose joined to a pose of another robot is public.  max_block None: the library's default"""
+    robot_of = np.ascontiguousarray(robot_of, dtype=np.int32)
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    n = len(rowptr) - 1
+    if len(robot_of) != n:
+        raise ValueError("covariance_nested_plan: robot_of holds %d entries, the pattern has %d rows" % (len(robot_of), n))
+    block_of = np.zeros(n, dtype=np.int32)
+    info = np.zeros(6, dtype=np.int32)
+    _chk(lib().dpgo_covariance_nested_plan(n, _d(robot_of), _d(rowptr), _d(col), int(max_block or 0), _d(block_of), _d(info)),
+         "covariance_nested_plan")
+    return block_of, _nested_plan_info(info)
 
 
 # ---- transports of the calls across teams (dpgo_transport_t; DESIGN.md 5d) ----
@@ -968,6 +992,14 @@ class Team:
                  "round_across")
         return res, T
 
+    def covariance_plan(self, max_block=None):
+        """the sets of covariances(method="nested") for this team: (block_of[N] in team order with the block index, -1 = separator
+        pose, -2 = pose 0; info dict as capi.covariance_nested_plan).  max_block None: the library's default"""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        block_of, info = np.zeros(N, dtype=np.int32), np.zeros(6, dtype=np.int32)
+        _chk(lib().dpgo_team_covariance_nested_plan(self.h, int(max_block or 0), _d(block_of), _d(info)), "covariance_nested_plan")
+        return block_of, _nested_plan_info(info)
+
     def covariances(self, T=None, pairs=None, method=None, transport=None, owner_of_robot=None):
         """Marginal pose covariances at the trajectory T (12 doubles per pose in team order; None: the rounding of the
         current iterate, self.round()): (Covariance, diag[N, 6, 6], cross[len(pairs), 6, 6]).  Pose i is perturbed by
@@ -976,14 +1008,20 @@ class Team:
         weights; cross[k] is the block of the pose pair pairs[k] = (a, b).  method: "dense" (the default of one team) inverts
         the whole reduced Hessian, "schur" eliminates the poses without shared edges robot by robot and inverts only the Schur
         complement on the public poses -- the same blocks to round-off, in a fraction of the memory and time when the robots
-        share few poses.  Raises DpgoError when T is not in SE(3), the weighted graph is disconnected, the matrices do not fit
+        share few poses.  "nested" (one team only; covariances_nested takes its block size) goes one step further: a robot
+        whose interior holds more poses than the block size has it dissected into blocks, and the dissection's separator poses
+        join the public ones -- what a single robot, or a few robots with large interiors, need.  Raises DpgoError when T is not in SE(3), the weighted graph is disconnected, the matrices do not fit
         the device, or T is not a minimum (a non-positive pivot).  Changes no solver state.
         With a transport (a team split across participants, owner_of_robot as for certify / round): the Schur path is the
         only method ("dense" raises ValueError; the default means "schur").  T and diag are this team's poses in team order,
         pairs name poses of the whole problem (robots by id, then poses; pose 0 is robot 0's first pose), the same list on
         every participant, and cross is complete on every participant; the scalars are identical everywhere."""
-        if method not in (None, "dense", "schur"):
-            raise ValueError("covariances: method must be \"dense\" or \"schur\", not %r" % (method,))
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("covariances: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        if method == "nested" and transport is not None:
+            raise ValueError("covariances: method=\"nested\" has no call across teams (it was given a transport)")
+        if method == "nested":
+            return self.covariances_nested(T, pairs)
         if transport is not None and method == "dense":
             raise ValueError("covariances: a team split across participants has no dense path (method=\"dense\" with a "
                              "transport)")
@@ -1007,6 +1045,23 @@ class Team:
                                                              _d(pr) if len(pr) else None, _d(diag),
                                                              _d(cross) if len(pr) else None, C.byref(res)),
                  "marginal_covariances_across")
+        return res, diag, cross
+
+    def covariances_nested(self, T=None, pairs=None, max_block=None):
+        """covariances(method="nested") with its parameter: max_block, the largest block in poses that a robot's interior is
+        left whole at or dissected into (None: the library's default, COV_NESTED_DEFAULT_BLOCK).  The same return value,
+        conventions and errors as covariances; when no robot's interior exceeds max_block the call is method="schur", bit for bit."""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("covariances: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        res, diag, cross = Covariance(), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
+        _chk(lib().dpgo_team_marginal_covariances_nested(self.h, _d(T), int(max_block or 0), len(pr), _d(pr) if len(pr) else None,
+                                                         _d(diag), _d(cross) if len(pr) else None, C.byref(res)),
+             "marginal_covariances_nested")
         return res, diag, cross
 
 
@@ -1106,17 +1161,21 @@ def _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, 
 
 
 def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None,
-                    refine_translations=True, certify_kw=None, device=0, covariances=False, covariance_method="dense"):
+                    refine_translations=True, certify_kw=None, device=0, covariances=False, covariance_method="dense",
+                    covariance_max_block=None):
     """End to end: the Riemannian staircase, then the SE-Sync rounding of its final point (Team.round on the final team).
     Returns dict(T=trajectory, 12 doubles per pose in team order anchored at the first pose, r=final rank, ranks,
     certificate, rounding=Rounding, f_relaxed, f_rounded, gap_rel, escape_costs).  gap_rel = (f_rounded - f_relaxed) /
     f_relaxed bounds the relative suboptimality of T (up to the certificate's eta) when the point is certified; it is None
     otherwise.  covariances=True adds covariances=(Covariance, diag[N, 6, 6]): Team.covariances of the final team at T by
-    covariance_method ("dense" or "schur")."""
+    covariance_method ("dense", "schur", or "nested" with covariance_max_block)."""
     def round_final(team, out):
         out["rounding"], out["T"] = team.round(refine_translations=refine_translations)
         if covariances:
-            out["covariances"] = team.covariances(out["T"], method=covariance_method)[:2]
+            if covariance_method == "nested":
+                out["covariances"] = team.covariances_nested(out["T"], max_block=covariance_max_block)[:2]
+            else:
+                out["covariances"] = team.covariances(out["T"], method=covariance_method)[:2]
 
     out = _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, None, 30, certify_kw, device,
                      on_final=round_final)

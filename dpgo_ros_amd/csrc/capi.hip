@@ -1669,16 +1669,17 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
 
 }  // extern "C"
 
-// ---- marginal pose covariances (covariance.hip): every refusal that can be decided on the host comes first
-extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
-                                              double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
-  const char *what = "marginal_covariances";
+// ---- marginal pose covariances (covariance.hip): every refusal that can be decided on the host comes first.
+// The three methods share them: DPGO_OK to go on (the device is selected), 1 when the team holds the anchor alone and the outputs
+// are already written, DPGO_ERR with a message that `what` prefixes.  flags_error: what is wrong with the caller's flags (or null)
+int dpgo_cert::covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs,
+                                      double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses) {
   if (res) std::memset(res, 0, sizeof *res);
   if (!t || !T || !cov_diag || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))) {
     set_err(std::string(what) + ": null argument");
     return DPGO_ERR;
   }
-  if (flags != 0 && flags != DPGO_COV_SCHUR) { set_err(std::string(what) + ": flags must be 0 or DPGO_COV_SCHUR"); return DPGO_ERR; }
+  if (flags_error) { set_err(std::string(what) + ": " + flags_error); return DPGO_ERR; }
   if (dpgo_cert::check_team_local(t, what)) return DPGO_ERR;
   const int na = (int)t->ag.size();
   std::vector<int> offs(na + 1, 0);
@@ -1714,12 +1715,23 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
     if (dpgo_cert::team_measurements(t, offs, what, mm)) return DPGO_ERR;
     if (check_joined_to_pose0(mm.data(), (int)mm.size(), N, what)) return DPGO_ERR;
   }
+  *num_poses = N;
   if (N < 2) {  // the anchor alone: nothing is free
     std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
     if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
-    return DPGO_OK;
+    return 1;
   }
   HIPC(hipSetDevice(t->device));
+  return DPGO_OK;
+}
+
+extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
+                                              double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
+  const char *what = "marginal_covariances";
+  int N = 0;
+  const int pre = dpgo_cert::covariance_host_checks(t, T, flags != 0 && flags != DPGO_COV_SCHUR ? "flags must be 0 or DPGO_COV_SCHUR" : nullptr,
+                                                    num_pairs, pairs, cov_diag, cov_pairs, res, what, &N);
+  if (pre != DPGO_OK) return pre > 0 ? DPGO_OK : pre;
   if (flags == DPGO_COV_SCHUR) {
     // by robot-wise Schur complement (covariance_schur.hip): its own memory accounting, from the partition
     int fail[3] = {0, 0, 0};

@@ -155,6 +155,10 @@ int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flag
 // DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian was not positive
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
                       dpgo_covariance_t *res);
+// the refusals of the marginal covariances that are decided on the host, shared by its methods (capi.hip): DPGO_OK, 1 (the
+// anchor alone: outputs written), or DPGO_ERR
+int covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs, double *cov_diag,
+                           double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses);
 // k_cov_logdet on a Cholesky factor left in A: out[0 .. 2] = 2 sum log L_kk, min L_kk^2, max L_kk^2
 int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out);
 // the same call by robot-wise Schur complement (covariance_schur.hip; flags = DPGO_COV_SCHUR): DPGO_OK, DPGO_ERR with a message,

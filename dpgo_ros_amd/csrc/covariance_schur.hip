@@ -29,18 +29,9 @@
 #include <map>
 #include <tuple>
 
-#include "certify_internal.h"
-#include "covariance_block.h"
+#include "covariance_schur.h"
 
 namespace dpgo {
-
-// where an item's block goes: block (r, c) of the launch's column-major target (leading dimension ld).  Hc = H_lo,hi is
-// formed with bi as lo, or bj when CD_FLIP is set; the target receives Hc, or its transpose with CD_TRANS; with CD_MIRROR
-// the other one goes to block (c, r) as well (symmetric targets list every pair of poses once)
-struct CovDst {
-  int r, c, f, pad_;
-};
-constexpr int CD_FLIP = 1, CD_TRANS = 2, CD_MIRROR = 4;
 
 // k_cov_assemble's work item, written where the host's list says instead of at the global position.  The same per-block
 // arithmetic (cov_form_block), the same merged parallel edges, one writer per block.  bi, bj: rows of T (and of lam)
@@ -62,82 +53,11 @@ __global__ __launch_bounds__(256) void k_cov_assemble_map(const AgentDev *__rest
   if ((di.z & CD_MIRROR) && di.x != di.y) cov_store_block(H + r * ld + c, (size_t)ld, Hc, !tr);
 }
 
-// ---- C = op(A) B (sub: C -= op(A) B), column-major, op(A) m x k (TA: A is k x m and transposed), B k x n, any m, n, k >= 1
-// and leading dimensions.  One workgroup of 256 threads = 4 waves per 64 x 64 tile of C; a K slab of 32 is staged in LDS
-// (zero padded past the edges), the next slab's loads are in flight under the products.  v_mfma_f64_16x16x4_f64: operands
-// A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], result D[row = (lane >> 4) + 4 reg][col = lane & 15]
-// (the f64 map, not the f32 one).  As in dense_inverse.hip the instruction's ROW index carries the matrix COLUMN j and its
-// column index the matrix row i, so the 16 lanes that share a result register store 16 consecutive rows of one column.
-// Wave w owns the quadrant rows 32 (w & 1), columns 32 (w >> 1) as 2 x 2 blocks of 16 x 16.  An element's sum runs over k in
-// index order whatever tile it lies in.
-constexpr int GK = 32;
-typedef double v4f64_t __attribute__((ext_vector_type(4)));
-
+// C = op(A) B (sub: C -= op(A) B): one workgroup per 64 x 64 tile (dgemm_tile, covariance_schur.h)
 template <bool TA>
 __global__ __launch_bounds__(256) void k_dgemm(const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb,
                                                double *__restrict__ C, int ldc, int m, int n, int k, int sub) {
-  __shared__ double As[GK][65], Bs[GK][65];
-  const int tid = threadIdx.x, i0 = 64 * blockIdx.x, j0 = 64 * blockIdx.y;
-  double ra[8], rb[8];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int t = tid + 256 * q;
-      const int kb = t & 31, jb = t >> 5;  // B: consecutive threads run down a column of B
-      const double vb = gp(B)[(size_t)min(j0 + jb, n - 1) * ldb + min(k0 + kb, k - 1)];
-      rb[q] = (k0 + kb < k && j0 + jb < n) ? vb : 0.0;
-      if (TA) {
-        const double va = gp(A)[(size_t)min(i0 + jb, m - 1) * lda + min(k0 + kb, k - 1)];
-        ra[q] = (k0 + kb < k && i0 + jb < m) ? va : 0.0;
-      } else {
-        const int ia = t & 63, ka = t >> 6;
-        const double va = gp(A)[(size_t)min(k0 + ka, k - 1) * lda + min(i0 + ia, m - 1)];
-        ra[q] = (k0 + ka < k && i0 + ia < m) ? va : 0.0;
-      }
-    }
-  };
-  v4f64_t acc[2][2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < 2; ++v) acc[u][v] = v4f64_t{0.0, 0.0, 0.0, 0.0};
-  const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  const int ib = 32 * (wave & 1), jbase = 32 * (wave >> 1);
-  load(0);
-  for (int k0 = 0; k0 < k; k0 += GK) {
-    __syncthreads();  // (the products of the slab before this one have read LDS)
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int t = tid + 256 * q;
-      Bs[t & 31][t >> 5] = rb[q];
-      if (TA) As[t & 31][t >> 5] = ra[q];
-      else As[t >> 6][t & 63] = ra[q];
-    }
-    __syncthreads();
-    if (k0 + GK < k) load(k0 + GK);
-#pragma unroll
-    for (int kk = 0; kk < GK; kk += 4) {
-      double a[2], b[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) { a[u] = Bs[kk + lk][jbase + 16 * u + li]; b[u] = As[kk + lk][ib + 16 * u + li]; }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[v], b[u], acc[u][v], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = i0 + ib + 16 * u + li, j = j0 + jbase + 16 * v + lk + 4 * q;
-        if (i < m && j < n) {
-          double *c = C + (size_t)j * ldc + i;
-          gp(c)[0] = sub ? gp(c)[0] - acc[u][v][q] : acc[u][v][q];
-        }
-      }
+  dgemm_tile<TA>(A, lda, B, ldb, C, ldc, m, n, k, sub, 64 * blockIdx.x, 64 * blockIdx.y);
 }
 
 // the upper triangle of the n x n column-major A from its lower one (the Schur complement B^T W is symmetric to round-off
@@ -147,15 +67,6 @@ __global__ __launch_bounds__(256) void k_schur_mirror(double *__restrict__ A, in
   if (e >= (size_t)n * n) return;
   const int i = (int)(e % n), j = (int)(e / n);
   if (i > j) gp(A)[(size_t)i * n + j] = gp(A)[e];
-}
-
-// sum_k Z[rz, k] W[rw, k], k in index order, one fused multiply-add per term: EVERY row product of the extraction goes
-// through here, so a diagonal block and the pair (i, i) agree bitwise
-__device__ __forceinline__ double schur_row_dot(const double *__restrict__ Z, size_t ldz, int rz, const double *__restrict__ W,
-                                                size_t ldw, int rw, int K) {
-  double s = 0.0;
-  for (int k = 0; k < K; ++k) s = __builtin_fma(gp(Z)[(size_t)k * ldz + rz], gp(W)[(size_t)k * ldw + rw], s);
-  return s;
 }
 
 // a list entry of the extraction kernels: output block blk, two indices inside the launch's sets, one flag
@@ -290,16 +201,16 @@ static void launch_dgemm(hipStream_t s, bool ta, const double *A, int lda, const
   else hipLaunchKernelGGL(k_dgemm<false>, grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, m, n, k, sub ? 1 : 0);
 }
 
-// who is public, who is interior among a team's poses; the fixed pose (team index `zero`, -1: not in this
-// team) belongs to neither set
-struct SchurPartition {
-  int na = 0, N = 0, nS = 0, max_int = 0;
-  std::vector<int> offs, robot_of, pos, sep, sep_off;  // pos: index inside the pose's own set; sep: team pose of separator index
-  std::vector<char> pub;
-  std::vector<std::vector<int>> interior;              // team poses of robot a's interior, in order
-};
+void launch_cov_assemble_map(hipStream_t s, const AgentDev *agents, const CovItem *items, const CovSrc *src, const CovDst *dst, int count,
+                             const double *T, const double *lam, double *H, int ld) {
+  if (count > 0) k_cov_assemble_map<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(agents, items, src, dst, count, T, lam, H, ld);
+}
 
-static void schur_partition(dpgo_team_t *t, int zero, SchurPartition &P) {
+void launch_schur_mirror(hipStream_t s, double *A, int n) {
+  if (n > 0) k_schur_mirror<<<(unsigned)(((size_t)n * n + 255) / 256), 256, 0, s>>>(A, n);
+}
+
+void schur_partition(dpgo_team_t *t, int zero, SchurPartition &P) {
   P.na = (int)t->ag.size();
   P.offs.assign(P.na + 1, 0);
   for (int k = 0; k < P.na; ++k) P.offs[k + 1] = P.offs[k] + t->ag[k]->n;
@@ -379,57 +290,6 @@ static int schur_fits(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax,
   msg = buf;
   return -1;
 }
-
-// the work lists of the assembly: raw stored blocks, sorted by (list, block column, block row) and merged where they name
-// the same pose pair (parallel edges, in record order)
-struct SchurItems {
-  struct Raw { int bi, bj, agent, idx, list; CovDst d; };
-  std::vector<Raw> raw;
-  std::vector<CovItem> items;
-  std::vector<CovSrc> srcs;
-  std::vector<CovDst> dsts;
-  std::vector<int> lbeg;
-  void add(int list, int bi, int bj, int agent, int idx, int r, int c, int f) { raw.push_back({bi, bj, agent, idx, list, {r, c, f, 0}}); }
-  void finish(int nlists) {
-    std::stable_sort(raw.begin(), raw.end(), [](const Raw &x, const Raw &y) {
-      return x.list != y.list ? x.list < y.list : x.bj != y.bj ? x.bj < y.bj : x.bi < y.bi;
-    });
-    lbeg.assign(nlists + 1, 0);
-    int cur = -1;
-    for (const Raw &q : raw) {
-      if (q.list == cur && items.back().bi == q.bi && items.back().bj == q.bj) ++items.back().count;
-      else {
-        while (cur < q.list) lbeg[++cur] = (int)items.size();
-        items.push_back({q.bi, q.bj, (int)srcs.size(), 1});
-        dsts.push_back(q.d);
-      }
-      srcs.push_back({q.agent, q.idx});
-    }
-    while (cur < nlists) lbeg[++cur] = (int)items.size();
-  }
-  int count(int list) const { return lbeg[list + 1] - lbeg[list]; }
-};
-
-// events: a mark per phase boundary; phase of the interval that ENDS at a mark: 0 assembly, 1 interior factorisations,
-// 2 products, 3 separator inverse, 4 extraction, -1 not counted
-struct SchurMarks {
-  std::vector<hipEvent_t> ev;
-  std::vector<int> phase;
-  std::vector<std::string> note;  // products: the shapes, for the DPGO_TIMING report
-  std::vector<double> flops;
-  ~SchurMarks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-  int mark(int ph, hipStream_t s) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) { set_err("marginal_covariances: event failed"); return DPGO_ERR; }
-    ev.push_back(e);
-    phase.push_back(ph);
-    note.emplace_back();
-    flops.push_back(0.0);
-    if (hipEventRecord(e, s) != hipSuccess) { set_err("marginal_covariances: event failed"); return DPGO_ERR; }
-    return 0;
-  }
-};
-#define MARK(ph) do { if (marks.mark(ph, s)) return DPGO_ERR; } while (0)
 
 // the device side of one call: what a single team and a participant of a split team share
 struct SchurDev {

@@ -474,7 +474,7 @@ __global__ __launch_bounds__(256) void k_wtw(const InvJob *jobs) {
 }
 
 int dense_spd_inverse_batched(hipStream_t stream, int count, double *const *A, double *const *work, double *const *M,
-                              const int *N, bool work_is_zero) {
+                              const int *N, bool work_is_zero, int *fail_index) {
   if (count <= 0) return 0;
   std::vector<InvJob> jobs(count);
   size_t linv_total = 0;
@@ -531,7 +531,11 @@ int dense_spd_inverse_batched(hipStream_t stream, int count, double *const *A, d
   std::vector<int> fail(count, 0);
   (void)hipMemcpyAsync(fail.data(), fail_d, sizeof(int) * count, hipMemcpyDeviceToHost, stream);
   (void)hipStreamSynchronize(stream);  // (the scratch goes back to the pool behind this: nothing queued still reads it)
-  for (int b = 0; b < count; ++b) if (fail[b]) return fail[b] + (b << 24);
+  for (int b = 0; b < count; ++b)
+    if (fail[b]) {
+      if (fail_index) { *fail_index = b; return fail[b]; }  // (a batch of more than 128 matrices: the index does not fit the code)
+      return fail[b] + (b << 24);
+    }
   return 0;
 }
 

@@ -196,9 +196,11 @@ int rtr_fused_tl_fit_pairs(int r);
 // A is destroyed; work must hold N*N doubles.  Returns 0, or the (1-based) failing pivot block.
 int dense_spd_inverse(hipStream_t stream, double *A, double *work, double *M, int N);
 // the same for `count` matrices at once (one per agent): every step's kernels serve the whole batch (blockIdx.z).
-// Returns 0, or failing pivot + (batch index << 24).
+// Returns 0, or failing pivot + (batch index << 24): a code that holds a batch index below 128.  With fail_index given it
+// returns the (1-based) failing pivot alone and stores the batch index of the first matrix that failed there, whatever
+// the size of the batch.
 int dense_spd_inverse_batched(hipStream_t stream, int count, double *const *A, double *const *work, double *const *M,
-                              const int *N, bool work_is_zero = false);
+                              const int *N, bool work_is_zero = false, int *fail_index = nullptr);
 
 // A X^T = B^T for RR right-hand sides from the Cholesky factor only (A destroyed; the solution overwrites B [N][RR];
 // Y [N][RR] is scratch).  Returns 0, or the (1-based) failing pivot.

@@ -346,6 +346,46 @@ typedef struct {
  * Changes no solver state; two calls give the same bits. */
 int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
                                    double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
+/* ---- the same covariances by nested dissection inside each robot (csrc/covariance_nested.hip; DESIGN.md 5e, "nested") ----
+ * DPGO_COV_SCHUR takes its sets from the team alone: one robot has no separator at all, a few robots with large interiors pay
+ * a dense inverse of order 6 |I_a| each.  Here a robot whose interior holds more than max_block poses has the pattern of its
+ * block-CSR, restricted to the interior, dissected by the plan of the two-level preconditioner (dpgo_two_level_plan with
+ * max_sub = max_block): the subdomains become BLOCKS of at most max_block + max_block / 5 poses, the dissection's separator
+ * poses are PROMOTED into the robot's part of the separator S (public and promoted poses in team order).  A robot whose
+ * interior fits is one block.  Blocks are ordered by robot, then by first pose; N_b = the separator poses coupled to block b,
+ * ascending.  C_b = H_bb^-1, W_b = C_b H[b, N_b] (the coupled columns alone), S_c = H_SS - sum_b H[b, N_b]^T W_b (block after
+ * block, no atomics), Sigma_SS = S_c^-1; the blocks of Sigma follow as for DPGO_COV_SCHUR with N_b in the place of a robot's
+ * public poses, log det sums the blocks in order and the separator last.  Exact and deterministic (two calls: the same bits);
+ * when no robot is split the call IS the DPGO_COV_SCHUR call (it delegates: the same bits and messages).
+ * Device bytes, with n_b = 6 |I_b|, K_b = 6 |N_b|, s = 6 |S|:
+ *   large = 8 (3 s^2  +  sum_b n_b K_b  +  max_b (3 n_b^2 + n_b K_b + K_b^2))
+ *           (S_c, the inverse's work matrix and Sigma_SS; every kept W_b; the workspace of the largest block -- H_bb, work, C_b,
+ *            B_b, B_b^T W_b.  Blocks are eliminated a batch at a time, batches filled in block order while their workspaces fit
+ *            what is left of the free memory, 2 GiB at the most; the request that is checked counts the largest block alone)
+ *   small = 8 (33 N + A ceil(max_a n_a / 256) + 4 (blocks + 1) + 72 (N + P)) + 48 max(K_max, 1) c + 24 (2 N + 3 P) + 40 Q
+ *           + 232 blocks + 4 (N + sum_b |N_b| + A + 1) + 8192 (ceil(s / 32) + sum_b ceil(n_b / 32))
+ *           (N poses, A robots, P pairs, Q stored blocks and shared-edge records, c = min(P, 65535, 2^23 / (6 max(K_max, 1)))
+ *            pairs across blocks per launch; 232 bytes of tables per block: one record of 56, three products of 48, two assembly
+ *            targets of 16).
+ * A request above the free device memory plus the idle pooled buffers is refused before any device work; the message gives
+ * both figures, says whether the separator or the batch workspace sets them, and that another max_block changes them. */
+#define DPGO_COV_NESTED_DEFAULT_BLOCK 256
+/* Host arithmetic only, no device: the sets for a global block-CSR pattern in team order (robot_of non-decreasing from 0
+ * without gaps; a pose joined to a pose of another robot is public; pose 0 is fixed).  block_of[num_poses]: the block index,
+ * -1 a separator pose, -2 pose 0.  info[6]: blocks, separator poses, promoted poses among them, the largest block (poses),
+ * the largest |N_b|, sum_b |N_b|.  max_block <= 0: DPGO_COV_NESTED_DEFAULT_BLOCK.  Either output may be NULL. */
+int dpgo_covariance_nested_plan(int num_poses, const int *robot_of, const int *rowptr, const int *col, int max_block,
+                                int *block_of, int *info);
+/* the same plan from the team's own structure (public: a pose that a shared-edge record names, edges of weight 0 included).
+ * block_of: one entry per pose of the team in team order.  All robots local and INITIALIZED. */
+int dpgo_team_covariance_nested_plan(dpgo_team_t *t, int max_block, int *block_of, int *info);
+/* dpgo_team_marginal_covariances by that plan: the same arguments, outputs and conventions, max_block in the place of flags.
+ * The refusals of DPGO_COV_SCHUR carry over (robots missing or not initialised, T outside SE(3), a pair outside [0, N), a
+ * weighted graph that is not joined to pose 0, the bytes above); a non-positive pivot names the robot, the block and the pose,
+ * or the separator.  A refused call leaves cov_diag / cov_pairs untouched and *res all zero.  Changes no solver state.  There
+ * is no call across teams. */
+int dpgo_team_marginal_covariances_nested(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs,
+                                          double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
 /* ---- certificate and rounding across teams (csrc/certify_across.hip) ----
  * A participant is one team that holds a subset of the robots; owner_rank_of_robot[num_robots] says which participant holds
  * each (the meaning of dpgo_team_attach_comm).  The library does not own the transport: it calls the two functions below,
