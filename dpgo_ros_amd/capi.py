@@ -100,6 +100,7 @@ CERT_NO_DEFLATION, CERT_NO_PRECONDITIONER, CERT_ETA_RELATIVE = 1, 2, 4
 ROUND_REFINE_TRANSLATIONS = 1
 COV_SCHUR = 1  # DPGO_COV_SCHUR
 COV_NESTED_DEFAULT_BLOCK = 256  # DPGO_COV_NESTED_DEFAULT_BLOCK
+GATE_DENSE, GATE_SCHUR, GATE_NESTED = 0, 1, 2  # DPGO_GATE_*
 PRECOND_AUTO, PRECOND_DENSE, PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL = 0, 1, 2, 3
 
 # every symbol include/dpgo_hip.h declares (checked by tests/test_abi.py)
@@ -127,7 +128,8 @@ dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
 dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
-dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested""".split()
+dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
+dpgo_team_gate_candidates""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1063,6 +1065,64 @@ class Team:
                                                          _d(diag), _d(cross) if len(pr) else None, C.byref(res)),
              "marginal_covariances_nested")
         return res, diag, cross
+
+    def _gate_call(self, what, cand, T, method, max_block, want_innovation, want_sigma):
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("%s: method must be \"dense\", \"schur\" or \"nested\", not %r" % (what, method))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("%s: T holds %d doubles, the team's %d poses need %d" % (what, T.size, N, 12 * N))
+        cand = np.ascontiguousarray(cand, dtype=MEAS_DTYPE).reshape(-1)
+        K = len(cand)
+        res = Covariance()
+        xi, d2 = (np.zeros((K, 6)), np.zeros(K)) if want_innovation else (None, None)
+        sg = np.zeros((K, 6, 6)) if want_sigma else None
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        _chk(lib().dpgo_team_gate_candidates(self.h, _d(T), code, int(max_block or 0), K, _d(cand),
+                                             _d(xi) if want_innovation and K else None, _d(d2) if want_innovation and K else None,
+                                             _d(sg) if want_sigma and K else None, C.byref(res)), "gate_candidates")
+        return res, xi, d2, sg
+
+    def gate(self, candidates, T=None, method=None, max_block=None, quantile=0.99, sigma_rel=False):
+        """Candidate measurements tested against the estimate's own uncertainty.  candidates: MEAS_DTYPE
+        records (r1, p1) -> (r2, p2) with R (row-major), t, kappa, tau, T_j ~ T_i (R, t); weight and the flags are ignored: a
+        candidate is a fresh measurement that is not in the graph.  T and method as in covariances (T None: the rounding of
+        the current iterate; method None: "dense"); max_block: method="nested" only.  Returns (Covariance, xi[K, 6], d2[K],
+        accept[K]) and, with sigma_rel=True, sigma_rel[K, 6, 6] behind them.  xi = (Log(R~^T R_ij), t_ij - t~) is the
+        innovation, rotation first; sigma_rel the covariance of the relative pose (R_ij, t_ij) = T_i^-1 T_j under the
+        perturbation R_ij <- R_ij Exp(phi), t_ij <- t_ij + delta (delta in frame i); d2 = xi^T (sigma_rel + Sigma_meas)^-1 xi
+        with Sigma_meas = diag(I / (2 kappa), I / tau), the cost's own noise model; accept = sqrt(d2) <=
+        error_threshold_at_quantile(quantile, 6).  The covariance blocks never leave the device: one kernel behind the
+        covariance path forms the outputs.  Raises DpgoError as covariances does, and for a candidate that names a robot or pose
+        outside the team, joins a pose to itself, has kappa <= 0 or tau <= 0, or an R outside SO(3).  Changes no solver state."""
+        res, xi, d2, sg = self._gate_call("gate", candidates, T, method, max_block, True, bool(sigma_rel))
+        accept = np.sqrt(d2) <= error_threshold_at_quantile(quantile, 6)
+        return (res, xi, d2, accept, sg) if sigma_rel else (res, xi, d2, accept)
+
+    def relative_covariances(self, pairs, T=None, method=None, max_block=None):
+        """sigma_rel[K, 6, 6] of gate for the pose pairs[k] = (i, j), team-order pose indices with i != j: the covariance of
+        the relative pose T_i^-1 T_j.  No measurement is involved; the same bits as gate(..., sigma_rel=True) gives."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        offs = np.cumsum([0] + [self.agents[i].n for i in self.ids])
+        N = int(offs[-1])
+        if len(pr) and (pr.min() < 0 or pr.max() >= N):
+            raise ValueError("relative_covariances: a pair names a pose outside [0, %d)" % N)
+        cand = np.zeros(len(pr), dtype=MEAS_DTYPE)
+        ids = np.asarray(self.ids, dtype=np.int64)
+        for e, (r, p) in enumerate((("r1", "p1"), ("r2", "p2"))):
+            k = np.searchsorted(offs, pr[:, e], side="right") - 1
+            cand[r], cand[p] = ids[k], pr[:, e] - offs[k]
+        return self._gate_call("relative_covariances", cand, T, method, max_block, False, True)[3]
+
+    def zero_weight_measurements(self):
+        """the team's measurements whose current weight is 0 (what GNC-TLS has rejected, or set_measurement_weight), in the
+        form gate accepts; each shared edge once, as the lower robot's copy (the rule of round's translation refinement)"""
+        out = [e for i in self.ids for e in self.agents[i].measurements()
+               if e["weight"] == 0.0 and (e["r1"] == e["r2"] or min(int(e["r1"]), int(e["r2"])) == i)]
+        return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
 
 
 def covariance_to_body_frame(cov, T):

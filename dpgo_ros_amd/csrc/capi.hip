@@ -1673,9 +1673,11 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
 // The three methods share them: DPGO_OK to go on (the device is selected), 1 when the team holds the anchor alone and the outputs
 // are already written, DPGO_ERR with a message that `what` prefixes.  flags_error: what is wrong with the caller's flags (or null)
 int dpgo_cert::covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs,
-                                      double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses) {
+                                      double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses,
+                                      bool staged) {
   if (res) std::memset(res, 0, sizeof *res);
-  if (!t || !T || !cov_diag || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))) {
+  // staged: the blocks stay on the device for an epilogue (certify_internal.h) and the two outputs are not used
+  if (!t || !T || (!staged && !cov_diag) || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || (!staged && !cov_pairs)))) {
     set_err(std::string(what) + ": null argument");
     return DPGO_ERR;
   }
@@ -1717,8 +1719,10 @@ int dpgo_cert::covariance_host_checks(dpgo_team_t *t, const double *T, const cha
   }
   *num_poses = N;
   if (N < 2) {  // the anchor alone: nothing is free
-    std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
-    if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
+    if (!staged) {
+      std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
+      if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
+    }
     return 1;
   }
   HIPC(hipSetDevice(t->device));
@@ -1727,15 +1731,20 @@ int dpgo_cert::covariance_host_checks(dpgo_team_t *t, const double *T, const cha
 
 extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
                                               double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
+  return dpgo_cert::marginal_covariances_call(t, T, flags, num_pairs, pairs, cov_diag, cov_pairs, res, nullptr);
+}
+
+int dpgo_cert::marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
+                                         double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi) {
   const char *what = "marginal_covariances";
   int N = 0;
   const int pre = dpgo_cert::covariance_host_checks(t, T, flags != 0 && flags != DPGO_COV_SCHUR ? "flags must be 0 or DPGO_COV_SCHUR" : nullptr,
-                                                    num_pairs, pairs, cov_diag, cov_pairs, res, what, &N);
+                                                    num_pairs, pairs, cov_diag, cov_pairs, res, what, &N, epi != nullptr);
   if (pre != DPGO_OK) return pre > 0 ? DPGO_OK : pre;
   if (flags == DPGO_COV_SCHUR) {
     // by robot-wise Schur complement (covariance_schur.hip): its own memory accounting, from the partition
     int fail[3] = {0, 0, 0};
-    const int rc = dpgo_cert::covariance_schur_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail);
+    const int rc = dpgo_cert::covariance_schur_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail, epi);
     if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
     if (rc > 0) {
       const std::string where = fail[0] < 0 ? "the Schur complement on the public poses"
@@ -1763,7 +1772,7 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
       return DPGO_ERR;
     }
   }
-  const int rc = dpgo_cert::covariance_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res);
+  const int rc = dpgo_cert::covariance_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, epi);
   if (rc > 0) {
     std::memset(res, 0, sizeof *res);
     const int row = rc - 1;

@@ -151,21 +151,43 @@ int team_measurements(dpgo_team_t *t, const std::vector<int> &offs, const char *
 int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flags, dpgo_certificate_t *out, double *v);
 
 
+// What a covariance path has staged on the device when its last extraction kernel is queued: T (the iterate layout, 12 per
+// pose), the N diagonal blocks and behind them the num_pairs pair blocks (36 doubles each, row-major), all ordered on
+// `stream`.  The buffers belong to the path and live until the epilogue has returned AND the path has drained the stream.
+struct CovStage {
+  const double *Td, *diag, *pairs;
+  int N, num_pairs;
+  hipStream_t stream;
+};
+// A step behind the staged blocks (gate.hip).  A path that is given one calls run() in the place of its copy of the blocks
+// to the host (cov_diag / cov_pairs are then not touched and may be null), and drains the stream afterwards: run() queues
+// its kernels and its own copies on stage.stream and does not synchronise.  DPGO_OK, or DPGO_ERR with a message.
+struct CovEpilogue {
+  virtual int run(const CovStage &stage) = 0;
+  virtual ~CovEpilogue() = default;
+};
+
 // the device part of dpgo_team_marginal_covariances (covariance.hip; the host-side refusals are in capi.hip): DPGO_OK,
 // DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian was not positive
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
-                      dpgo_covariance_t *res);
+                      dpgo_covariance_t *res, CovEpilogue *epi = nullptr);
+// dpgo_team_marginal_covariances / _nested with an epilogue in the place of the copy of the blocks (capi.hip,
+// covariance_nested.hip): the public calls are these with epi = nullptr; with one, cov_diag and cov_pairs may be null
+int marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
+                              double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi);
+int marginal_covariances_nested_call(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs, double *cov_diag,
+                                     double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi);
 // the refusals of the marginal covariances that are decided on the host, shared by its methods (capi.hip): DPGO_OK, 1 (the
 // anchor alone: outputs written), or DPGO_ERR
 int covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs, double *cov_diag,
-                           double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses);
+                           double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses, bool staged = false);
 // k_cov_logdet on a Cholesky factor left in A: out[0 .. 2] = 2 sum log L_kk, min L_kk^2, max L_kk^2
 int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out);
 // the same call by robot-wise Schur complement (covariance_schur.hip; flags = DPGO_COV_SCHUR): DPGO_OK, DPGO_ERR with a message,
 // or 1 when a pivot was not positive -- fail[0] the local index of the robot whose interior block failed (-1: the separator),
 // fail[1] the team pose of the pivot, fail[2] its row in that factor
 int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
-                            dpgo_covariance_t *res, int *fail);
+                            dpgo_covariance_t *res, int *fail, CovEpilogue *epi = nullptr);
 // the same over a split team (dpgo_team_marginal_covariances_across; covariance_schur.hip)
 int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
                             const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);

@@ -99,7 +99,7 @@ int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out) {
 // T on the device, Lambda, H_red, its inverse, the requested blocks.  The outputs are written only when the factorisation
 // succeeded.  Returns DPGO_OK, DPGO_ERR (message set), or k + 1 > 0: the pivot of row k of H_red was not positive.
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
-                      dpgo_covariance_t *res) {
+                      dpgo_covariance_t *res, CovEpilogue *epi) {
   if (check_team(t, "marginal_covariances")) return DPGO_ERR;
   const int na = (int)t->ag.size();
   std::vector<int> offs(na + 1, 0);
@@ -174,8 +174,13 @@ int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int 
   k_cov_extract<<<(unsigned)((nout + 255) / 256), 256, 0, s>>>(d_M.p, n, N, pairs_d, num_pairs, outd);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(ev[3], s));
-  std::vector<double> host(4 + nout);
-  HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * (4 + nout), hipMemcpyDeviceToHost, s));
+  // with an epilogue the blocks stay on the device: the statistics alone come back, the epilogue queues its own copies
+  std::vector<double> host(4 + (epi ? 0 : nout));
+  HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
+  if (epi && epi->run({Td, outd, outd + (size_t)36 * N, N, num_pairs, s})) {
+    (void)hipStreamSynchronize(s);  // (copies into this frame and into the epilogue may be queued)
+    return DPGO_ERR;
+  }
   HIPC(hipStreamSynchronize(s));
   float ms_a = 0.f, ms_x = 0.f;
   HIPC(hipEventElapsedTime(&ms_a, ev[0], ev[1]));
@@ -194,6 +199,7 @@ int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int 
   if (timing)
     std::fprintf(stderr, "marginal_covariances: n %d, %zu blocks, assemble %.3f ms, invert %.3f ms, extract %.3f ms\n", n, items.size(),
                  ms_a, ms_i, ms_x);
+  if (epi) return DPGO_OK;
   std::memcpy(cov_diag, host.data() + 4, sizeof(double) * 36 * (size_t)N);
   if (num_pairs > 0) std::memcpy(cov_pairs, host.data() + 4 + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
   return DPGO_OK;

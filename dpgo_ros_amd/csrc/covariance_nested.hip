@@ -405,7 +405,7 @@ double gemm_flops(const GemmItem *it, int count) {
 // (message set), or 1: a pivot was not positive -- fail[0] the block (-1: the separator), fail[1] the team pose, fail[2] the
 // row of that factor.  The outputs are written only when every factorisation succeeded.
 int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T, int num_pairs, const int *pairs, double *cov_diag,
-                             double *cov_pairs, dpgo_covariance_t *res, int *fail) {
+                             double *cov_pairs, dpgo_covariance_t *res, int *fail, CovEpilogue *epi) {
   const char *what = "marginal_covariances_nested";
   const int na = P.na, N = P.N, nS = 6 * P.nS, nblk = (int)P.blocks.size();
   int max_n = 0, kmax = 0;
@@ -675,8 +675,13 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   }
   HIPC(hipGetLastError());
   MARK(4);
-  std::vector<double> host(4 * (size_t)(nblk + 1) + 2 * nout);
+  // with an epilogue the blocks stay on the device: the statistics alone come back, the epilogue queues its own copies
+  std::vector<double> host(4 * (size_t)(nblk + 1) + (epi ? 0 : 2 * nout));
   HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
+  if (epi && epi->run({Td, outd, outd + (size_t)36 * N, N, num_pairs, s})) {
+    (void)hipStreamSynchronize(s);  // (copies into this frame and into the epilogue may be queued)
+    return DPGO_ERR;
+  }
   HIPC(hipStreamSynchronize(s));
   double ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (size_t k = 1; k < marks.ev.size(); ++k) {
@@ -706,6 +711,7 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
                  6 * (N - 1), nblk, 6 * P.largest_block(), nbatch, nS, P.promoted, 6 * P.largest_nb(),
                  nbytes.large + nbytes.small + 8.0 * (ws_need - nbytes.ws_min), ms[0], ms[1], flops_fact / (1e9 * std::max(ms[1], 1e-9)), ms[2],
                  flops_prod / (1e9 * std::max(ms[2], 1e-9)), ms[3], ms[4]);
+  if (epi) return DPGO_OK;
   const double *o = host.data() + 4 * (size_t)(nblk + 1) + nout;
   std::memcpy(cov_diag, o, sizeof(double) * 36 * (size_t)N);
   if (num_pairs > 0) std::memcpy(cov_pairs, o + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
@@ -767,17 +773,22 @@ extern "C" int dpgo_team_covariance_nested_plan(dpgo_team_t *t, int max_block, i
 
 extern "C" int dpgo_team_marginal_covariances_nested(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs,
                                                      double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
+  return marginal_covariances_nested_call(t, T, max_block, num_pairs, pairs, cov_diag, cov_pairs, res, nullptr);
+}
+
+int dpgo_cert::marginal_covariances_nested_call(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs,
+                                                double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi) {
   const char *what = "marginal_covariances_nested";
   int N = 0;
-  const int pre = covariance_host_checks(t, T, nullptr, num_pairs, pairs, cov_diag, cov_pairs, res, what, &N);
+  const int pre = covariance_host_checks(t, T, nullptr, num_pairs, pairs, cov_diag, cov_pairs, res, what, &N, epi != nullptr);
   if (pre != DPGO_OK) return pre > 0 ? DPGO_OK : pre;
   if (check_team(t, what)) return DPGO_ERR;
   NestPlan P;
   nest_plan_team(t, nest_max_block(max_block), P);
   // no robot is split: the sets are those of the robot-wise Schur path, and so is the call
-  if (!P.split) return dpgo_team_marginal_covariances(t, T, DPGO_COV_SCHUR, num_pairs, pairs, cov_diag, cov_pairs, res);
+  if (!P.split) return marginal_covariances_call(t, T, DPGO_COV_SCHUR, num_pairs, pairs, cov_diag, cov_pairs, res, epi);
   int fail[3] = {0, 0, 0};
-  const int rc = covariance_nested_device(t, P, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail);
+  const int rc = covariance_nested_device(t, P, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail, epi);
   if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
   if (rc > 0) {
     const std::string where = fail[0] < 0 ? "the Schur complement on the separator"

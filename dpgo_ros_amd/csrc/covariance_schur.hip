@@ -399,7 +399,7 @@ static void schur_report(const SchurMarks &marks, double ms[5]) {
 // separator), fail[1] the team pose, fail[2] the row of that factor.  The outputs are written only when every factorisation
 // succeeded.
 int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
-                            dpgo_covariance_t *res, int *fail) {
+                            dpgo_covariance_t *res, int *fail, CovEpilogue *epi) {
   const char *what = "marginal_covariances";
   if (check_team(t, what)) return DPGO_ERR;
   SchurPartition P;
@@ -565,8 +565,13 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
   }
   if (schur_cross_pairs(s, d_rob.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
   MARK(4);
-  std::vector<double> host(4 * (size_t)(na + 1) + 2 * nout);
+  // with an epilogue the blocks stay on the device: the statistics alone come back, the epilogue queues its own copies
+  std::vector<double> host(4 * (size_t)(na + 1) + (epi ? 0 : 2 * nout));
   HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
+  if (epi && epi->run({Td, outd, outd + (size_t)36 * N, N, num_pairs, s})) {
+    (void)hipStreamSynchronize(s);  // (copies into this frame and into the epilogue may be queued)
+    return DPGO_ERR;
+  }
   HIPC(hipStreamSynchronize(s));
   double ms[5];
   schur_report(marks, ms);
@@ -590,6 +595,7 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
                  "marginal_covariances (Schur): n %d, separator %d, largest interior %d, %zu blocks, assemble %.3f ms, factorisations %.3f ms, "
                  "products %.3f ms, separator inverse %.3f ms, extract %.3f ms\n",
                  6 * (N - 1), nS, 6 * P.max_int, L.items.size(), ms[0], ms[1], ms[2], ms[3], ms[4]);
+  if (epi) return DPGO_OK;
   const double *o = host.data() + 4 * (size_t)(na + 1) + nout;
   std::memcpy(cov_diag, o, sizeof(double) * 36 * (size_t)N);
   if (num_pairs > 0) std::memcpy(cov_pairs, o + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);

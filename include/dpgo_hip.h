@@ -386,6 +386,37 @@ int dpgo_team_covariance_nested_plan(dpgo_team_t *t, int max_block, int *block_o
  * is no call across teams. */
 int dpgo_team_marginal_covariances_nested(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs,
                                           double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
+/* ---- candidate measurements gated by Mahalanobis distance (csrc/gate.hip) ----
+ * A candidate is a dpgo_measurement_t (r1, p1) -> (r2, p2) with R~ (row-major), t~, kappa, tau; weight, fixed_weight and
+ * is_known_inlier are ignored: it is a fresh measurement that is not in the graph.  Its endpoints map to the team poses i != j,
+ * T_j ~ T_i T~.  With T and Sigma as above (R_i <- R_i Exp(phi_i), t_i <- t_i + delta_i, rotation first, pose 0 fixed):
+ *   relative pose   R_ij = R_i^T R_j, t_ij = R_i^T (t_j - t_i), perturbed the same way: R_ij <- R_ij Exp(phi_ij),
+ *                   t_ij <- t_ij + delta_ij (delta_ij in frame i)
+ *   Jacobians       J_i = [[-R_ij^T, 0], [[t_ij]x, -R_i^T]],  J_j = [[I, 0], [0, R_i^T]]   (6 x 6, rotation first)
+ *   sigma_rel       J_i Sigma_ii J_i^T + J_i Sigma_ij J_j^T + J_j Sigma_ij^T J_i^T + J_j Sigma_jj J_j^T, stored as (A + A^T) / 2:
+ *                   bitwise symmetric, row-major; an endpoint that is pose 0 has zero blocks and needs no special case
+ *   xi              (Log(R~^T R_ij)v, t_ij - t~): theta = atan2(|a|, c) with a the vee of the antisymmetric part and
+ *                   c = (tr - 1) / 2; zero in gives zero out; within 0.1 rad of pi the axis comes from the symmetric part, and
+ *                   theta = pi gives a finite vector of norm pi
+ *   Sigma_meas      diag(I_3 / (2 kappa), I_3 / tau): the inverse Hessian of the candidate's own term
+ *                   1/2 (kappa |R_ij - R~|_F^2 + tau |t_ij - t~|^2) of the cost at zero residual
+ *   d2              xi^T (sigma_rel + Sigma_meas)^-1 xi by a 6 x 6 Cholesky; a non-positive pivot (garbage blocks) gives +inf.
+ * A candidate passes at quantile q when sqrt(d2) <= dpgo_error_threshold_at_quantile(q, 6).
+ * The blocks come from the covariance path `method` (max_block: DPGO_GATE_NESTED only, as in
+ * dpgo_team_marginal_covariances_nested), asked for the candidates' pairs (i, j), each once; they stay on the device, one
+ * kernel forms the outputs, and only xi (6 num), d2 (num) and sigma_rel (36 num) -- those that are not NULL -- come back.
+ * With xi == d2 == NULL only the endpoints of cand are read: the relative-covariance query.  Duplicated candidates give
+ * identical bits; two calls give the same bits.  Refused with DPGO_ERR and a message before any device work, every output
+ * untouched: num <= 0; all three outputs NULL; exactly one of xi and d2 NULL; an unknown method; an endpoint that is not a
+ * robot or pose of the team; i == j; and, when xi / d2 are requested, kappa <= 0 or tau <= 0, or R~ outside SO(3) by the
+ * 1e-8 rule of T.  Every refusal of the chosen covariance path carries over with its own message (T outside SE(3), a
+ * disconnected weighted graph, too little device memory, a non-positive pivot); the outputs are then untouched and *res all
+ * zero.  *res: the path's own record.  Changes no solver state.  There is no call across teams. */
+enum { DPGO_GATE_DENSE = 0, DPGO_GATE_SCHUR = 1, DPGO_GATE_NESTED = 2 };
+int dpgo_team_gate_candidates(dpgo_team_t *t, const double *T, int method, int max_block /* NESTED only */,
+                              int num, const dpgo_measurement_t *cand,
+                              double *xi /* 6 num or NULL */, double *d2 /* num or NULL */,
+                              double *sigma_rel /* 36 num or NULL */, dpgo_covariance_t *res);
 /* ---- certificate and rounding across teams (csrc/certify_across.hip) ----
  * A participant is one team that holds a subset of the robots; owner_rank_of_robot[num_robots] says which participant holds
  * each (the meaning of dpgo_team_attach_comm).  The library does not own the transport: it calls the two functions below,
