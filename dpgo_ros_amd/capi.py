@@ -129,7 +129,7 @@ dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
-dpgo_team_gate_candidates""".split()
+dpgo_team_gate_candidates dpgo_team_pairwise_consistency dpgo_max_clique""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1123,6 +1123,71 @@ class Team:
         out = [e for i in self.ids for e in self.agents[i].measurements()
                if e["weight"] == 0.0 and (e["r1"] == e["r2"] or min(int(e["r1"]), int(e["r2"])) == i)]
         return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
+
+
+def _adjacency_words(adjacency):
+    """a bool K x K matrix as K rows of ceil(K / 64) words, bit b of word w of row k = adjacency[k, 64 w + b]"""
+    A = np.ascontiguousarray(adjacency, dtype=bool)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("max_clique: the adjacency matrix must be square, not of shape %r" % (A.shape,))
+    K = A.shape[0]
+    W = (K + 63) // 64
+    padded = np.zeros((K, 64 * W), dtype=np.uint8)
+    padded[:, :K] = A
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u8").reshape(K, W)
+
+
+def _adjacency_bools(words, K):
+    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8).reshape(K, -1), axis=1, bitorder="little")[:, :K].astype(bool)
+
+
+def max_clique(adjacency, max_nodes=0):
+    """(members, proven): the ascending vertices of a maximum clique of the graph with the bool K x K matrix `adjacency`
+    (symmetric, zero diagonal), by exact branch and bound on the host; the same input gives the same members.  After
+    max_nodes search nodes (0: no limit) the search stops and returns the best clique found with proven = False."""
+    words = _adjacency_words(adjacency)
+    K = len(words)
+    members, size, proven = np.zeros(max(K, 1), dtype=np.int32), C.c_int(0), C.c_int(0)
+    _chk(lib().dpgo_max_clique(K, _d(words), C.c_longlong(int(max_nodes)), _d(members), C.byref(size), C.byref(proven)), "max_clique")
+    return members[:size.value].copy(), bool(proven.value)
+
+
+def pairwise_consistency(team_a, team_b, candidates, T_a=None, T_b=None, method=None, max_block=None, quantile=0.99, max_nodes=0):
+    """The pairwise-consistent set of candidate loop closures between two teams that are not joined yet (pairwise consistency
+    maximisation).  candidates: MEAS_DTYPE records whose (r1, p1) names a pose of team_a and (r2, p2) a pose of
+    team_b, with R (row-major), t, kappa, tau; weight and the flags are ignored.  Each team has a connected weighted graph of
+    its own (build one single-robot team per robot from its private measurements); they may be the same team.  T_a, T_b: the
+    trajectories in the teams' own gauges (None: the rounding of that team's iterate, as in Team.gate); method, max_block: the
+    covariance path of both teams, as in Team.gate.  For every two candidates the loop through both and through the two
+    teams' own trajectories is tested against its covariance on the device; returns a dict with d2[K, K] (symmetric, zero
+    diagonal), consistent (bool [K, K]: d2 <= error_threshold_at_quantile(quantile, 6) ** 2 off the diagonal), inliers (the
+    ascending indices of a maximum clique of `consistent`), proven (False when max_nodes > 0 stopped the search) and res_a,
+    res_b (each path's Covariance).  Raises DpgoError as Team.covariances does for either team, and for a candidate that names
+    a robot or pose outside its team, has kappa <= 0 or tau <= 0, or an R outside SO(3).  Changes no solver state."""
+    if method not in (None, "dense", "schur", "nested"):
+        raise ValueError("pairwise_consistency: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+    Ts = []
+    for team, T in ((team_a, T_a), (team_b, T_b)):
+        N = int(sum(team.agents[i].n for i in team.ids))
+        if T is None:
+            T = team.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("pairwise_consistency: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        Ts.append(T)
+    cand = np.ascontiguousarray(candidates, dtype=MEAS_DTYPE).reshape(-1)
+    K = len(cand)
+    W = (K + 63) // 64
+    d2, words = np.zeros((K, K)), np.zeros((K, max(W, 1)), dtype="<u8")
+    members, size, proven = np.zeros(max(K, 1), dtype=np.int32), C.c_int(0), C.c_int(0)
+    res_a, res_b = Covariance(), Covariance()
+    code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+    _chk(lib().dpgo_team_pairwise_consistency(team_a.h, _d(Ts[0]), team_b.h, _d(Ts[1]), code, int(max_block or 0), K, _d(cand),
+                                              C.c_double(quantile), C.c_longlong(int(max_nodes)), _d(d2), _d(words), _d(members),
+                                              C.byref(size), C.byref(proven), C.byref(res_a), C.byref(res_b)),
+         "pairwise_consistency")
+    return dict(d2=d2, consistent=_adjacency_bools(words, K), inliers=members[:size.value].copy(), proven=bool(proven.value),
+                res_a=res_a, res_b=res_b)
 
 
 def covariance_to_body_frame(cov, T):

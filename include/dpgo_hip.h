@@ -14,6 +14,7 @@
  */
 #ifndef DPGO_HIP_H
 #define DPGO_HIP_H
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -417,6 +418,46 @@ int dpgo_team_gate_candidates(dpgo_team_t *t, const double *T, int method, int m
                               int num, const dpgo_measurement_t *cand,
                               double *xi /* 6 num or NULL */, double *d2 /* num or NULL */,
                               double *sigma_rel /* 36 num or NULL */, dpgo_covariance_t *res);
+/* ---- the pairwise-consistent set of candidates between two teams (csrc/consistency.hip, csrc/max_clique.cpp) ----
+ * Pairwise consistency maximisation (Mangelson et al. 2018) for loop closures between two teams that are NOT joined yet, each
+ * with a connected weighted graph of its own (they may be the same handle), trajectories T_a and T_b in their own gauges.
+ * Candidate k is a dpgo_measurement_t whose (r1, p1) names a pose i_k of team a and (r2, p2) a pose j_k of team b, with R~
+ * (row-major), t~, kappa, tau; weight and the flags are ignored.  Z_k ~ (T^a_{i_k})^-1 G T^b_{j_k} for one unknown G common
+ * to the true candidates.  For k < l, every pose perturbed as R <- R Exp(phi), t <- t + delta:
+ *   segments     A_kl = (T^a_{i_l})^-1 T^a_{i_k},  B_kl = (T^b_{j_k})^-1 T^b_{j_l}, with the covariances sigma_rel(i_l, i_k) and
+ *                sigma_rel(j_k, j_l) of dpgo_team_gate_candidates from each team's own covariance path `method` (bit for bit
+ *                those blocks); a segment whose two poses coincide is the identity with zero covariance
+ *   loop         E_kl = Z_l^-1 A_kl Z_k B_kl, the identity when both candidates are true;  xi = (Log(R_E)v, t_E), the
+ *                logarithm of the gate
+ *   covariance   S = J_A Sigma_A J_A^T + J_B Sigma_B J_B^T + J_k N_k J_k^T + J_l N_l J_l^T, symmetrised, N = diag(I / (2 kappa),
+ *                I / tau), J the Jacobians of the four-factor product.  The correlation between the two segments is dropped:
+ *                zero for separate teams; PCM's standing approximation when a and b are the same team
+ *   distance     d2[k, l] = d2[l, k] = xi^T S^-1 xi by a 6 x 6 Cholesky (a non-positive pivot gives +inf), d2[k, k] = 0; both
+ *                triangles are bitwise equal.  k and l are consistent when d2 <= thr^2, thr =
+ *                dpgo_error_threshold_at_quantile(quantile, 6)
+ * d2 (num x num, row-major) and adj (num rows of W = ceil(num / 64) words, bit b of word w of row k: k and 64 w + b are
+ * consistent; no bit on the diagonal or at or beyond num) may each be NULL.  members receives the ascending indices of a
+ * maximum clique of the consistency graph (room for num), *size their number and *proven whether the search finished
+ * (dpgo_max_clique with max_nodes).  *res_a / *res_b: each path's own record; a team none of whose segments joins two
+ * different poses (num = 1, for one) is not asked, and its record is all zero.  Two calls give the same bits.
+ * Refused with DPGO_ERR and a message that names the candidate, before any device work and with every output untouched:
+ * num <= 0, a NULL argument, an unknown method, quantile outside (0, 1), max_nodes < 0, teams on different devices, an endpoint
+ * that is not a robot or pose of its team, kappa <= 0 or tau <= 0, a non-finite entry, R~ outside SO(3) by the 1e-8 rule, and
+ * staged bytes (384 per segment, 12 num^2 and small change) that do not fit the free device memory.  Every refusal of the
+ * covariance path of either team carries over with its own message, the outputs untouched.  Changes no solver state of either
+ * team.  There is no call across processes. */
+int dpgo_team_pairwise_consistency(dpgo_team_t *a, const double *T_a, dpgo_team_t *b, const double *T_b,
+                                   int method /* DPGO_GATE_* */, int max_block /* NESTED only */, int num,
+                                   const dpgo_measurement_t *cand, double quantile, long long max_nodes,
+                                   double *d2 /* num^2 or NULL */, uint64_t *adj /* num W or NULL */, int *members, int *size,
+                                   int *proven, dpgo_covariance_t *res_a, dpgo_covariance_t *res_b);
+/* A maximum clique of the graph on K vertices whose adjacency matrix is adj: K rows of W = ceil(K / 64) words, bit b of word w
+ * of row k set when k and 64 w + b are joined.  Host only.  Exact branch and bound on bitsets with a greedy-colouring bound;
+ * the vertices are ordered by degeneracy and the search is seeded by a greedy clique; a larger clique replaces the incumbent
+ * only when strictly larger, so the same input gives the same members.  After max_nodes search nodes (0: no limit) it stops
+ * and returns the incumbent with *proven = 0, else *proven = 1.  members (room for K): ascending.  Refused: K <= 0, a NULL
+ * argument, max_nodes < 0, a matrix that is not symmetric, a set diagonal bit, a set bit at or beyond K. */
+int dpgo_max_clique(int K, const uint64_t *adj, long long max_nodes, int *members, int *size, int *proven);
 /* ---- certificate and rounding across teams (csrc/certify_across.hip) ----
  * A participant is one team that holds a subset of the robots; owner_rank_of_robot[num_robots] says which participant holds
  * each (the meaning of dpgo_team_attach_comm).  The library does not own the transport: it calls the two functions below,
