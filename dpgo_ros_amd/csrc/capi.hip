@@ -1668,125 +1668,3 @@ int dpgo_team_time_kernel(dpgo_team_t *t, int id, int which, int reps, double *a
 }
 
 }  // extern "C"
-
-// ---- marginal pose covariances (covariance.hip): every refusal that can be decided on the host comes first.
-// The three methods share them: DPGO_OK to go on (the device is selected), 1 when the team holds the anchor alone and the outputs
-// are already written, DPGO_ERR with a message that `what` prefixes.  flags_error: what is wrong with the caller's flags (or null)
-int dpgo_cert::covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs,
-                                      double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses,
-                                      bool staged) {
-  if (res) std::memset(res, 0, sizeof *res);
-  // staged: the blocks stay on the device for an epilogue (certify_internal.h) and the two outputs are not used
-  if (!t || !T || (!staged && !cov_diag) || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || (!staged && !cov_pairs)))) {
-    set_err(std::string(what) + ": null argument");
-    return DPGO_ERR;
-  }
-  if (flags_error) { set_err(std::string(what) + ": " + flags_error); return DPGO_ERR; }
-  if (dpgo_cert::check_team_local(t, what)) return DPGO_ERR;
-  const int na = (int)t->ag.size();
-  std::vector<int> offs(na + 1, 0);
-  for (int k = 0; k < na; ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
-  const int N = offs[na];
-  // T in SE(3): R column-major in the first 9 of the 12 doubles of a pose
-  for (int g = 0; g < N; ++g) {
-    const double *R = T + (size_t)12 * g;
-    double orth = 0.0;
-    for (int p = 0; p < 3; ++p)
-      for (int q = 0; q < 3; ++q) {
-        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
-        orth = std::max(orth, std::fabs(d));
-      }
-    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
-    bool finite = true;
-    for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(R[k]);
-    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "%s: pose %d of T is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", what, g, orth, det);
-      set_err(buf);
-      return DPGO_ERR;
-    }
-  }
-  for (int k = 0; k < 2 * num_pairs; ++k)
-    if (pairs[k] < 0 || pairs[k] >= N) {
-      set_err(std::string(what) + ": pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) +
-              ", outside [0, " + std::to_string(N) + ")");
-      return DPGO_ERR;
-    }
-  {
-    std::vector<dpgo_measurement_t> mm;
-    if (dpgo_cert::team_measurements(t, offs, what, mm)) return DPGO_ERR;
-    if (check_joined_to_pose0(mm.data(), (int)mm.size(), N, what)) return DPGO_ERR;
-  }
-  *num_poses = N;
-  if (N < 2) {  // the anchor alone: nothing is free
-    if (!staged) {
-      std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
-      if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
-    }
-    return 1;
-  }
-  HIPC(hipSetDevice(t->device));
-  return DPGO_OK;
-}
-
-extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs,
-                                              double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
-  return dpgo_cert::marginal_covariances_call(t, T, flags, num_pairs, pairs, cov_diag, cov_pairs, res, nullptr);
-}
-
-int dpgo_cert::marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
-                                         double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi) {
-  const char *what = "marginal_covariances";
-  int N = 0;
-  const int pre = dpgo_cert::covariance_host_checks(t, T, flags != 0 && flags != DPGO_COV_SCHUR ? "flags must be 0 or DPGO_COV_SCHUR" : nullptr,
-                                                    num_pairs, pairs, cov_diag, cov_pairs, res, what, &N, epi != nullptr);
-  if (pre != DPGO_OK) return pre > 0 ? DPGO_OK : pre;
-  if (flags == DPGO_COV_SCHUR) {
-    // by robot-wise Schur complement (covariance_schur.hip): its own memory accounting, from the partition
-    int fail[3] = {0, 0, 0};
-    const int rc = dpgo_cert::covariance_schur_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail, epi);
-    if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
-    if (rc > 0) {
-      const std::string where = fail[0] < 0 ? "the Schur complement on the public poses"
-                                            : "the interior Hessian of robot " + std::to_string(t->ag[fail[0]]->id);
-      set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(fail[2]) + " of " + where + " (pose " +
-              std::to_string(fail[1]) + "): the Hessian is not positive definite at this T: not a minimum");
-      return DPGO_ERR;
-    }
-    return rc;
-  }
-  {
-    // three dense matrices of order 6 (N - 1); idle pooled buffers count as used memory but are one flush away from free
-    // (the accounting of the preconditioner budget, assembly.hip)
-    const double n = 6.0 * (N - 1), need = 3.0 * n * n * 8.0;
-    size_t free_b = 0, total_b = 0;
-    HIPC(hipMemGetInfo(&free_b, &total_b));
-    const double avail = (double)free_b + (double)pool_held(t->device);
-    if (need > avail) {
-      char buf[400];
-      std::snprintf(buf, sizeof buf,
-                    "%s: the dense Hessian of order %.0f and its inverse need %.0f bytes, %.0f are available on the device.  "
-                    "flags = DPGO_COV_SCHUR (method=\"schur\") eliminates one robot's interior at a time and needs far less",
-                    what, n, need, avail);
-      set_err(buf);
-      return DPGO_ERR;
-    }
-  }
-  const int rc = dpgo_cert::covariance_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, epi);
-  if (rc > 0) {
-    std::memset(res, 0, sizeof *res);
-    const int row = rc - 1;
-    set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(row) + " of the reduced Hessian (pose " +
-            std::to_string(row / 6 + 1) + "): the Hessian is not positive definite at this T: not a minimum");
-    return DPGO_ERR;
-  }
-  if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
-  return rc;
-}
-
-// the same call over a split team (covariance_schur.hip): the Schur path is its only method
-extern "C" int dpgo_team_marginal_covariances_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
-                                                     const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
-                                                     double *cov_pairs, dpgo_covariance_t *res) {
-  return dpgo_cert::covariance_schur_across(t, tr, owner_rank_of_robot, T, flags, num_pairs, pairs, cov_diag, cov_pairs, res);
-}

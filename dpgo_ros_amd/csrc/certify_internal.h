@@ -167,17 +167,18 @@ struct CovEpilogue {
   virtual ~CovEpilogue() = default;
 };
 
-// the device part of dpgo_team_marginal_covariances (covariance.hip; the host-side refusals are in capi.hip): DPGO_OK,
-// DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian was not positive
+// the device part of dpgo_team_marginal_covariances by the dense inverse (covariance.hip, behind the host-side refusals of
+// marginal_covariances_call): DPGO_OK, DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian
+// was not positive
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
                       dpgo_covariance_t *res, CovEpilogue *epi = nullptr);
-// dpgo_team_marginal_covariances / _nested with an epilogue in the place of the copy of the blocks (capi.hip,
+// dpgo_team_marginal_covariances / _nested with an epilogue in the place of the copy of the blocks (covariance.hip,
 // covariance_nested.hip): the public calls are these with epi = nullptr; with one, cov_diag and cov_pairs may be null
 int marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
                               double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi);
 int marginal_covariances_nested_call(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs, double *cov_diag,
                                      double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi);
-// the refusals of the marginal covariances that are decided on the host, shared by its methods (capi.hip): DPGO_OK, 1 (the
+// the refusals of the marginal covariances that are decided on the host, shared by its methods (covariance.hip): DPGO_OK, 1 (the
 // anchor alone: outputs written), or DPGO_ERR
 int covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs, double *cov_diag,
                            double *cov_pairs, dpgo_covariance_t *res, const char *what, int *num_poses, bool staged = false);

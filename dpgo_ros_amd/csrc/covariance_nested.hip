@@ -17,13 +17,15 @@
 // are filled in block order while their matrices fit the workspace.  A block's arithmetic does not depend on the batch it
 // rides in (one workgroup per 64 x 64 tile and K in index order, dgemm_tile; the factorisation's kernels serve a matrix by
 // blockIdx.z), so neither do the bits of the result.  No atomics, fp64 throughout, outputs staged on the device.
+// The blocks are the sets of the extraction kernels of covariance_extract.h, which the Schur path launches too; the head and
+// the tail of the call are CovFrame's (covariance_frame.h).
 // Loads of matrices, lists and index arrays go through gp(); the one exception is the record of a table (GemmItem,
-// NestTarget, NestBlock: one per workgroup or per thread, a few dozen bytes), copied as a struct like SchurRobot in
-// covariance_schur.hip -- where the index is uniform (blockIdx) the compiler reads it through the scalar cache.
+// NestTarget, CovBlock: one per workgroup or per thread, a few dozen bytes), copied as a struct -- where the index is
+// uniform (blockIdx) the compiler reads it through the scalar cache.
 #include <cmath>
 #include <cstdlib>
 
-#include "covariance_schur.h"
+#include "covariance_extract.h"
 
 namespace dpgo {
 
@@ -72,20 +74,6 @@ __global__ __launch_bounds__(256) void k_dgemm_batched(const GemmItem *__restric
   dgemm_tile<TA>(g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.m, g.n, g.k, sub, i0, j0);
 }
 
-// block b on the device.  W: the kept W_b (ld x K, ld = 6 |I_b|, K = 6 |N_b|); nb: the |N_b| separator indices; ipose: the
-// team pose of interior index li; M: C_b while the block's batch is being eliminated; G, Z: Sigma_SS[N_b, N_b] (K x K) and
-// Z_b (ld x K) while its batch is being extracted (M, G and Z lie in the batch workspace: blocks of different batches share them)
-struct NestBlock {
-  const double *W;
-  const int *nb, *ipose;
-  double *M, *G, *Z;
-  int ld, K;
-};
-static_assert(sizeof(NestBlock) == 56, "the byte formula of include/dpgo_hip.h counts 56 bytes");
-
-// row r of the separator's matrices for column k of a block's W: pose nb[k / 6], component k mod 6
-__device__ __forceinline__ size_t nest_row(const int *__restrict__ nb, int k) { return (size_t)6 * gp(nb)[k / 6] + (size_t)(k % 6); }
-
 // S[N_b, N_b] -= P (K x K, column-major, ld K), S of order n.  One launch per block, in block order on one stream: two blocks
 // that meet in an element of S subtract from it in that order
 __global__ __launch_bounds__(256) void k_nest_scatter_sub(double *__restrict__ S, int n, const double *__restrict__ P, int K,
@@ -93,131 +81,8 @@ __global__ __launch_bounds__(256) void k_nest_scatter_sub(double *__restrict__ S
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (size_t)K * K) return;
   const int i = (int)(e % K), j = (int)(e / K);
-  double *s = S + nest_row(nb, j) * n + nest_row(nb, i);
+  double *s = S + cov_row(nb, j) * n + cov_row(nb, i);
   gp(s)[0] = gp(s)[0] - gp(P)[e];
-}
-
-// a list entry of the extraction: output block blk, block b (or -1), two indices, one flag
-struct NestBlk {
-  int blk, b, i, j, f, pad_;
-};
-// a pair of interior poses of two blocks: output block, block and interior index of the left pose, then of the right one
-struct NestCross {
-  int blk, ba, li, bb, lj, pad_;
-};
-
-// keep[36 blk + 6 a + c] = C_b[6 i + a, 6 j + c], one thread per element
-__global__ __launch_bounds__(256) void k_nest_keep(const NestBlock *__restrict__ tab, const NestBlk *__restrict__ list, int count,
-                                                   double *__restrict__ keep) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, c = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], b = gp(lp)[1], i = gp(lp)[2], j = gp(lp)[3];
-  const NestBlock B = tab[b];
-  gp(keep)[(size_t)36 * blk + q] = gp(B.M)[((size_t)6 * j + c) * B.ld + (size_t)6 * i + a];
-}
-
-// G_b = Sigma_SS[N_b, N_b] for the blocks b0 + blockIdx.y of a batch (Sg: Sigma_SS, order n)
-__global__ __launch_bounds__(256) void k_nest_gather(const NestBlock *__restrict__ tab, int b0, const double *__restrict__ Sg, int n) {
-  const NestBlock B = tab[b0 + blockIdx.y];
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)B.K * B.K) return;
-  const int i = (int)(e % B.K), j = (int)(e / B.K);
-  gp(B.G)[e] = gp(Sg)[nest_row(B.nb, j) * n + nest_row(B.nb, i)];
-}
-
-// the diagonal blocks of the interior poses of the blocks b0 + blockIdx.y: X = C_ii + Z[i,:] W[i,:]^T, out = (X + X^T) / 2 by
-// the statement of k_schur_diag (both operands of an element and of its mirror are the same two numbers)
-__global__ __launch_bounds__(256) void k_nest_diag(const NestBlock *__restrict__ tab, int b0, const double *__restrict__ keep,
-                                                   double *__restrict__ out) {
-  const NestBlock B = tab[b0 + blockIdx.y];
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)6 * B.ld) return;
-  const int r = (int)(e % B.ld), c = (int)(e / B.ld), li = r / 6, a = r - 6 * li;
-  const double sac = schur_row_dot(B.Z, B.ld, r, B.W, B.ld, 6 * li + c, B.K), sca = schur_row_dot(B.Z, B.ld, 6 * li + c, B.W, B.ld, r, B.K);
-  const size_t o = (size_t)36 * gp(B.ipose)[li];
-  gp(out)[o + 6 * a + c] = 0.5 * ((gp(keep)[o + 6 * a + c] + sac) + (gp(keep)[o + 6 * c + a] + sca));
-}
-
-// pairs of two interior poses of one block: out = C_ij + Z[i,:] W[j,:]^T
-__global__ __launch_bounds__(256) void k_nest_pair_same(const NestBlock *__restrict__ tab, const NestBlk *__restrict__ list, int count,
-                                                        const double *__restrict__ keep, double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, c = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], b = gp(lp)[1], i = gp(lp)[2], j = gp(lp)[3];
-  const NestBlock B = tab[b];
-  const size_t o = (size_t)36 * blk + q;
-  gp(out)[o] = gp(keep)[o] + schur_row_dot(B.Z, B.ld, 6 * i + a, B.W, B.ld, 6 * j + c, B.K);
-}
-
-// blocks of Sigma_SS (Sg, order n): f = 1 a diagonal block, symmetrised as k_cov_extract does; f = 0 the block (i, j)
-__global__ __launch_bounds__(256) void k_nest_public(const double *__restrict__ Sg, int n, const NestBlk *__restrict__ list, int count,
-                                                     double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, c = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], i = gp(lp)[2], j = gp(lp)[3], f = gp(lp)[4];
-  const size_t oi = (size_t)6 * i, oj = (size_t)6 * j;
-  double v = gp(Sg)[(oj + c) * n + oi + a];
-  if (f) v = 0.5 * (v + gp(Sg)[(oi + a) * n + oi + c]);
-  gp(out)[(size_t)36 * blk + q] = v;
-}
-
-// interior pose i of block b with separator pose j: -W_b[i,:] Sigma_SS[N_b, j], k in index order (f: its transpose, the pair
-// was (separator, interior))
-__global__ __launch_bounds__(256) void k_nest_pair_is(const NestBlock *__restrict__ tab, const double *__restrict__ Sg, int n,
-                                                      const NestBlk *__restrict__ list, int count, double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, c = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], b = gp(lp)[1], li = gp(lp)[2], sj = gp(lp)[3], f = gp(lp)[4];
-  const NestBlock B = tab[b];
-  const double *col = Sg + ((size_t)6 * sj + c) * n;
-  double acc = 0.0;
-  for (int k = 0; k < B.K; ++k) acc = __builtin_fma(gp(B.W)[(size_t)k * B.ld + 6 * li + a], gp(col)[nest_row(B.nb, k)], acc);
-  gp(out)[(size_t)36 * blk + (f ? 6 * c + a : 6 * a + c)] = -acc;
-}
-
-// interior poses of two blocks, first half: t[p][c][a] = sum_k W_a[6 li + a, k] Sigma_SS[N_a[k], N_b[c]] for the K_b columns
-// c.  blockIdx.y: the pair of this chunk; a thread per column, the six rows at once (Sigma_SS is bitwise symmetric: the
-// element is read at [N_b[c], N_a[k]], consecutive threads near-consecutive addresses)
-__global__ __launch_bounds__(256) void k_nest_cross_t(const NestBlock *__restrict__ tab, const double *__restrict__ Sg, int n,
-                                                      const NestCross *__restrict__ list, int kmax, double *__restrict__ tbuf) {
-  const int *lp = (const int *)(list + blockIdx.y);
-  const int ba = gp(lp)[1], li = gp(lp)[2], bb = gp(lp)[3];
-  const NestBlock A = tab[ba], B = tab[bb];
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= B.K) return;
-  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const double *w = A.W + 6 * li, *sg = Sg + nest_row(B.nb, c);
-  for (int k = 0; k < A.K; ++k) {
-    const double sv = gp(sg)[nest_row(A.nb, k) * n];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[a] = __builtin_fma(gp(w)[(size_t)k * A.ld + a], sv, acc[a]);
-  }
-  double *o = tbuf + ((size_t)blockIdx.y * kmax + c) * 6;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) gp(o)[a] = acc[a];
-}
-
-// second half: out[a][c] = sum_l t[p][l][a] W_b[6 lj + c, l], l in index order
-__global__ __launch_bounds__(256) void k_nest_cross_out(const NestBlock *__restrict__ tab, const NestCross *__restrict__ list, int count,
-                                                        int kmax, const double *__restrict__ tbuf, double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int p = (int)(e / 36), q = (int)(e % 36), a = q / 6, c = q - 6 * a;
-  const int *lp = (const int *)(list + p);
-  const int blk = gp(lp)[0], bb = gp(lp)[3], lj = gp(lp)[4];
-  const NestBlock B = tab[bb];
-  const double *t = tbuf + (size_t)p * kmax * 6 + a;
-  double acc = 0.0;
-  for (int l = 0; l < B.K; ++l) acc = __builtin_fma(gp(t)[(size_t)6 * l], gp(B.W)[(size_t)l * B.ld + 6 * lj + c], acc);
-  gp(out)[(size_t)36 * blk + q] = acc;
 }
 
 }  // namespace dpgo
@@ -331,11 +196,6 @@ double nest_block_ws(const NestPlan::Block &b) {
   return 3.0 * n * n + n * K + K * K;
 }
 
-size_t nest_cross_chunk(size_t pairs, int kmax) {
-  if (pairs == 0) return 0;
-  return std::max<size_t>(1, std::min<size_t>({pairs, (size_t)65535, ((size_t)8 << 20) / ((size_t)6 * std::max(kmax, 1))}));
-}
-
 struct NestBytes {
   double large = 0, small = 0, ws_min = 0, w_all = 0, sep = 0;
   int ws_block = -1;
@@ -344,7 +204,7 @@ struct NestBytes {
 // large = 8 (3 (6 |S|)^2 + sum_b 36 |I_b| |N_b| + max_b ws_b); small: T, T Q, Lambda (33 N doubles), the Gershgorin scratch,
 // 4 statistics per factor, the kept and the output blocks (72 (N + P) doubles), the scratch of pairs across blocks, the lists
 // (24 bytes per kept or requested block), the work list (40 bytes per stored block of Q), the tables of the blocks
-// (56 + 3 x 48 + 2 x 16 bytes each: a NestBlock, three GemmItem, two NestTarget), the index lists (4 bytes per interior pose
+// (56 + 3 x 48 + 2 x 16 bytes each: a CovBlock, three GemmItem, two NestTarget), the index lists (4 bytes per interior pose
 // and per entry of an N_b), the Linv blocks of dense_spd_inverse (8 KiB per 32 rows of every factor)
 NestBytes nest_bytes(dpgo_team_t *t, const NestPlan &P, int num_pairs) {
   NestBytes r;
@@ -366,8 +226,8 @@ NestBytes nest_bytes(dpgo_team_t *t, const NestPlan &P, int num_pairs) {
   r.large = 8.0 * (r.sep + r.w_all + r.ws_min);
   const double N = P.N, np = num_pairs, A = P.na, nb = (double)P.blocks.size();
   r.small = 8.0 * (33.0 * N + A * ((max_n + 255) / 256) + 4.0 * (nb + 1.0) + 72.0 * (N + np)) +
-            8.0 * 6.0 * std::max(kmax, 1) * (double)nest_cross_chunk((size_t)num_pairs, kmax) + 24.0 * (2.0 * N + 3.0 * np) +
-            40.0 * (double)stored + (double)(sizeof(NestBlock) + 3 * sizeof(GemmItem) + 2 * sizeof(NestTarget)) * nb +
+            8.0 * 6.0 * std::max(kmax, 1) * (double)cov_cross_chunk((size_t)num_pairs, kmax) + 24.0 * (2.0 * N + 3.0 * np) +
+            40.0 * (double)stored + (double)(sizeof(CovBlock) + 3 * sizeof(GemmItem) + 2 * sizeof(NestTarget)) * nb +
             4.0 * (N + (double)P.sum_nb() + A + 1.0) + 8.0 * 1024.0 * linv;
   return r;
 }
@@ -407,17 +267,14 @@ double gemm_flops(const GemmItem *it, int count) {
 int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T, int num_pairs, const int *pairs, double *cov_diag,
                              double *cov_pairs, dpgo_covariance_t *res, int *fail, CovEpilogue *epi) {
   const char *what = "marginal_covariances_nested";
-  const int na = P.na, N = P.N, nS = 6 * P.nS, nblk = (int)P.blocks.size();
-  int max_n = 0, kmax = 0;
-  for (int k = 0; k < na; ++k) max_n = std::max(max_n, t->ag[k]->n);
+  const int N = P.N, nS = 6 * P.nS, nblk = (int)P.blocks.size();
+  int kmax = 0;
   for (const NestPlan::Block &b : P.blocks) kmax = std::max(kmax, 6 * (int)b.nb.size());
   // ---- memory: refused before any device work
   const NestBytes nbytes = nest_bytes(t, P, num_pairs);
   double avail = 0.0;
   {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { set_err(std::string(what) + ": hipMemGetInfo failed"); return DPGO_ERR; }
-    avail = (double)free_b + (double)pool_held(t->device);
+    if (!cov_device_avail(t, &avail)) { set_err(std::string(what) + ": hipMemGetInfo failed"); return DPGO_ERR; }
     if (nbytes.large + nbytes.small > avail) {
       const bool by_sep = nbytes.sep >= nbytes.ws_min;
       const NestPlan::Block &wb = P.blocks[nbytes.ws_block];
@@ -445,7 +302,6 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   SchurItems L;
   auto classify = [&](int bi, int bj, int agent, int idx) -> int {
     if (bi == 0 || bj == 0) return 0;
-    if (bi < 0 || bi >= N || bj < 0 || bj >= N) return -1;
     const int ci = P.block_of[bi], cj = P.block_of[bj];
     if (ci < 0 && cj < 0) { if (bi <= bj) L.add(nblk, bi, bj, agent, idx, P.pos[bi], P.pos[bj], CD_MIRROR); }
     else if (ci >= 0 && cj >= 0) {
@@ -459,54 +315,23 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     }
     return 0;
   };
-  for (int k = 0; k < na; ++k) {
-    const Agent &a = *t->ag[k];
-    for (int j = 0; j < a.n; ++j)
-      for (int p = a.rowptr[j]; p < a.rowptr[j + 1]; ++p)
-        if (classify(P.offs[k] + a.col[p], P.offs[k] + j, k, p)) { set_err(std::string(what) + ": a stored block lies outside the plan's sets"); return DPGO_ERR; }
-    for (size_t e = 0; e < a.se_host.size(); ++e) {
-      const SharedEdgeDev &se = a.se_host[e];
-      if (se.src_agent_local < 0 || se.src_agent_local >= na ||
-          classify(P.offs[se.src_agent_local] + se.src_frame, P.offs[k] + se.lpose, k, ~(int)e)) {
-        set_err(std::string(what) + ": a stored block lies outside the plan's sets");
-        return DPGO_ERR;
-      }
-    }
-  }
+  if (cov_for_each_stored_block(t, P.offs, classify)) { set_err(std::string(what) + ": a stored block lies outside the plan's sets"); return DPGO_ERR; }
   L.finish(nblk + 1);
   // ---- the outputs asked for, by case.  Block numbers: [0, N) the diagonal blocks, N + k pair k.  keep and same are in
   // block order (the blocks of a batch are one range of either list)
-  std::vector<std::vector<NestBlk>> keep_of(nblk), same_of(nblk);
-  std::vector<NestBlk> pub_list, is_list;
-  std::vector<NestCross> cross_list;
-  for (int g = 1; g < N; ++g) {
-    const int b = P.block_of[g];
-    if (b < 0) pub_list.push_back({g, -1, P.pos[g], P.pos[g], 1, 0});
-    else keep_of[b].push_back({g, b, P.pos[g], P.pos[g], 0, 0});
-  }
-  for (int k = 0; k < num_pairs; ++k) {
-    const int a = pairs[2 * k], b = pairs[2 * k + 1], blk = N + k;
-    if (a == 0 || b == 0) continue;  // zeros
-    const int ca = P.block_of[a], cb = P.block_of[b];
-    if (ca < 0 && cb < 0) pub_list.push_back({blk, -1, P.pos[a], P.pos[b], 0, 0});
-    else if (ca >= 0 && cb >= 0) {
-      if (ca == cb) { keep_of[ca].push_back({blk, ca, P.pos[a], P.pos[b], 0, 0}); same_of[ca].push_back({blk, ca, P.pos[a], P.pos[b], 0, 0}); }
-      else cross_list.push_back({blk, ca, P.pos[a], cb, P.pos[b], 0});
-    } else if (ca >= 0) is_list.push_back({blk, ca, P.pos[a], P.pos[b], 0, 0});
-    else is_list.push_back({blk, cb, P.pos[b], P.pos[a], 1, 0});
-  }
-  std::vector<NestBlk> keep_list, same_list;
+  CovOutputs O;
+  cov_classify_outputs(N, nblk, pairs, num_pairs, [&](int g) { return P.block_of[g]; }, P.pos, O);
+  std::vector<CovBlk> keep_list, same_list;
   std::vector<int> keep_beg(nblk + 1, 0), same_beg(nblk + 1, 0);
   for (int b = 0; b < nblk; ++b) {
-    keep_list.insert(keep_list.end(), keep_of[b].begin(), keep_of[b].end());
-    same_list.insert(same_list.end(), same_of[b].begin(), same_of[b].end());
+    keep_list.insert(keep_list.end(), O.keep[b].begin(), O.keep[b].end());
+    same_list.insert(same_list.end(), O.same[b].begin(), O.same[b].end());
     keep_beg[b + 1] = (int)keep_list.size();
     same_beg[b + 1] = (int)same_list.size();
   }
   // ---- device storage
-  const size_t SS = (size_t)nS * nS, L3 = (size_t)12 * N, nout = (size_t)36 * (N + num_pairs);
-  const size_t cross_chunk = nest_cross_chunk(cross_list.size(), kmax);
-  const int gstride = (max_n + 255) / 256;
+  const size_t SS = (size_t)nS * nS;
+  const size_t cross_chunk = cov_cross_chunk(O.cross.size(), kmax);
   // the batch workspace: the largest batch as the batches were cut
   double ws_need = 0.0;
   for (int q = 0; q < nbatch; ++q) {
@@ -514,21 +339,19 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     for (int b = bbeg[q]; b < bbeg[q + 1]; ++b) u += nest_block_ws(P.blocks[b]);
     ws_need = std::max(ws_need, u);
   }
-  DevBuf<double> d_S, d_Wk, d_M, d_W, d_ws, d_small, d_t;
+  CovFrame F(t);
+  DevBuf<double> d_S, d_Wk, d_M, d_W, d_ws, d_t;
   DevBuf<int> d_int;
   DevBuf<CovItem> d_items;
   DevBuf<CovSrc> d_src;
   DevBuf<CovDst> d_dst;
   DevBuf<NestTarget> d_tgt;
   DevBuf<GemmItem> d_gemm;
-  DevBuf<NestBlock> d_tab;
-  DevBuf<NestBlk> d_keep, d_same, d_pub, d_is;
-  DevBuf<NestCross> d_cross;
-  // d_small: T, E = T Q, Lambda, the Gershgorin scratch of k_cert_lambda, [logdet, min, max] per factor, the kept blocks of the
-  // C_b, the output blocks
-  const size_t small = 2 * L3 + (size_t)9 * N + (size_t)na * gstride + 4 * (size_t)(nblk + 1) + 2 * nout;
-  // d_int: the pose offsets of the robots, the team pose of every interior index (block after block), the N_b
-  std::vector<int> ints(P.offs.begin(), P.offs.end());
+  DevBuf<CovBlock> d_tab;
+  DevBuf<CovBlk> d_keep, d_same, d_pub, d_is;
+  DevBuf<CovCross> d_cross;
+  // d_int: the team pose of every interior index (block after block), the N_b
+  std::vector<int> ints;
   std::vector<size_t> ipose_at(nblk), nb_at(nblk), w_at(nblk + 1, 0);
   for (int b = 0; b < nblk; ++b) {
     ipose_at[b] = ints.size();
@@ -539,19 +362,20 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   }
   hipStream_t s = t->stream;
   const bool bad = d_S.alloc(SS) || d_Wk.alloc(SS) || d_M.alloc(SS) || d_W.alloc(w_at[nblk]) || d_ws.alloc((size_t)ws_need) ||
-                   d_small.alloc(small) || d_t.alloc(cross_chunk * 6 * std::max(kmax, 1)) || d_int.upload(ints, s) ||
+                   d_t.alloc(cross_chunk * 6 * std::max(kmax, 1)) || d_int.upload(ints, s) ||
                    d_items.upload(L.items, s) || d_src.upload(L.srcs, s) || d_dst.upload(L.dsts, s) || d_tgt.alloc((size_t)2 * nblk) ||
                    d_gemm.alloc((size_t)3 * nblk) || d_tab.alloc(nblk) || d_keep.upload(keep_list, s) || d_same.upload(same_list, s) ||
-                   d_pub.upload(pub_list, s) || d_is.upload(is_list, s) || d_cross.upload(cross_list, s);
-  if (bad) {
+                   d_pub.upload(O.pub, s) || d_is.upload(O.is, s) || d_cross.upload(O.cross, s);
+  auto nomem = [&]() {
     set_err(std::string(what) + ": device allocation failed (the nested path needs " + std::to_string((long long)(nbytes.large + nbytes.small)) +
             " bytes)");
     return DPGO_ERR;
-  }
+  };
+  if (bad) return nomem();
   // the tables of the blocks.  Workspace of block b inside its batch: A | Wk | M | B (later Z) | P (later G)
   std::vector<NestTarget> tgt(2 * (size_t)nblk);
   std::vector<GemmItem> gemm(3 * (size_t)nblk);  // [0, nblk) W = C B, [nblk, 2 nblk) P = B^T W, [2 nblk, 3 nblk) Z = W G
-  std::vector<NestBlock> tab(nblk);
+  std::vector<CovBlock> tab(nblk);
   std::vector<double *> pA(nblk), pWk(nblk), pM(nblk), pP(nblk);
   std::vector<int> order(nblk);
   for (int q = 0; q < nbatch; ++q) {
@@ -571,17 +395,12 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
       tab[b] = {W, d_int.p + nb_at[b], d_int.p + ipose_at[b], M, Pm, B, n, K};
     }
   }
-  double *Td = d_small.p, *E = Td + L3, *lam = E + L3, *gmax = lam + (size_t)9 * N, *stat = gmax + (size_t)na * gstride,
-         *keepd = stat + 4 * (size_t)(nblk + 1), *outd = keepd + nout;
-  SchurMarks marks;
   HIPC(hipMemcpyAsync(d_tgt.p, tgt.data(), sizeof(NestTarget) * tgt.size(), hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d_gemm.p, gemm.data(), sizeof(GemmItem) * gemm.size(), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(NestBlock) * tab.size(), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(Td, T, sizeof(double) * L3, hipMemcpyHostToDevice, s));
-  HIPC(hipMemsetAsync(keepd, 0, sizeof(double) * 2 * nout, s));
-  MARK(-1);
-  launch_cert_apply3(s, t->d_agents.p, d_int.p, na, max_n, Td, E, nullptr);
-  launch_cert_lambda3(s, t->d_agents.p, d_int.p, na, max_n, Td, E, lam, gmax);
+  HIPC(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(CovBlock) * tab.size(), hipMemcpyHostToDevice, s));
+  if (const int rc = F.begin(T, nblk + 1, num_pairs, true)) return rc > 0 ? nomem() : DPGO_ERR;
+  double *Td = F.Td, *lam = F.lam, *stat = F.stat, *keepd = F.keepd, *outd = F.outd;
+  SchurMarks &marks = F.marks;
   if (nS > 0) {
     HIPC(hipMemsetAsync(d_S.p, 0, sizeof(double) * SS, s));
     launch_cov_assemble_map(s, t->d_agents.p, d_items.p + L.lbeg[nblk], d_src.p, d_dst.p + L.lbeg[nblk], L.count(nblk), Td, lam, d_S.p, nS);
@@ -629,7 +448,7 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     MARK(2);
     flops_prod += gemm_flops(gemm.data() + b0, cnt) + gemm_flops(gemm.data() + nblk + b0, cnt);
     const int k0 = keep_beg[b0], nk = keep_beg[b1] - k0;  // (never empty: the diagonal blocks)
-    k_nest_keep<<<(unsigned)(((size_t)36 * nk + 255) / 256), 256, 0, s>>>(d_tab.p, d_keep.p + k0, nk, keepd);
+    launch_ext_keep(s, d_tab.p, d_keep.p + k0, nk, keepd);
     HIPC(hipGetLastError());
     MARK(4);
   }
@@ -643,8 +462,7 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     if (f > 0) { fail[0] = -1; fail[1] = P.sep[(f - 1) / 6]; fail[2] = f - 1; return 1; }
     if (launch_cov_logdet(s, d_S.p, nS, stat + 4 * nblk)) return DPGO_ERR;
     MARK(3);
-    if (!pub_list.empty())
-      k_nest_public<<<(unsigned)((36 * pub_list.size() + 255) / 256), 256, 0, s>>>(d_M.p, nS, d_pub.p, (int)pub_list.size(), outd);
+    launch_ext_public(s, d_M.p, nS, d_pub.p, (int)O.pub.size(), outd);
     HIPC(hipGetLastError());
     MARK(4);
   }
@@ -654,54 +472,26 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     const int b0 = bbeg[q], b1 = bbeg[q + 1], cnt = b1 - b0;
     int mk = 0, mld = 0;
     for (int b = b0; b < b1; ++b) { mk = std::max(mk, tab[b].K); mld = std::max(mld, tab[b].ld); }
-    if (mk > 0) k_nest_gather<<<dim3((unsigned)(((size_t)mk * mk + 255) / 256), cnt, 1), 256, 0, s>>>(d_tab.p, b0, d_M.p, nS);
+    launch_ext_gather(s, d_tab.p, b0, cnt, mk, d_M.p, nS);
     launch_dgemm_batched(s, false, d_gemm.p + 2 * nblk + b0, gemm.data() + 2 * nblk + b0, cnt, false);
     HIPC(hipGetLastError());
     MARK(2);
     flops_prod += gemm_flops(gemm.data() + 2 * nblk + b0, cnt);
-    k_nest_diag<<<dim3((unsigned)(((size_t)6 * mld + 255) / 256), cnt, 1), 256, 0, s>>>(d_tab.p, b0, keepd, outd);
-    const int s0 = same_beg[b0], ns = same_beg[b1] - s0;
-    if (ns > 0) k_nest_pair_same<<<(unsigned)(((size_t)36 * ns + 255) / 256), 256, 0, s>>>(d_tab.p, d_same.p + s0, ns, keepd, outd);
+    launch_ext_diag(s, d_tab.p, b0, cnt, mld, keepd, outd);
+    const int s0 = same_beg[b0];
+    launch_ext_pair_same(s, d_tab.p, d_same.p + s0, same_beg[b1] - s0, keepd, outd);
     HIPC(hipGetLastError());  // (the workspace serves the next batch: its launches are ordered behind these on the stream)
     MARK(4);
   }
-  if (!is_list.empty())
-    k_nest_pair_is<<<(unsigned)((36 * is_list.size() + 255) / 256), 256, 0, s>>>(d_tab.p, d_M.p, nS, d_is.p, (int)is_list.size(), outd);
-  // (kmax = 0: no block is coupled to the separator, the blocks across two of them are the zeros already there)
-  for (size_t c0 = 0; kmax > 0 && c0 < cross_list.size(); c0 += cross_chunk) {
-    const int cnt = (int)std::min<size_t>(cross_chunk, cross_list.size() - c0);
-    k_nest_cross_t<<<dim3((kmax + 255) / 256, cnt, 1), 256, 0, s>>>(d_tab.p, d_M.p, nS, d_cross.p + c0, kmax, d_t.p);
-    k_nest_cross_out<<<(unsigned)((36 * (size_t)cnt + 255) / 256), 256, 0, s>>>(d_tab.p, d_cross.p + c0, cnt, kmax, d_t.p, outd);
-  }
+  launch_ext_pair_is<RowList>(s, d_tab.p, d_M.p, nS, d_is.p, (int)O.is.size(), outd);
+  launch_ext_cross_pairs<RowList>(s, d_tab.p, d_M.p, nS, d_cross.p, O.cross.size(), kmax, d_t.p, cross_chunk, outd);
   HIPC(hipGetLastError());
   MARK(4);
-  // with an epilogue the blocks stay on the device: the statistics alone come back, the epilogue queues its own copies
-  std::vector<double> host(4 * (size_t)(nblk + 1) + (epi ? 0 : 2 * nout));
-  HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
-  if (epi && epi->run({Td, outd, outd + (size_t)36 * N, N, num_pairs, s})) {
-    (void)hipStreamSynchronize(s);  // (copies into this frame and into the epilogue may be queued)
-    return DPGO_ERR;
-  }
-  HIPC(hipStreamSynchronize(s));
-  double ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (size_t k = 1; k < marks.ev.size(); ++k) {
-    float v = 0.f;
-    if (marks.phase[k] >= 0 && hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) == hipSuccess) ms[marks.phase[k]] += v;
-  }
   // log det and pivots: the blocks in order, the separator last
-  double logdet = 0.0, mn = INFINITY, mx = 0.0;
-  for (int k = 0; k <= nblk; ++k) {
-    if (k == nblk && nS == 0) continue;
-    logdet += host[4 * k];
-    mn = std::fmin(mn, host[4 * k + 1]);
-    mx = std::fmax(mx, host[4 * k + 2]);
-  }
-  res->n = 6 * (N - 1);
-  res->logdet = logdet;
-  res->min_pivot = mn;
-  res->max_pivot = mx;
-  res->seconds_assemble = 1e-3 * ms[0];
-  res->seconds_invert = 1e-3 * (ms[1] + ms[2] + ms[3]);
+  std::vector<char> counted(nblk + 1, 1);
+  counted[nblk] = nS > 0;
+  if (F.finish(epi, res, cov_diag, cov_pairs, counted)) return DPGO_ERR;
+  const double *ms = F.ms;
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr,
@@ -711,10 +501,6 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
                  6 * (N - 1), nblk, 6 * P.largest_block(), nbatch, nS, P.promoted, 6 * P.largest_nb(),
                  nbytes.large + nbytes.small + 8.0 * (ws_need - nbytes.ws_min), ms[0], ms[1], flops_fact / (1e9 * std::max(ms[1], 1e-9)), ms[2],
                  flops_prod / (1e9 * std::max(ms[2], 1e-9)), ms[3], ms[4]);
-  if (epi) return DPGO_OK;
-  const double *o = host.data() + 4 * (size_t)(nblk + 1) + nout;
-  std::memcpy(cov_diag, o, sizeof(double) * 36 * (size_t)N);
-  if (num_pairs > 0) std::memcpy(cov_pairs, o + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
   return DPGO_OK;
 }
 
@@ -791,10 +577,9 @@ int dpgo_cert::marginal_covariances_nested_call(dpgo_team_t *t, const double *T,
   const int rc = covariance_nested_device(t, P, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail, epi);
   if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
   if (rc > 0) {
-    const std::string where = fail[0] < 0 ? "the Schur complement on the separator"
-                                          : "block " + std::to_string(fail[0]) + " of robot " + std::to_string(t->ag[P.blocks[fail[0]].robot]->id);
-    set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(fail[2]) + " of " + where + " (pose " + std::to_string(fail[1]) +
-            "): the Hessian is not positive definite at this T: not a minimum");
+    set_err(pivot_message(what, fail[2], fail[0] < 0 ? "the Schur complement on the separator"
+                                                     : "block " + std::to_string(fail[0]) + " of robot " + std::to_string(t->ag[P.blocks[fail[0]].robot]->id),
+                          fail[1]));
     return DPGO_ERR;
   }
   return rc;

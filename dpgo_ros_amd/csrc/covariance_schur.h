@@ -1,6 +1,7 @@
 // covariance_schur.h -- what the robot-wise Schur path (covariance_schur.hip) shares with the nested path
 // (covariance_nested.hip): the destination record of the assembly through a pose map, the tile of the fp64 product, the
-// partition into public and interior poses, the work lists and the phase marks.
+// partition into public and interior poses and the work lists.  The extraction kernels both paths launch are in
+// covariance_extract.h, the frame of a call (marks, head, tail) in covariance_frame.h.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -8,6 +9,7 @@
 
 #include "certify_internal.h"
 #include "covariance_block.h"
+#include "covariance_frame.h"
 
 namespace dpgo {
 
@@ -159,26 +161,5 @@ struct SchurItems {
   }
   int count(int list) const { return lbeg[list + 1] - lbeg[list]; }
 };
-
-// events: a mark per phase boundary; phase of the interval that ENDS at a mark: 0 assembly, 1 interior factorisations,
-// 2 products, 3 separator inverse, 4 extraction, -1 not counted
-struct SchurMarks {
-  std::vector<hipEvent_t> ev;
-  std::vector<int> phase;
-  std::vector<std::string> note;  // products: the shapes, for the DPGO_TIMING report
-  std::vector<double> flops;
-  ~SchurMarks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-  int mark(int ph, hipStream_t s) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) { set_err("marginal_covariances: event failed"); return DPGO_ERR; }
-    ev.push_back(e);
-    phase.push_back(ph);
-    note.emplace_back();
-    flops.push_back(0.0);
-    if (hipEventRecord(e, s) != hipSuccess) { set_err("marginal_covariances: event failed"); return DPGO_ERR; }
-    return 0;
-  }
-};
-#define MARK(ph) do { if (marks.mark(ph, s)) return DPGO_ERR; } while (0)
 
 }  // namespace dpgo_cert

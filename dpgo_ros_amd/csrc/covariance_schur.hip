@@ -15,6 +15,9 @@
 //     Sigma_st = the block of Sigma_SS                                                   (public, public)
 //     log det H_red = sum_a log det H_II,a + log det S_c      (summed on the host in robot order, the separator last).
 // Kept per robot: W_a, the diagonal blocks of C_a and its blocks of requested pairs, log det and pivots; C_a is dropped.
+// The blocks are read out by the extraction kernels of covariance_extract.h, the ones the nested path launches: a robot is a
+// set of their table whose separator indices are a window of one array 0, 1, 2, ... (iota), because a robot's part of the
+// separator is one contiguous range.  The head and the tail of the call are CovFrame's (covariance_frame.h).
 //
 // THE ROW-OWNER RULE.  A symmetric target (H_II,a, H_SS) is filled from the stored blocks S_ij with i <= j (team order)
 // alone: the thread forms H_ij and writes it and its transpose.  A stored block S_ij lives with the robot that holds pose
@@ -29,7 +32,7 @@
 #include <map>
 #include <tuple>
 
-#include "covariance_schur.h"
+#include "covariance_extract.h"
 
 namespace dpgo {
 
@@ -67,125 +70,6 @@ __global__ __launch_bounds__(256) void k_schur_mirror(double *__restrict__ A, in
   if (e >= (size_t)n * n) return;
   const int i = (int)(e % n), j = (int)(e / n);
   if (i > j) gp(A)[(size_t)i * n + j] = gp(A)[e];
-}
-
-// a list entry of the extraction kernels: output block blk, two indices inside the launch's sets, one flag
-struct SchurBlk {
-  int blk, i, j, f;
-};
-// an interior pose in a pair across sets: output block, robot and interior index of the left pose, then the right one
-// (robot b and interior index, or b < 0 and the separator index), f: store the transpose
-struct SchurCross {
-  int blk, a, li, b, lj, f;
-};
-// robot a on the device: W_a (6 |I_a| x K, ld = 6 |I_a|), K = 6 s_a, soff = 6 x its first separator index
-struct SchurRobot {
-  const double *W;
-  int ld, K, soff, pad_;
-};
-
-// keep[36 blk + 6 a + b] = C[6 i + a, 6 j + b] of the n x n column-major C, one thread per element
-__global__ __launch_bounds__(256) void k_schur_keep(const double *__restrict__ Cm, int n, const SchurBlk *__restrict__ list, int count,
-                                                    double *__restrict__ keep) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], i = gp(lp)[1], j = gp(lp)[2];
-  gp(keep)[(size_t)36 * blk + q] = gp(Cm)[((size_t)6 * j + b) * n + (size_t)6 * i + a];
-}
-
-// the diagonal blocks of the interior poses of one robot: X = C_ii + Z[i,:] W[i,:]^T, out = (X + X^T) / 2 (both operands of an
-// element and of its mirror are the same two numbers: bitwise symmetric).  Thread e: row r = e mod nrows of Z (pose r / 6,
-// a = r mod 6: consecutive threads read consecutive rows), b = e / nrows.  ipose: team pose of interior index li
-__global__ __launch_bounds__(256) void k_schur_diag(const double *__restrict__ Z, const double *__restrict__ W, int nrows, int K,
-                                                    const int *__restrict__ ipose, const double *__restrict__ keep,
-                                                    double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)6 * nrows) return;
-  const int r = (int)(e % nrows), b = (int)(e / nrows), li = r / 6, a = r - 6 * li;
-  const double sab = schur_row_dot(Z, nrows, r, W, nrows, 6 * li + b, K), sba = schur_row_dot(Z, nrows, 6 * li + b, W, nrows, r, K);
-  const size_t o = (size_t)36 * gp(ipose)[li];
-  gp(out)[o + 6 * a + b] = 0.5 * ((gp(keep)[o + 6 * a + b] + sab) + (gp(keep)[o + 6 * b + a] + sba));
-}
-
-// pairs of two interior poses of one robot: out = C_ij + Z[i,:] W[j,:]^T
-__global__ __launch_bounds__(256) void k_schur_pair_same(const double *__restrict__ Z, const double *__restrict__ W, int nrows, int K,
-                                                         const SchurBlk *__restrict__ list, int count, const double *__restrict__ keep,
-                                                         double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], i = gp(lp)[1], j = gp(lp)[2];
-  const size_t o = (size_t)36 * blk + q;
-  gp(out)[o] = gp(keep)[o] + schur_row_dot(Z, nrows, 6 * i + a, W, nrows, 6 * j + b, K);
-}
-
-// blocks of Sigma_SS (M, order n): f = 1 a diagonal block, symmetrised as k_cov_extract does; f = 0 the block (i, j)
-__global__ __launch_bounds__(256) void k_schur_public(const double *__restrict__ M, int n, const SchurBlk *__restrict__ list, int count,
-                                                      double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], i = gp(lp)[1], j = gp(lp)[2], f = gp(lp)[3];
-  const size_t oi = (size_t)6 * i, oj = (size_t)6 * j;
-  double v = gp(M)[(oj + b) * n + oi + a];
-  if (f) v = 0.5 * (v + gp(M)[(oi + a) * n + oi + b]);
-  gp(out)[(size_t)36 * blk + q] = v;
-}
-
-// interior pose i of robot a with public pose s: -W_a[i,:] Sigma_SS[s_a, s] (f: its transpose, the pair was (s, i))
-__global__ __launch_bounds__(256) void k_schur_pair_ip(const SchurRobot *__restrict__ robots, const double *__restrict__ M, int n,
-                                                       const SchurCross *__restrict__ list, int count, double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int q = (int)(e % 36), a = q / 6, b = q - 6 * a;
-  const int *lp = (const int *)(list + e / 36);
-  const int blk = gp(lp)[0], ra = gp(lp)[1], li = gp(lp)[2], s = gp(lp)[4], f = gp(lp)[5];
-  const SchurRobot R = robots[ra];
-  const double *col = M + ((size_t)6 * s + b) * n + R.soff;
-  double acc = 0.0;
-  for (int k = 0; k < R.K; ++k) acc = __builtin_fma(gp(R.W)[(size_t)k * R.ld + 6 * li + a], gp(col)[k], acc);
-  gp(out)[(size_t)36 * blk + (f ? 6 * b + a : 6 * a + b)] = -acc;
-}
-
-// interior poses of two different robots, first half: t[p][c][a] = sum_k W_a[6 li + a, k] Sigma_SS[s_a + k, s_b + c] for
-// the K_b columns c.  blockIdx.y: the pair of this chunk; a thread per column, the six rows at once (Sigma_SS is bitwise
-// symmetric: the element is read at [s_b + c, s_a + k], consecutive threads consecutive addresses)
-__global__ __launch_bounds__(256) void k_schur_cross_t(const SchurRobot *__restrict__ robots, const double *__restrict__ M, int n,
-                                                       const SchurCross *__restrict__ list, int kmax, double *__restrict__ tbuf) {
-  const int *lp = (const int *)(list + blockIdx.y);
-  const int ra = gp(lp)[1], li = gp(lp)[2], rb = gp(lp)[3];
-  const SchurRobot A = robots[ra], B = robots[rb];
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= B.K) return;
-  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const double *w = A.W + 6 * li, *sg = M + (size_t)A.soff * n + B.soff + c;
-  for (int k = 0; k < A.K; ++k) {
-    const double sv = gp(sg)[(size_t)k * n];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[a] = __builtin_fma(gp(w)[(size_t)k * A.ld + a], sv, acc[a]);
-  }
-  double *o = tbuf + ((size_t)blockIdx.y * kmax + c) * 6;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) gp(o)[a] = acc[a];
-}
-
-// second half: out[a][b] = sum_c t[p][c][a] W_b[6 lj + b, c], c in index order
-__global__ __launch_bounds__(256) void k_schur_cross_out(const SchurRobot *__restrict__ robots, const SchurCross *__restrict__ list, int count,
-                                                         int kmax, const double *__restrict__ tbuf, double *__restrict__ out) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (size_t)36 * count) return;
-  const int p = (int)(e / 36), q = (int)(e % 36), a = q / 6, b = q - 6 * a;
-  const int *lp = (const int *)(list + p);
-  const int blk = gp(lp)[0], rb = gp(lp)[3], lj = gp(lp)[4];
-  const SchurRobot B = robots[rb];
-  const double *t = tbuf + (size_t)p * kmax * 6 + a;
-  double acc = 0.0;
-  for (int c = 0; c < B.K; ++c) acc = __builtin_fma(gp(t)[(size_t)6 * c], gp(B.W)[(size_t)c * B.ld + 6 * lj + b], acc);
-  gp(out)[(size_t)36 * blk + q] = acc;
 }
 
 }  // namespace dpgo
@@ -238,18 +122,12 @@ void schur_partition(dpgo_team_t *t, int zero, SchurPartition &P) {
   P.nS = (int)P.sep.size();
 }
 
-// pairs between interiors of two robots handled by one launch pair: the scratch t (6 kmax doubles each) stays within 64 MB
-// and the pair index, which rides on gridDim.y, within its limit of 65 535
-static size_t schur_cross_chunk(size_t pairs, int kmax) {
-  if (pairs == 0) return 0;
-  return std::max<size_t>(1, std::min<size_t>({pairs, (size_t)65535, ((size_t)8 << 20) / ((size_t)6 * std::max(kmax, 1))}));
-}
-
 // the device bytes of the call.  The large buffers: three square ones of order M = max(6 max_a |I_a|, 6 |S|),
 // the separator, every kept W_a, one more of the largest W_a (B_a, later Z_a).  The small ones: T, T Q, Lambda, the
 // Gershgorin scratch, the factors' statistics, the kept and the output blocks (2 x 36 (N + P) doubles, P pairs), the scratch
-// of the pairs between two robots' interiors (every pair counted as one), the block and pair lists, the work list (40 bytes per
-// stored block of Q), the maps, and the Linv blocks of dense_spd_inverse.  nS: the separator of the WHOLE problem (a split
+// of the pairs between two robots' interiors (every pair counted as one), the block and pair lists (a CovBlk per pose and two
+// per pair, a CovCross per pair), the work list (40 bytes per stored block of Q), the maps and iota, the table of sets (a
+// CovBlock per robot and two per pair: a split team's rows), and the Linv blocks of dense_spd_inverse.  nS: the separator of the WHOLE problem (a split
 // team inverts it too); `who` names what sets M
 static double schur_bytes(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax, int num_pairs, std::string &who) {
   int big = -1, max_n = 0;
@@ -270,17 +148,17 @@ static double schur_bytes(dpgo_team_t *t, const SchurPartition &P, int nS, int k
                  : "the " + std::to_string(P.max_int) + " interior poses of robot " + std::to_string(t->ag[big]->id);
   const double N = P.N, np = num_pairs, A = P.na;
   const double small = 8.0 * (33.0 * N + A * ((max_n + 255) / 256) + 4.0 * (A + 1.0) + 72.0 * (N + np)) +
-                       8.0 * 6.0 * std::max(kmax, 1) * (double)schur_cross_chunk((size_t)num_pairs, kmax) + 16.0 * (N + np) + 24.0 * np +
-                       40.0 * (double)stored + 4.0 * (A + 1.0 + 2.0 * N) + 20.0 * (A + 2.0 * np) + 8.0 * 1024.0 * std::ceil(M / 32.0);
+                       8.0 * 6.0 * std::max(kmax, 1) * (double)cov_cross_chunk((size_t)num_pairs, kmax) + (double)sizeof(CovBlk) * (N + 2.0 * np) +
+                       (double)sizeof(CovCross) * np + 40.0 * (double)stored + 4.0 * (A + 1.0 + 2.0 * N + nS) +
+                       (double)sizeof(CovBlock) * (A + 2.0 * np) + 8.0 * 1024.0 * std::ceil(M / 32.0);
   return 8.0 * (3.0 * M * M + ms * ms + w_all + w_max) + small;
 }
 
 static int schur_fits(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax, int num_pairs, const char *what, std::string &msg) {
   std::string who;
   const double need = schur_bytes(t, P, nS, kmax, num_pairs, who);
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { msg = std::string(what) + ": hipMemGetInfo failed"; return -1; }
-  const double avail = (double)free_b + (double)pool_held(t->device);
+  double avail = 0.0;
+  if (!cov_device_avail(t, &avail)) { msg = std::string(what) + ": hipMemGetInfo failed"; return -1; }
   if (need <= avail) return 0;
   char buf[400];
   std::snprintf(buf, sizeof buf,
@@ -300,7 +178,8 @@ struct SchurDev {
   DevBuf<CovItem> items;
   DevBuf<CovSrc> src;
   DevBuf<CovDst> dst;
-  DevBuf<SchurBlk> blk;
+  DevBuf<CovBlk> blk;    // the list of the launch at hand
+  DevBuf<CovBlock> tab;  // the robots as sets of the extraction kernels (a split team: behind them the gathered rows)
   const SchurItems *L = nullptr;
   void assemble(int list, double *H, int ld) const {
     const int cnt = L->count(list);
@@ -312,10 +191,10 @@ struct SchurDev {
 
 // One robot: H_II and B assembled (lists `lii`, `lb`), C = H_II^-1 into D.M, W = C B, Sd -= B^T W (Sd: the
 // robot's diagonal block of the separator, leading dimension lds), the statistics of the factor into stat[0 .. 2], the blocks
-// of C named by `keep` into keepd.  DPGO_OK, DPGO_ERR (message set), or row + 1 of a non-positive pivot.  A single team and
+// of C named by `keep` (its entries name the robot's set of D.tab) into keepd.  DPGO_OK, DPGO_ERR (message set), or row + 1 of a non-positive pivot.  A single team and
 // every participant of a split team come through here with the same shapes: the same bits.
 static int schur_robot_step(SchurDev &D, SchurMarks &marks, int robot_id, int lii, int lb, int ni, int K, double *W, double *Sd, int lds,
-                            const std::vector<SchurBlk> &keep, double *keepd, double *stat) {
+                            const std::vector<CovBlk> &keep, double *keepd, double *stat) {
   hipStream_t s = D.s;
   HIPC(hipMemsetAsync(D.A.p, 0, sizeof(double) * (size_t)ni * ni, s));
   D.assemble(lii, D.A.p, ni);
@@ -339,17 +218,17 @@ static int schur_robot_step(SchurDev &D, SchurMarks &marks, int robot_id, int li
                       std::to_string(ni) + ") and B^T W (" + std::to_string(K) + " x " + std::to_string(K) + " x " + std::to_string(ni) + ")";
   marks.flops.back() = 2.0 * ni * (double)ni * K + 2.0 * K * (double)K * ni;
   // (keep is never empty: the diagonal blocks)
-  HIPC(hipMemcpyAsync(D.blk.p, keep.data(), sizeof(SchurBlk) * keep.size(), hipMemcpyHostToDevice, s));
-  k_schur_keep<<<(unsigned)((36 * keep.size() + 255) / 256), 256, 0, s>>>(D.M.p, ni, D.blk.p, (int)keep.size(), keepd);
+  HIPC(hipMemcpyAsync(D.blk.p, keep.data(), sizeof(CovBlk) * keep.size(), hipMemcpyHostToDevice, s));
+  launch_ext_keep(s, D.tab.p, D.blk.p, (int)keep.size(), keepd);
   HIPC(hipGetLastError());
   MARK(4);
   return DPGO_OK;
 }
 
-// The same robot once Sigma_SS (order nS) is known: Z = W Sigma_SS[s, s] into D.B, the diagonal blocks of its interior
-// poses and its pairs of two interior poses
-static int schur_robot_blocks(SchurDev &D, SchurMarks &marks, int robot_id, int ni, int K, const double *W, const double *Sss, int nS,
-                              const int *ipose_d, const std::vector<SchurBlk> &same, const double *keepd, double *outd) {
+// The same robot (set `set` of D.tab) once Sigma_SS (order nS) is known: Z = W Sigma_SS[s, s] into D.B, in place on the
+// robot's diagonal block Sss of Sigma_SS; the diagonal blocks of its interior poses and its pairs of two interior poses
+static int schur_robot_blocks(SchurDev &D, SchurMarks &marks, int robot_id, int set, int ni, int K, const double *W, const double *Sss, int nS,
+                              const std::vector<CovBlk> &same, const double *keepd, double *outd) {
   hipStream_t s = D.s;
   launch_dgemm(s, false, W, ni, Sss, nS, D.B.p, ni, ni, K, K, false);
   HIPC(hipGetLastError());
@@ -357,38 +236,42 @@ static int schur_robot_blocks(SchurDev &D, SchurMarks &marks, int robot_id, int 
   marks.note.back() = "robot " + std::to_string(robot_id) + ": Z = W Sigma_SS[s, s] (" + std::to_string(ni) + " x " + std::to_string(K) + " x " +
                       std::to_string(K) + ")";
   marks.flops.back() = 2.0 * ni * (double)K * K;
-  k_schur_diag<<<(unsigned)(((size_t)6 * ni + 255) / 256), 256, 0, s>>>(D.B.p, W, ni, K, ipose_d, keepd, outd);
+  launch_ext_diag(s, D.tab.p, set, 1, ni, keepd, outd);
   if (!same.empty()) {
-    HIPC(hipMemcpyAsync(D.blk.p, same.data(), sizeof(SchurBlk) * same.size(), hipMemcpyHostToDevice, s));
-    k_schur_pair_same<<<(unsigned)((36 * same.size() + 255) / 256), 256, 0, s>>>(D.B.p, W, ni, K, D.blk.p, (int)same.size(), keepd, outd);
+    HIPC(hipMemcpyAsync(D.blk.p, same.data(), sizeof(CovBlk) * same.size(), hipMemcpyHostToDevice, s));
+    launch_ext_pair_same(s, D.tab.p, D.blk.p, (int)same.size(), keepd, outd);
   }
   HIPC(hipGetLastError());  // (D.blk and D.B serve the next robot: its copy and its product are ordered behind these on the stream)
   MARK(4);
   return DPGO_OK;
 }
 
-// pairs of interior poses of two robots: list entries name rows of the robot table (k_schur_cross_t / _out), in chunks
-static int schur_cross_pairs(hipStream_t s, const SchurRobot *rob_d, const double *Sss, int nS, const std::vector<SchurCross> &list,
-                             SchurCross *list_d, int kmax, double *tbuf, size_t chunk, double *outd) {
+// pairs of interior poses of two robots: list entries name sets of the table, in chunks
+static int schur_cross_pairs(hipStream_t s, const CovBlock *tab_d, const double *Sss, int nS, const std::vector<CovCross> &list, CovCross *list_d,
+                             int kmax, double *tbuf, size_t chunk, double *outd) {
   if (list.empty()) return DPGO_OK;
-  HIPC(hipMemcpyAsync(list_d, list.data(), sizeof(SchurCross) * list.size(), hipMemcpyHostToDevice, s));
-  for (size_t c0 = 0; c0 < list.size(); c0 += chunk) {
-    const int cnt = (int)std::min<size_t>(chunk, list.size() - c0);
-    k_schur_cross_t<<<dim3((kmax + 255) / 256, cnt, 1), 256, 0, s>>>(rob_d, Sss, nS, list_d + c0, kmax, tbuf);
-    k_schur_cross_out<<<(unsigned)((36 * (size_t)cnt + 255) / 256), 256, 0, s>>>(rob_d, list_d + c0, cnt, kmax, tbuf, outd);
-  }
+  HIPC(hipMemcpyAsync(list_d, list.data(), sizeof(CovCross) * list.size(), hipMemcpyHostToDevice, s));
+  launch_ext_cross_pairs<RowRun>(s, tab_d, Sss, nS, list_d, list.size(), kmax, tbuf, chunk, outd);
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
-static void schur_report(const SchurMarks &marks, double ms[5]) {
+// blocks of Sigma_SS (M, order nS) and pairs of an interior with a public pose, behind the separator's inverse
+static int schur_listed(SchurDev &D, int nS, const std::vector<CovBlk> &list, CovBlk *list_d, bool pub, double *outd) {
+  if (list.empty()) return DPGO_OK;
+  HIPC(hipMemcpyAsync(list_d, list.data(), sizeof(CovBlk) * list.size(), hipMemcpyHostToDevice, D.s));
+  if (pub) launch_ext_public(D.s, D.M.p, nS, list_d, (int)list.size(), outd);
+  else launch_ext_pair_is<RowRun>(D.s, D.tab.p, D.M.p, nS, list_d, (int)list.size(), outd);
+  HIPC(hipGetLastError());
+  return DPGO_OK;
+}
+
+// the products' lines of the DPGO_TIMING report (on a drained stream)
+static void schur_report(const SchurMarks &marks) {
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
-  for (int k = 0; k < 5; ++k) ms[k] = 0.0;
-  for (size_t k = 1; k < marks.ev.size(); ++k) {
+  for (size_t k = 1; timing && k < marks.ev.size(); ++k) {
     float v = 0.f;
-    if (hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) != hipSuccess) continue;
-    if (marks.phase[k] >= 0) ms[marks.phase[k]] += v;
-    if (timing && marks.flops[k] > 0.0)
+    if (marks.flops[k] > 0.0 && hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) == hipSuccess)
       std::fprintf(stderr, "marginal_covariances (Schur): products, %s: %.3f ms, %.2f TFLOP/s\n", marks.note[k].c_str(), v,
                    marks.flops[k] / (1e9 * v));
   }
@@ -405,11 +288,8 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
   SchurPartition P;
   schur_partition(t, 0, P);
   const int na = P.na, N = P.N, nS = 6 * P.nS;
-  int max_n = 0, kmax = 0;
-  for (int k = 0; k < na; ++k) {
-    max_n = std::max(max_n, t->ag[k]->n);
-    kmax = std::max(kmax, 6 * (P.sep_off[k + 1] - P.sep_off[k]));
-  }
+  int kmax = 0;
+  for (int k = 0; k < na; ++k) kmax = std::max(kmax, 6 * (P.sep_off[k + 1] - P.sep_off[k]));
   {
     std::string msg;
     if (schur_fits(t, P, P.nS, kmax, num_pairs, what, msg)) { set_err(msg); return DPGO_ERR; }
@@ -420,7 +300,6 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
   SchurItems L;
   auto classify = [&](int bi, int bj, int agent, int idx) -> int {
     if (bi == 0 || bj == 0) return 0;
-    if (bi < 0 || bi >= N || bj >= N) return -1;
     const bool pi = P.pub[bi], pj = P.pub[bj];
     if (pi && pj) { if (bi <= bj) L.add(2 * na, bi, bj, agent, idx, P.pos[bi], P.pos[bj], CD_MIRROR); }
     else if (!pi && !pj) {
@@ -432,93 +311,56 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
     }
     return 0;
   };
-  for (int k = 0; k < na; ++k) {
-    const Agent &a = *t->ag[k];
-    for (int j = 0; j < a.n; ++j)
-      for (int p = a.rowptr[j]; p < a.rowptr[j + 1]; ++p)
-        if (classify(P.offs[k] + a.col[p], P.offs[k] + j, k, p)) { set_err(std::string(what) + ": a stored block lies outside the team"); return DPGO_ERR; }
-    for (size_t e = 0; e < a.se_host.size(); ++e) {
-      const SharedEdgeDev &se = a.se_host[e];
-      if (se.src_agent_local < 0 || se.src_agent_local >= na ||
-          classify(P.offs[se.src_agent_local] + se.src_frame, P.offs[k] + se.lpose, k, ~(int)e)) {
-        set_err(std::string(what) + ": a stored block lies outside the team");
-        return DPGO_ERR;
-      }
-    }
-  }
+  if (cov_for_each_stored_block(t, P.offs, classify)) { set_err(std::string(what) + ": a stored block lies outside the team"); return DPGO_ERR; }
   L.finish(2 * na + 1);
-  // ---- the outputs asked for, by case.  Block numbers: [0, N) the diagonal blocks, N + k pair k.
-  std::vector<std::vector<SchurBlk>> keep_list(na), same_list(na);
-  std::vector<SchurBlk> pub_list;
-  std::vector<SchurCross> ip_list, cross_list;
-  for (int g = 1; g < N; ++g) {
-    if (P.pub[g]) pub_list.push_back({g, P.pos[g], P.pos[g], 1});
-    else keep_list[P.robot_of[g]].push_back({g, P.pos[g], P.pos[g], 0});
-  }
-  for (int k = 0; k < num_pairs; ++k) {
-    const int a = pairs[2 * k], b = pairs[2 * k + 1], blk = N + k;
-    if (a == 0 || b == 0) continue;  // zeros
-    const int ra = P.robot_of[a], rb = P.robot_of[b];
-    if (P.pub[a] && P.pub[b]) pub_list.push_back({blk, P.pos[a], P.pos[b], 0});
-    else if (!P.pub[a] && !P.pub[b]) {
-      if (ra == rb) { keep_list[ra].push_back({blk, P.pos[a], P.pos[b], 0}); same_list[ra].push_back({blk, P.pos[a], P.pos[b], 0}); }
-      else cross_list.push_back({blk, ra, P.pos[a], rb, P.pos[b], 0});
-    } else if (!P.pub[a]) ip_list.push_back({blk, ra, P.pos[a], -1, P.pos[b], 0});
-    else ip_list.push_back({blk, rb, P.pos[b], -1, P.pos[a], 1});
-  }
+  // ---- the outputs asked for, by case: a robot's interior is a set, the public poses the separator
+  CovOutputs O;
+  cov_classify_outputs(N, na, pairs, num_pairs, [&](int g) { return P.pub[g] ? -1 : P.robot_of[g]; }, P.pos, O);
   // ---- device storage
   const int M = std::max(6 * P.max_int, nS);
-  const size_t MM = (size_t)M * M, L3 = (size_t)12 * N, nout = (size_t)36 * (N + num_pairs);
+  const size_t MM = (size_t)M * M;
   size_t w_max = 0;
   for (int k = 0; k < na; ++k) w_max = std::max(w_max, (size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k]));
   // scratch of the pairs between interiors of two robots: at most 64 MB at a time
-  const size_t cross_chunk = schur_cross_chunk(cross_list.size(), kmax);
+  const size_t cross_chunk = cov_cross_chunk(O.cross.size(), kmax);
+  CovFrame F(t);
   SchurDev D;
-  DevBuf<double> d_S, d_small, d_t;
+  DevBuf<double> d_S, d_t;
   std::vector<DevBuf<double>> d_W(na);
   DevBuf<int> d_int;
-  DevBuf<SchurCross> d_cross;
-  DevBuf<SchurRobot> d_rob;
-  const int gstride = (max_n + 255) / 256;
-  // d_small: T, E = T Q, Lambda, the Gershgorin scratch of k_cert_lambda, [logdet, min, max] per factor, the kept blocks of the
-  // C_a, the output blocks
-  const size_t small = 2 * L3 + (size_t)9 * N + (size_t)na * gstride + 4 * (size_t)(na + 1) + 2 * nout;
-  size_t nblk = pub_list.size();
-  for (int k = 0; k < na; ++k) nblk = std::max(nblk, keep_list[k].size() + same_list[k].size());
-  bool bad = D.A.alloc(MM) || D.Wk.alloc(MM) || D.M.alloc(MM) || d_S.alloc((size_t)nS * nS) || D.B.alloc(w_max) || d_small.alloc(small) ||
-             d_int.alloc((size_t)na + 1 + (size_t)N) || D.items.upload(L.items, t->stream) || D.src.upload(L.srcs, t->stream) ||
-             D.dst.upload(L.dsts, t->stream) || D.blk.alloc(nblk) || d_cross.alloc(std::max(ip_list.size(), cross_list.size())) ||
-             d_rob.alloc(na) || d_t.alloc(cross_chunk * 6 * std::max(kmax, 1));
+  DevBuf<CovBlk> d_is;
+  DevBuf<CovCross> d_cross;
+  hipStream_t s = t->stream;
+  size_t nblk = O.pub.size();
+  for (int k = 0; k < na; ++k) nblk = std::max(nblk, O.keep[k].size() + O.same[k].size());
+  // d_int: the team pose of every interior index (robot after robot), then iota = 0, 1, ..., |S| - 1
+  std::vector<int> ints, ipose_off(na + 1, 0);
+  for (int k = 0; k < na; ++k) {
+    ints.insert(ints.end(), P.interior[k].begin(), P.interior[k].end());
+    ipose_off[k + 1] = (int)ints.size();
+  }
+  for (int q = 0; q < P.nS; ++q) ints.push_back(q);
+  bool bad = D.A.alloc(MM) || D.Wk.alloc(MM) || D.M.alloc(MM) || d_S.alloc((size_t)nS * nS) || D.B.alloc(w_max) || d_int.upload(ints, s) ||
+             D.items.upload(L.items, s) || D.src.upload(L.srcs, s) || D.dst.upload(L.dsts, s) || D.blk.alloc(nblk) || d_is.alloc(O.is.size()) ||
+             d_cross.alloc(O.cross.size()) || D.tab.alloc(na) || d_t.alloc(cross_chunk * 6 * std::max(kmax, 1));
   for (int k = 0; k < na && !bad; ++k) bad = d_W[k].alloc((size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k])) != 0;
-  if (bad) {
+  auto nomem = [&]() {
     std::string who;
     set_err(std::string(what) + ": device allocation failed (the Schur path needs " +
             std::to_string((long long)schur_bytes(t, P, P.nS, kmax, num_pairs, who)) + " bytes)");
     return DPGO_ERR;
-  }
-  double *Td = d_small.p, *E = Td + L3, *lam = E + L3, *gmax = lam + (size_t)9 * N, *stat = gmax + (size_t)na * gstride,
-         *keepd = stat + 4 * (size_t)(na + 1), *outd = keepd + nout;
-  int *off = d_int.p, *ipose_d = off + na + 1;
-  hipStream_t s = t->stream;
-  D.s = s; D.agents = t->d_agents.p; D.Td = Td; D.lam = lam; D.L = &L;
-  SchurMarks marks;
-  std::vector<int> ipose_h;
-  std::vector<int> ipose_off(na + 1, 0);
-  for (int k = 0; k < na; ++k) {
-    ipose_h.insert(ipose_h.end(), P.interior[k].begin(), P.interior[k].end());
-    ipose_off[k + 1] = (int)ipose_h.size();
-  }
-  std::vector<SchurRobot> rob(na);
+  };
+  if (bad) return nomem();
+  // the robots as sets: M = C_a during the robot's step, Z = Z_a during its extraction, nb a window of iota
+  std::vector<CovBlock> rob(na);
+  const int *iota_d = d_int.p + ipose_off[na];
   for (int k = 0; k < na; ++k)
-    rob[k] = {d_W[k].p, 6 * (int)P.interior[k].size(), 6 * (P.sep_off[k + 1] - P.sep_off[k]), 6 * P.sep_off[k], 0};
-  HIPC(hipMemcpyAsync(off, P.offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, s));
-  if (!ipose_h.empty()) HIPC(hipMemcpyAsync(ipose_d, ipose_h.data(), sizeof(int) * ipose_h.size(), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_rob.p, rob.data(), sizeof(SchurRobot) * na, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(Td, T, sizeof(double) * L3, hipMemcpyHostToDevice, s));
-  HIPC(hipMemsetAsync(keepd, 0, sizeof(double) * 2 * nout, s));
-  MARK(-1);
-  launch_cert_apply3(s, t->d_agents.p, off, na, max_n, Td, E, nullptr);
-  launch_cert_lambda3(s, t->d_agents.p, off, na, max_n, Td, E, lam, gmax);
+    rob[k] = {d_W[k].p, iota_d + P.sep_off[k], d_int.p + ipose_off[k], D.M.p, nullptr, D.B.p, 6 * (int)P.interior[k].size(),
+              6 * (P.sep_off[k + 1] - P.sep_off[k])};
+  HIPC(hipMemcpyAsync(D.tab.p, rob.data(), sizeof(CovBlock) * na, hipMemcpyHostToDevice, s));
+  if (const int rc = F.begin(T, na + 1, num_pairs, true)) return rc > 0 ? nomem() : DPGO_ERR;
+  D.s = s; D.agents = t->d_agents.p; D.Td = F.Td; D.lam = F.lam; D.L = &L;
+  SchurMarks &marks = F.marks;
   if (nS > 0) {
     HIPC(hipMemsetAsync(d_S.p, 0, sizeof(double) * (size_t)nS * nS, s));
     D.assemble(2 * na, d_S.p, nS);
@@ -526,79 +368,49 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
   HIPC(hipGetLastError());
   MARK(0);
   // ---- the robots, one after another: the three square buffers and B serve each in turn
+  std::vector<char> counted(na + 1, 0);
   for (int k = 0; k < na; ++k) {
     const int ni = rob[k].ld;
     if (ni == 0) continue;
-    const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_S.p + (size_t)rob[k].soff * nS + rob[k].soff, nS,
-                                   keep_list[k], keepd, stat + 4 * k);
+    const size_t soff = (size_t)6 * P.sep_off[k];
+    const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_S.p + soff * nS + soff, nS, O.keep[k], F.keepd,
+                                   F.stat + 4 * k);
     if (f < 0) return DPGO_ERR;
     if (f > 0) { fail[0] = k; fail[1] = P.interior[k][(f - 1) / 6]; fail[2] = f - 1; return 1; }
+    counted[k] = 1;
   }
   // ---- the separator
   if (nS > 0) {
-    k_schur_mirror<<<(unsigned)(((size_t)nS * nS + 255) / 256), 256, 0, s>>>(d_S.p, nS);
+    launch_schur_mirror(s, d_S.p, nS);
     HIPC(hipGetLastError());
     const int f = dense_spd_inverse(s, d_S.p, D.Wk.p, D.M.p, nS);
     HIPC(hipGetLastError());
     if (f < 0) { set_err(std::string(what) + ": scratch allocation of the inverse failed"); return DPGO_ERR; }
     if (f > 0) { fail[0] = -1; fail[1] = P.sep[(f - 1) / 6]; fail[2] = f - 1; return 1; }
-    if (launch_cov_logdet(s, d_S.p, nS, stat + 4 * na)) return DPGO_ERR;
+    if (launch_cov_logdet(s, d_S.p, nS, F.stat + 4 * na)) return DPGO_ERR;
+    counted[na] = 1;
     MARK(3);
-    if (!pub_list.empty()) {
-      HIPC(hipMemcpyAsync(D.blk.p, pub_list.data(), sizeof(SchurBlk) * pub_list.size(), hipMemcpyHostToDevice, s));
-      k_schur_public<<<(unsigned)((36 * pub_list.size() + 255) / 256), 256, 0, s>>>(D.M.p, nS, D.blk.p, (int)pub_list.size(), outd);
-      HIPC(hipGetLastError());
-    }
+    if (schur_listed(D, nS, O.pub, D.blk.p, true, F.outd)) return DPGO_ERR;
     MARK(4);
   }
   // ---- the interior blocks
   for (int k = 0; k < na; ++k) {
     if (rob[k].ld == 0) continue;
-    if (schur_robot_blocks(D, marks, t->ag[k]->id, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)rob[k].soff * nS + rob[k].soff, nS,
-                           ipose_d + ipose_off[k], same_list[k], keepd, outd))
+    const size_t soff = (size_t)6 * P.sep_off[k];
+    if (schur_robot_blocks(D, marks, t->ag[k]->id, k, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + soff * nS + soff, nS, O.same[k], F.keepd, F.outd))
       return DPGO_ERR;
   }
-  if (!ip_list.empty()) {
-    HIPC(hipMemcpyAsync(d_cross.p, ip_list.data(), sizeof(SchurCross) * ip_list.size(), hipMemcpyHostToDevice, s));
-    k_schur_pair_ip<<<(unsigned)((36 * ip_list.size() + 255) / 256), 256, 0, s>>>(d_rob.p, D.M.p, nS, d_cross.p, (int)ip_list.size(), outd);
-    HIPC(hipGetLastError());
-  }
-  if (schur_cross_pairs(s, d_rob.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
+  if (schur_listed(D, nS, O.is, d_is.p, false, F.outd)) return DPGO_ERR;
+  if (schur_cross_pairs(s, D.tab.p, D.M.p, nS, O.cross, d_cross.p, kmax, d_t.p, cross_chunk, F.outd)) return DPGO_ERR;
   MARK(4);
-  // with an epilogue the blocks stay on the device: the statistics alone come back, the epilogue queues its own copies
-  std::vector<double> host(4 * (size_t)(na + 1) + (epi ? 0 : 2 * nout));
-  HIPC(hipMemcpyAsync(host.data(), stat, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
-  if (epi && epi->run({Td, outd, outd + (size_t)36 * N, N, num_pairs, s})) {
-    (void)hipStreamSynchronize(s);  // (copies into this frame and into the epilogue may be queued)
-    return DPGO_ERR;
-  }
-  HIPC(hipStreamSynchronize(s));
-  double ms[5];
-  schur_report(marks, ms);
-  // log det and pivots: the robots in order, the separator last
-  double logdet = 0.0, mn = INFINITY, mx = 0.0;
-  for (int k = 0; k <= na; ++k) {
-    if (k < na ? rob[k].ld == 0 : nS == 0) continue;
-    logdet += host[4 * k];
-    mn = std::fmin(mn, host[4 * k + 1]);
-    mx = std::fmax(mx, host[4 * k + 2]);
-  }
-  res->n = 6 * (N - 1);
-  res->logdet = logdet;
-  res->min_pivot = mn;
-  res->max_pivot = mx;
-  res->seconds_assemble = 1e-3 * ms[0];
-  res->seconds_invert = 1e-3 * (ms[1] + ms[2] + ms[3]);
+  if (F.finish(epi, res, cov_diag, cov_pairs, counted)) return DPGO_ERR;
+  schur_report(marks);
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr,
                  "marginal_covariances (Schur): n %d, separator %d, largest interior %d, %zu blocks, assemble %.3f ms, factorisations %.3f ms, "
                  "products %.3f ms, separator inverse %.3f ms, extract %.3f ms\n",
-                 6 * (N - 1), nS, 6 * P.max_int, L.items.size(), ms[0], ms[1], ms[2], ms[3], ms[4]);
-  if (epi) return DPGO_OK;
-  const double *o = host.data() + 4 * (size_t)(na + 1) + nout;
-  std::memcpy(cov_diag, o, sizeof(double) * 36 * (size_t)N);
-  if (num_pairs > 0) std::memcpy(cov_pairs, o + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
+                 6 * (N - 1), nS, 6 * P.max_int, L.items.size(), F.ms[0], F.ms[1], F.ms[2], F.ms[3], F.ms[4]);
   return DPGO_OK;
 }
 
@@ -629,28 +441,6 @@ double pair_hash(const int *pairs, int num_pairs) {
   return (double)(h & ((1ull << 52) - 1));
 }
 
-// "" or why pose g of T (12 doubles each, R column-major first) is not in SE(3)
-std::string se3_defect(const double *T, int N) {
-  for (int g = 0; g < N; ++g) {
-    const double *R = T + (size_t)12 * g;
-    double orth = 0.0;
-    for (int p = 0; p < 3; ++p)
-      for (int q = 0; q < 3; ++q) {
-        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
-        orth = std::max(orth, std::fabs(d));
-      }
-    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
-    bool finite = true;
-    for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(R[k]);
-    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "pose %d of T (team order) is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", g, orth, det);
-      return buf;
-    }
-  }
-  return "";
-}
-
 enum { XF_OK = 0, XF_PIVOT = 1, XF_MEMORY = 2, XF_LOCAL = 3 };
 
 }  // namespace
@@ -665,7 +455,13 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   else if (t) {
     int n = 0;
     for (auto &a : t->ag) n += a->n;
-    argerr = se3_defect(T, n);
+    double orth = 0.0, det = 0.0;
+    const int g = se3_defect(T, n, &orth, &det);
+    if (g >= 0) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "pose %d of T (team order) is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", g, orth, det);
+      argerr = buf;
+    }
   }
   Across x;
   if (x.begin(t, tr, owner, what, 3, 3, flags, (double)num_pairs, argerr.empty() ? pair_hash(pairs, num_pairs) : 0.0, 0,
@@ -792,17 +588,17 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   auto local_pose = [&](int g) { return P.offs[t->id2local.at(grobot[g])] + gframe[g]; };
   auto here = [&](int g) { return x.robot_holder[grobot[g]] == x.rank; };
   // pairs of two interior poses of one local robot must be known before the robot's step (its blocks of C_a are kept)
-  std::vector<std::vector<SchurBlk>> keep_list(na), same_list(na);
+  std::vector<std::vector<CovBlk>> keep_list(na), same_list(na);
   for (int k = 0; k < na; ++k)
-    for (int g : P.interior[k]) keep_list[k].push_back({g, P.pos[g], P.pos[g], 0});
+    for (int g : P.interior[k]) keep_list[k].push_back({g, k, P.pos[g], P.pos[g], 0, 0});
   for (int k = 0; k < num_pairs; ++k) {
     const int a = pairs[2 * k], b = pairs[2 * k + 1];
     if (a == 0 || b == 0 || grobot[a] != grobot[b] || !here(a)) continue;
     const int la = local_pose(a), lb = local_pose(b);
     if (P.pub[la] || P.pub[lb]) continue;
     const int lk = t->id2local.at(grobot[a]);
-    keep_list[lk].push_back({N + k, P.pos[la], P.pos[lb], 0});
-    same_list[lk].push_back({N + k, P.pos[la], P.pos[lb], 0});
+    keep_list[lk].push_back({N + k, lk, P.pos[la], P.pos[lb], 0, 0});
+    same_list[lk].push_back({N + k, lk, P.pos[la], P.pos[lb], 0, 0});
   }
 
   // ---- device storage (as the single team's, the separator that of the whole problem)
@@ -823,27 +619,31 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   DevBuf<double> d_S, d_small, d_t, d_T, d_D, d_X, d_rows;
   std::vector<DevBuf<double>> d_W(na);
   DevBuf<int> d_int;
-  DevBuf<SchurCross> d_cross;
-  DevBuf<SchurRobot> d_rob;
+  DevBuf<CovBlk> d_is;
+  DevBuf<CovCross> d_cross;
   size_t ncrosspairs = 0;
   for (int k = 0; k < num_pairs; ++k) ncrosspairs += (pairs[2 * k] && pairs[2 * k + 1] && grobot[pairs[2 * k]] != grobot[pairs[2 * k + 1]]);
-  const size_t cross_chunk = schur_cross_chunk(ncrosspairs, kmax);
+  const size_t cross_chunk = cov_cross_chunk(ncrosspairs, kmax);
   const size_t small = 4 * (size_t)(na + 1) + 2 * nout;
   size_t nblk = (size_t)N + num_pairs;
   SchurMarks marks;
-  std::vector<int> ipose_h, ipose_off(na + 1, 0);
+  // d_int: the team pose of every interior index (robot after robot), then iota = 0, 1, ..., |S| - 1 over the GLOBAL separator
+  std::vector<int> ints, ipose_off(na + 1, 0), soff(na, 0);
   for (int k = 0; k < na; ++k) {
-    ipose_h.insert(ipose_h.end(), P.interior[k].begin(), P.interior[k].end());
-    ipose_off[k + 1] = (int)ipose_h.size();
+    ints.insert(ints.end(), P.interior[k].begin(), P.interior[k].end());
+    ipose_off[k + 1] = (int)ints.size();
+    soff[k] = 6 * gsoff[t->ag[k]->id];
   }
+  for (int q = 0; q < nSp; ++q) ints.push_back(q);
+  const int *iota_d = nullptr;
   double *stat = nullptr, *keepd = nullptr, *outd = nullptr;
-  std::vector<SchurRobot> rob(na);
+  std::vector<CovBlock> rob(na);
   std::vector<double> hD, hX, hstat;
   // phase 1 on the device: this participant's robots.  DPGO_ERR: a local failure (message set)
   auto phase1 = [&]() -> int {
     bool bad = D.A.alloc(MM) || D.Wk.alloc(MM) || D.M.alloc(MM) || d_S.alloc((size_t)nS * nS) || D.B.alloc(w_max) || d_small.alloc(small) ||
-               d_int.alloc((size_t)N + 1) || D.items.upload(L.items, s) || D.src.upload(L.srcs, s) || D.dst.upload(L.dsts, s) ||
-               D.blk.alloc(nblk) || d_cross.alloc(std::max<size_t>(num_pairs, 1)) || d_rob.alloc((size_t)na + 2 * ncrosspairs) ||
+               d_int.upload(ints, s) || D.items.upload(L.items, s) || D.src.upload(L.srcs, s) || D.dst.upload(L.dsts, s) ||
+               D.blk.alloc(nblk) || d_is.alloc((size_t)num_pairs) || d_cross.alloc(ncrosspairs) || D.tab.alloc((size_t)na + 2 * ncrosspairs) ||
                d_t.alloc(cross_chunk * 6 * std::max(kmax, 1)) || d_T.alloc((size_t)12 * (N + halo_slots)) || d_D.alloc(d_all) ||
                d_X.alloc(36 * xb.size());
     for (int k = 0; k < na && !bad; ++k) bad = d_W[k].alloc((size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k])) != 0;
@@ -852,9 +652,13 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     HIPC(hipMemcpyAsync(d_T.p, c.T, sizeof(double) * 12 * (size_t)N, hipMemcpyDeviceToDevice, s));
     if (halo_slots > 0) HIPC(hipMemcpyAsync(d_T.p + (size_t)12 * N, x.d_halo, sizeof(double) * 12 * (size_t)halo_slots, hipMemcpyDeviceToDevice, s));
     D.s = s; D.agents = t->d_agents.p; D.Td = d_T.p; D.lam = c.lam; D.L = &L;
+    // the robots as sets (the table is on the device before the first keep launch): nb a window of iota at the robot's place
+    // in the global separator
+    iota_d = d_int.p + ipose_off[na];
     for (int k = 0; k < na; ++k)
-      rob[k] = {d_W[k].p, 6 * (int)P.interior[k].size(), 6 * (P.sep_off[k + 1] - P.sep_off[k]), 6 * gsoff[t->ag[k]->id], 0};
-    if (!ipose_h.empty()) HIPC(hipMemcpyAsync(d_int.p, ipose_h.data(), sizeof(int) * ipose_h.size(), hipMemcpyHostToDevice, s));
+      rob[k] = {d_W[k].p, iota_d + gsoff[t->ag[k]->id], d_int.p + ipose_off[k], D.M.p, nullptr, D.B.p, 6 * (int)P.interior[k].size(),
+                6 * (P.sep_off[k + 1] - P.sep_off[k])};
+    HIPC(hipMemcpyAsync(D.tab.p, rob.data(), sizeof(CovBlock) * na, hipMemcpyHostToDevice, s));
     HIPC(hipMemsetAsync(stat, 0, sizeof(double) * small, s));
     if (d_all) HIPC(hipMemsetAsync(d_D.p, 0, sizeof(double) * d_all, s));
     MARK(-1);
@@ -911,8 +715,8 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     if (h[1] == XF_OK) continue;
     std::string m = std::string(what) + ": rank " + std::to_string(q) + ": ";
     if (h[1] == XF_PIVOT)
-      m += "non-positive pivot at row " + std::to_string((long long)h[4]) + " of the interior Hessian of robot " + std::to_string((long long)h[2]) +
-           " (pose " + std::to_string((long long)h[3]) + "): the Hessian is not positive definite at this T: not a minimum";
+      m = pivot_message(std::string(what) + ": rank " + std::to_string(q), (long long)h[4],
+                        "the interior Hessian of robot " + std::to_string((long long)h[2]), (long long)h[3]);
     else if (h[1] == XF_MEMORY) m += "the Schur path does not fit its device (its own error names the bytes)";
     else m += "local failure (its own error names the cause)";
     if (q == x.rank && !fmsg.empty() && h[1] != XF_PIVOT) m += " [" + fmsg + "]";
@@ -973,30 +777,30 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   }
   // ---- the pair lists.  Owner of a pair: the holder of the (left) interior pose's robot; pairs of two public poses and
   // of two robots' interiors are formed by everyone
-  std::vector<SchurBlk> pub_list;
-  std::vector<SchurCross> ip_list, cross_list;
+  std::vector<CovBlk> pub_list, is_list;
+  std::vector<CovCross> cross_list;
   std::vector<int> pair_owner(num_pairs, -1);  // -1: everyone (or zeros)
   struct RowReq { int pair, robot, li; };
   std::vector<RowReq> rows;  // two per pair of two robots, in pair order
   for (int k = 0; k < na; ++k)
     for (int q = P.sep_off[k]; q < P.sep_off[k + 1]; ++q) {
       const int gsx = gsoff[t->ag[k]->id] + (q - P.sep_off[k]);
-      pub_list.push_back({P.sep[q], gsx, gsx, 1});
+      pub_list.push_back({P.sep[q], -1, gsx, gsx, 1, 0});
     }
   for (int k = 0; k < num_pairs; ++k) {
     const int a = pairs[2 * k], b = pairs[2 * k + 1], blk = N + k;
     if (a == 0 || b == 0) continue;
     const int ra = grobot[a], rb = grobot[b];
-    if (gpub[a] && gpub[b]) pub_list.push_back({blk, gpos[a], gpos[b], 0});
+    if (gpub[a] && gpub[b]) pub_list.push_back({blk, -1, gpos[a], gpos[b], 0, 0});
     else if (!gpub[a] && !gpub[b]) {
       if (ra == rb) pair_owner[k] = x.robot_holder[ra];
       else { rows.push_back({k, ra, gpos[a]}); rows.push_back({k, rb, gpos[b]}); }
     } else if (!gpub[a]) {
       pair_owner[k] = x.robot_holder[ra];
-      if (pair_owner[k] == x.rank) ip_list.push_back({blk, t->id2local.at(ra), gpos[a], -1, gpos[b], 0});
+      if (pair_owner[k] == x.rank) is_list.push_back({blk, t->id2local.at(ra), gpos[a], gpos[b], 0, 0});
     } else {
       pair_owner[k] = x.robot_holder[rb];
-      if (pair_owner[k] == x.rank) ip_list.push_back({blk, t->id2local.at(rb), gpos[b], -1, gpos[a], 1});
+      if (pair_owner[k] == x.rank) is_list.push_back({blk, t->id2local.at(rb), gpos[b], gpos[a], 1, 0});
     }
   }
   std::vector<size_t> clen(world, 1), rowoff(rows.size(), 0);
@@ -1015,7 +819,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   auto phase2 = [&]() -> int {
     if (nS > 0) {
       HIPC(hipMemcpyAsync(d_S.p, hS.data(), sizeof(double) * hS.size(), hipMemcpyHostToDevice, s));
-      k_schur_mirror<<<(unsigned)(((size_t)nS * nS + 255) / 256), 256, 0, s>>>(d_S.p, nS);
+      launch_schur_mirror(s, d_S.p, nS);
       HIPC(hipGetLastError());
       const int f = dense_spd_inverse(s, d_S.p, D.Wk.p, D.M.p, nS);
       HIPC(hipGetLastError());
@@ -1023,25 +827,16 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
       if (f > 0) { sfail = f; return DPGO_OK; }
       if (launch_cov_logdet(s, d_S.p, nS, stat + 4 * na)) return DPGO_ERR;
       MARK(3);
-      if (!pub_list.empty()) {
-        HIPC(hipMemcpyAsync(D.blk.p, pub_list.data(), sizeof(SchurBlk) * pub_list.size(), hipMemcpyHostToDevice, s));
-        k_schur_public<<<(unsigned)((36 * pub_list.size() + 255) / 256), 256, 0, s>>>(D.M.p, nS, D.blk.p, (int)pub_list.size(), outd);
-        HIPC(hipGetLastError());
-      }
+      if (schur_listed(D, nS, pub_list, D.blk.p, true, outd)) return DPGO_ERR;
       MARK(4);
     }
-    HIPC(hipMemcpyAsync(d_rob.p, rob.data(), sizeof(SchurRobot) * na, hipMemcpyHostToDevice, s));
     for (int k : byid) {
       if (rob[k].ld == 0) continue;
-      if (schur_robot_blocks(D, marks, t->ag[k]->id, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)rob[k].soff * nS + rob[k].soff, nS,
-                             d_int.p + ipose_off[k], same_list[k], keepd, outd))
+      if (schur_robot_blocks(D, marks, t->ag[k]->id, k, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)soff[k] * nS + soff[k], nS, same_list[k],
+                             keepd, outd))
         return DPGO_ERR;
     }
-    if (!ip_list.empty()) {
-      HIPC(hipMemcpyAsync(d_cross.p, ip_list.data(), sizeof(SchurCross) * ip_list.size(), hipMemcpyHostToDevice, s));
-      k_schur_pair_ip<<<(unsigned)((36 * ip_list.size() + 255) / 256), 256, 0, s>>>(d_rob.p, D.M.p, nS, d_cross.p, (int)ip_list.size(), outd);
-      HIPC(hipGetLastError());
-    }
+    if (schur_listed(D, nS, is_list, d_is.p, false, outd)) return DPGO_ERR;
     hout.resize(nout);
     HIPC(hipMemcpyAsync(hout.data(), outd, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
     if (nS > 0) HIPC(hipMemcpyAsync(sstat.data(), stat + 4 * na, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
@@ -1074,8 +869,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     int robot = 0;
     while (robot + 1 < nr && gsoff[robot + 1] <= sp) ++robot;
     const long long pose = x.robot_goff[robot] + pubf[robot][sp - gsoff[robot]];
-    set_err(std::string(what) + ": non-positive pivot at row " + std::to_string(sfail - 1) + " of the Schur complement on the public poses (pose " +
-            std::to_string(pose) + "): the Hessian is not positive definite at this T: not a minimum");
+    set_err(pivot_message(what, sfail - 1, "the Schur complement on the public poses", pose));
     return DPGO_ERR;
   }
   {
@@ -1095,41 +889,33 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     for (size_t r = 0; r < rows.size(); ++r) { ro[r] = total; total += 36 * (size_t)gs[rows[r].robot]; }
     if (d_rows.alloc(total)) { set_err("device allocation failed"); return DPGO_ERR; }
     std::vector<double> hr(total);
-    std::vector<SchurRobot> prob(rows.size());
+    std::vector<CovBlock> prob(rows.size());  // a row as a robot of one pose
     for (size_t r = 0; r < rows.size(); ++r) {
       const int q = x.robot_holder[rows[r].robot];
       std::memcpy(hr.data() + ro[r], gall.data() + (size_t)q * cmax + rowoff[r], sizeof(double) * 36 * (size_t)gs[rows[r].robot]);
-      prob[r] = {d_rows.p + ro[r], 6, 6 * gs[rows[r].robot], 6 * gsoff[rows[r].robot], 0};
+      prob[r] = {d_rows.p + ro[r], iota_d + gsoff[rows[r].robot], nullptr, nullptr, nullptr, nullptr, 6, 6 * gs[rows[r].robot]};
     }
     for (size_t r = 0; r + 1 < rows.size(); r += 2) cross_list.push_back({N + rows[r].pair, na + (int)r, 0, na + (int)r + 1, 0, 0});
     HIPC(hipMemcpyAsync(d_rows.p, hr.data(), sizeof(double) * total, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(d_rob.p + na, prob.data(), sizeof(SchurRobot) * prob.size(), hipMemcpyHostToDevice, s));
-    if (schur_cross_pairs(s, d_rob.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
+    HIPC(hipMemcpyAsync(D.tab.p + na, prob.data(), sizeof(CovBlock) * prob.size(), hipMemcpyHostToDevice, s));
+    if (schur_cross_pairs(s, D.tab.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
     std::vector<double> hc(36 * (size_t)num_pairs);
     HIPC(hipMemcpyAsync(hc.data(), outd + 36 * (size_t)N, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
-    for (const SchurCross &e : cross_list) std::memcpy(hout.data() + 36 * (size_t)e.blk, hc.data() + 36 * (size_t)(e.blk - N), sizeof(double) * 36);
+    for (const CovCross &e : cross_list) std::memcpy(hout.data() + 36 * (size_t)e.blk, hc.data() + 36 * (size_t)(e.blk - N), sizeof(double) * 36);
     return DPGO_OK;
   };
   if (!x.bad && phase3()) x.fail_local(g_err);
   if (x.finish()) return DPGO_ERR;
   // ---- the results: log det and pivots in robot order, the separator last
-  double logdet = 0.0, mn = INFINITY, mx = 0.0;
-  for (int i = 0; i < nr; ++i) {
-    if (rstat[4 * i + 3] == 0.0) continue;
-    logdet += rstat[4 * i];
-    mn = std::fmin(mn, rstat[4 * i + 1]);
-    mx = std::fmax(mx, rstat[4 * i + 2]);
-  }
-  if (nS > 0) { logdet += sstat[0]; mn = std::fmin(mn, sstat[1]); mx = std::fmax(mx, sstat[2]); }
+  std::vector<char> counted(nr + 1, 0);
+  for (int i = 0; i < nr; ++i) counted[i] = rstat[4 * i + 3] != 0.0;
+  counted[nr] = nS > 0;
+  rstat.insert(rstat.end(), sstat.begin(), sstat.end());
   double ms[5];
-  schur_report(marks, ms);
-  res->n = (int)(6 * (NG - 1));
-  res->logdet = logdet;
-  res->min_pivot = mn;
-  res->max_pivot = mx;
-  res->seconds_assemble = 1e-3 * ms[0];
-  res->seconds_invert = 1e-3 * (ms[1] + ms[2] + ms[3]);
+  marks.sum(ms);
+  cov_fill_result(res, 6 * (NG - 1), rstat.data(), counted, ms);
+  schur_report(marks);
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr,

@@ -326,7 +326,12 @@ int dpgo_translations_given_rotations(int device, const dpgo_measurement_t *m, i
  * the Schur complement on the public poses is inverted as a whole.  Exact and deterministic; the device holds three square
  * matrices of order M = max(6 x the largest interior, 6 x the public poses), the separator, and per robot a matrix of
  * 6 |I_a| x 6 s_a doubles (s_a: the robot's public poses) -- bytes = 8 (3 M^2 + (6 |S|)^2 + sum_a 36 |I_a| s_a + max_a 36 |I_a| s_a)
- * for these large buffers, plus the small ones (outputs, 72 doubles per requested block; lists; scratch: DESIGN.md 5e has every term). */
+ * for these large buffers, plus the small ones (N poses, P pairs, A robots, b stored blocks of Q, k = 6 max_a s_a):
+ *   small = 8 (33 N + A ceil(max_a n_a / 256) + 4 (A + 1) + 72 (N + P)) + 48 k min(P, 65535, 2^23 / (6 k))
+ *           + 24 (N + 2 P) + 24 P + 40 b + 4 (A + 1 + 2 N + |S|) + 56 (A + 2 P) + 8192 ceil(M / 32)
+ *   (T, T Q, Lambda, scratch, statistics, kept and output blocks; the scratch of pairs between two robots; list entries of 24
+ *    bytes; the work list; the maps and the index array 0 .. |S| - 1; a record of 56 bytes per set of the extraction kernels;
+ *    the Linv blocks of the inverse.  DESIGN.md 5e). */
 #define DPGO_COV_SCHUR 1
 typedef struct {
   int n;                 /* 6 (N - 1): the order of H_red */

@@ -224,6 +224,63 @@ def test_a_chain_split_among_robots_with_all_pairs():
     t.close()
 
 
+def test_a_robot_without_interior_between_two_with_one():
+    """a chain of 9 poses on robots of 4, 2 and 3 poses: both poses of the middle robot are public (the cuts), so its set has
+    an empty interior and two separator poses, next to two robots with interiors.  All 81 pairs against the dense path of
+    the same team under n eps cond_2 (cond_2 of the reference H_red; in the Frobenius norm over all blocks and in the 2-norm
+    block by block), the diagonal blocks bitwise the symmetrised pairs
+    (g, g), and the same call over one participant per robot bitwise the single team's"""
+    from tests.test_gpu_covariance_across import Split, bits, scalars
+    n, N, sizes = 9, 3, [4, 2, 3]
+    m, T = loop_chain(n, N, seed=5, between=False)
+    first = np.concatenate([[0], np.cumsum(sizes)])
+    robot_of = np.repeat(np.arange(N), sizes)
+    mp = m.copy()
+    for a, b in (("r1", "p1"), ("r2", "p2")):
+        mp[a], mp[b] = robot_of[m[b]], m[b] - first[robot_of[m[b]]]
+    public = np.zeros(n, dtype=bool)
+    cross = mp["r1"] != mp["r2"]
+    public[m["p1"][cross]] = public[m["p2"][cross]] = True
+    public[0] = False
+    info = covschur_ref.sets(robot_of, public)
+    assert info["s"][1] == 2 and not info["interior"][1] and info["interior"][0] and info["interior"][2], info
+    Hr, _, w = covref.dense_reference(covref.q_full(m, n), T, n)
+    assert w[0] > 0
+    nn = 6 * (n - 1)
+    bound = nn * EPS * w[-1] / w[0]
+    pairs = all_pairs(n)
+    t = capi.Team.from_measurements(mp, capi.default_params(r=5, num_robots=N, **RTR_NESTEROV))
+    t.set_initial(T, capi.fixed_stiefel(5))
+    X = t.global_X()
+    rs, ds_, cs = t.covariances(T, pairs, method="schur")
+    rd, dd, cd = t.covariances(T, pairs, method="dense")
+    t.close()
+    derr = np.linalg.norm(ds_ - dd) / np.linalg.norm(dd)
+    perr = np.linalg.norm(cs - cd) / np.linalg.norm(cd)
+    lerr = abs(rs.logdet - rd.logdet) / abs(rd.logdet)
+    print("chain %d on robots of %r: sets %r, cond_2 %.3e, |schur - dense|_F / |dense|_F: diagonal %.3e, pairs %.3e, logdet rel %.3e "
+          "(bound %.3e)" % (n, sizes, info["s"], w[-1] / w[0], derr, perr, lerr, bound))
+    assert rs.n == nn == rd.n
+    assert derr <= bound and perr <= bound and lerr <= bound
+    # block by block, so that an error confined to one block is not diluted: a block of a matrix has at most the matrix's
+    # 2-norm, and |Sigma|_2 = 1 / lambda_min(H_red)
+    worst = max(np.linalg.norm(a - b, 2) for a, b in zip(np.concatenate([ds_, cs]), np.concatenate([dd, cd])))
+    print("largest |block_schur - block_dense|_2 = %.3e (bound %.3e)" % (worst, bound / w[0]))
+    assert worst <= bound / w[0]
+    zero = (pairs[:, 0] == 0) | (pairs[:, 1] == 0)
+    assert not ds_[0].any() and not cs[zero].any() and cs[~zero].any()
+    for g in range(n):
+        Bc = cs[g * n + g]
+        assert ds_[g].tobytes() == (0.5 * (Bc + Bc.T)).tobytes()
+    sp = Split(mp, N, [[0], [1], [2]], X, **RTR_NESTEROV)
+    out = sp.run(lambda tm, tr: tm.covariances(T[sp.cols(sp.teams.index(tm), 12)], pairs, transport=tr, owner_of_robot=sp.owner))
+    for q, (r, d, c) in enumerate(out):
+        assert scalars(r) == scalars(rs), (q, r, rs)
+        assert bits(c) == bits(cs), q
+        assert bits(d) == bits(ds_.reshape(-1)[sp.cols(q, 36)]), q
+    sp.close()
+
+
 def test_a_graph_the_dense_path_refuses():
     """8 robots, the pose count taken from the device's memory so that the three dense matrices exceed it while the Schur
     path's own formula fits: "dense" refuses with the bytes and the pointer to "schur", "schur" answers and its column blocks
