@@ -129,7 +129,7 @@ dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
-dpgo_team_gate_candidates dpgo_team_pairwise_consistency dpgo_max_clique""".split()
+dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1124,6 +1124,58 @@ class Team:
                if e["weight"] == 0.0 and (e["r1"] == e["r2"] or min(int(e["r1"]), int(e["r2"])) == i)]
         return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
 
+    def measurements_once(self):
+        """all of the team's measurements with their current weights, in the form audit accepts; each shared edge once, as the
+        lower robot's copy (the rule of zero_weight_measurements)"""
+        out = [e for i in self.ids for e in self.agents[i].measurements()
+               if e["r1"] == e["r2"] or min(int(e["r1"]), int(e["r2"])) == i]
+        return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
+
+    def audit(self, measurements=None, T=None, method=None, max_block=None, quantile=0.99, min_redundancy=1e-6, sigma_loo=False):
+        """Measurements that are in the graph tested against the rest of it: leave-one-out gating.
+        measurements: MEAS_DTYPE records as in gate, whose weight w >= 0 says at which weight each is in the graph (w = 0: not in
+        the Hessian); the flags are ignored and the records are taken on trust.  None: measurements_once(), the team's own
+        with their current weights.  T, method and max_block as in gate.  Returns a dict:
+            measurements  the records audited,
+            xi[K, 6]      the innovation of gate,
+            xi_loo[K, 6]  the innovation the edge would have shown had it been left out of the graph,
+            d2[K]         to first order in the residuals the d2 gate would return for the edge had it been taken out, the
+                          graph solved again and the edge offered as a candidate; +inf where the record is not testable,
+            redundancy[K] rho = 1 - w tr(C) / 6 in [0, 1] with C the relative covariance whitened by the edge's own noise,
+            pivot_min[K]  the smallest Cholesky pivot of A = I - w C; the error of d2 grows like its reciprocal,
+            testable[K]   pivot_min > min_redundancy: the graph knows the relative pose by other ways than this edge,
+            accept[K]     testable and sqrt(d2) <= error_threshold_at_quantile(quantile, 6),
+            covariance    the Covariance record of the path,
+            sigma_loo[K, 6, 6]  with sigma_loo=True: the relative covariance of the graph without the edge (zero where the
+                          record is not testable).
+        At w = 0 this is gate; at w = 1 the normalised-residual test.  Raises DpgoError as gate does, and for a weight that is
+        negative or not finite or a min_redundancy outside (0, 1).  Changes no solver state."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("audit: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("audit: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        meas = self.measurements_once() if measurements is None else measurements
+        meas = np.ascontiguousarray(meas, dtype=MEAS_DTYPE).reshape(-1)
+        K = len(meas)
+        res = Covariance()
+        xi, xl, d2, rho, pm = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(K), np.zeros(K), np.zeros(K)
+        sg = np.zeros((K, 6, 6)) if sigma_loo else None
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        p = lambda a: _d(a) if K else None
+        _chk(lib().dpgo_team_audit_measurements(self.h, _d(T), code, int(max_block or 0), K, p(meas), C.c_double(min_redundancy),
+                                                p(xi), p(xl), p(d2), p(rho), p(pm), p(sg) if sigma_loo else None, C.byref(res)),
+             "audit_measurements")
+        testable = pm > min_redundancy
+        out = dict(measurements=meas, xi=xi, xi_loo=xl, d2=d2, redundancy=rho, pivot_min=pm, testable=testable,
+                   accept=testable & (np.sqrt(d2) <= error_threshold_at_quantile(quantile, 6)), covariance=res)
+        if sigma_loo:
+            out["sigma_loo"] = sg
+        return out
+
 
 def _adjacency_words(adjacency):
     """a bool K x K matrix as K rows of ceil(K / 64) words, bit b of word w of row k = adjacency[k, 64 w + b]"""
@@ -1287,13 +1339,14 @@ def _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, 
 
 def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None,
                     refine_translations=True, certify_kw=None, device=0, covariances=False, covariance_method="dense",
-                    covariance_max_block=None):
+                    covariance_max_block=None, audit=False):
     """End to end: the Riemannian staircase, then the SE-Sync rounding of its final point (Team.round on the final team).
     Returns dict(T=trajectory, 12 doubles per pose in team order anchored at the first pose, r=final rank, ranks,
     certificate, rounding=Rounding, f_relaxed, f_rounded, gap_rel, escape_costs).  gap_rel = (f_rounded - f_relaxed) /
     f_relaxed bounds the relative suboptimality of T (up to the certificate's eta) when the point is certified; it is None
     otherwise.  covariances=True adds covariances=(Covariance, diag[N, 6, 6]): Team.covariances of the final team at T by
-    covariance_method ("dense", "schur", or "nested" with covariance_max_block)."""
+    covariance_method ("dense", "schur", or "nested" with covariance_max_block).  audit=True adds audit=Team.audit() of the final
+    team at T, its own measurements at their final weights, by the same covariance_method / covariance_max_block."""
     def round_final(team, out):
         out["rounding"], out["T"] = team.round(refine_translations=refine_translations)
         if covariances:
@@ -1301,6 +1354,8 @@ def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iter
                 out["covariances"] = team.covariances_nested(out["T"], max_block=covariance_max_block)[:2]
             else:
                 out["covariances"] = team.covariances(out["T"], method=covariance_method)[:2]
+        if audit:
+            out["audit"] = team.audit(T=out["T"], method=covariance_method, max_block=covariance_max_block)
 
     out = _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, None, 30, certify_kw, device,
                      on_final=round_final)
@@ -1310,4 +1365,6 @@ def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iter
                f_rounded=rd.f_rounded, gap_rel=gap, escape_costs=out["escape_costs"])
     if covariances:
         res["covariances"] = out["covariances"]
+    if audit:
+        res["audit"] = out["audit"]
     return res

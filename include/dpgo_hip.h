@@ -423,6 +423,44 @@ int dpgo_team_gate_candidates(dpgo_team_t *t, const double *T, int method, int m
                               int num, const dpgo_measurement_t *cand,
                               double *xi /* 6 num or NULL */, double *d2 /* num or NULL */,
                               double *sigma_rel /* 36 num or NULL */, dpgo_covariance_t *res);
+/* ---- measurements that are in the graph audited by leave-one-out gating (csrc/audit.hip) ----
+ * Record k is a dpgo_measurement_t (r1, p1) -> (r2, p2), team poses i != j, with R~ (row-major), t~, kappa, tau and
+ * weight = w >= 0: the caller states that this measurement IS in the weighted graph at that weight (w = 0: not in the Hessian);
+ * fixed_weight and is_known_inlier are ignored, and the records are taken on trust.  Its own information w W0 is in Sigma, so
+ * its innovation is not independent of the estimate and the gate above does not apply; the audit takes the edge out again by
+ * the Woodbury identity on the 6 x 6 blocks of its pair.  T, Sigma, the perturbation, R_ij, t_ij, J_i, J_j, sigma_rel, xi and
+ * the logarithm are those of dpgo_team_gate_candidates.  Per record:
+ *   scaling      s = (sqrt(2 kappa) x 3, sqrt(tau) x 3): diag(s)^2 = Sigma_meas^-1 = W0, the edge's Hessian at zero residual
+ *   whitened     z = s o xi,  C_ab = sigma_rel,ab (s_a s_b)  (bitwise symmetric)
+ *   matrices     A = I - w C, the redundancy matrix of the edge: PSD in exact arithmetic, singular exactly in the directions
+ *                the graph knows through this edge alone;  B = I + (1 - w) C
+ *   rho          1 - w tr(C) / 6 in [0, 1], the redundancy number
+ *   pmin         A = L L^T; the smallest of the six pivots before the square root (pivots behind a non-positive one do not
+ *                count).  The record is testable when pmin > min_redundancy; the error of d2 grows like 1 / pmin
+ *   d2           u^T v with u = A^-1 z by both triangular solves and v = B^-1 z by its own Cholesky: to first order in the
+ *                residuals, what dpgo_team_gate_candidates would return for this edge had it been taken out of the graph, the
+ *                graph solved again and the edge offered as a candidate.  w = 0 is the gate itself, w = 1 the normalised
+ *                residual test
+ *   xi_loo       u / s elementwise: the innovation the edge would have shown had it been left out
+ *   sigma_loo    diag(1 / s) sym(A^-1 C) diag(1 / s), stored (X + X^T) / 2, row-major: (sigma_rel^-1 - w W0)^-1, the relative
+ *                covariance of the graph without the edge
+ *   failure      an untestable record, or a non-positive pivot of B (garbage blocks): d2 = +inf and xi_loo = 0; an untestable
+ *                record also sigma_loo = 0.  A record with d2 = +inf never passes
+ * A record passes at quantile q when it is testable and sqrt(d2) <= dpgo_error_threshold_at_quantile(q, 6).
+ * The blocks come from the covariance path `method` (max_block: DPGO_GATE_NESTED only), asked for the records' pairs (i, j),
+ * each ordered pair once in order of first use; they stay on the device, one kernel forms the outputs, and xi (6 num), xi_loo
+ * (6 num), d2, rho, pmin (num each) and, where it is not NULL, sigma_loo (36 num) come back.  Duplicated records give identical
+ * bits; two calls give the same bits.  Refused with DPGO_ERR and a message that names the record, before any device work, every
+ * output untouched: a NULL among the required arguments (all but sigma_loo); num <= 0; an unknown method; min_redundancy outside
+ * (0, 1); an endpoint that is not a robot or pose of the team; i == j; kappa <= 0 or tau <= 0; a non-finite value; a weight that
+ * is negative or not finite; R~ outside SO(3) by the 1e-8 rule of T.  Every refusal of the chosen covariance path carries over
+ * with its own message; the outputs are then untouched and *res all zero.  *res: the path's own record.  Changes no solver
+ * state.  There is no call across teams. */
+int dpgo_team_audit_measurements(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */,
+                                 int num, const dpgo_measurement_t *meas, double min_redundancy,
+                                 double *xi /* 6 num */, double *xi_loo /* 6 num */, double *d2 /* num */,
+                                 double *rho /* num */, double *pmin /* num */,
+                                 double *sigma_loo /* 36 num or NULL */, dpgo_covariance_t *res);
 /* ---- the pairwise-consistent set of candidates between two teams (csrc/consistency.hip, csrc/max_clique.cpp) ----
  * Pairwise consistency maximisation (Mangelson et al. 2018) for loop closures between two teams that are NOT joined yet, each
  * with a connected weighted graph of its own (they may be the same handle), trajectories T_a and T_b in their own gauges.
