@@ -125,7 +125,7 @@ dpgo_comm_unique_id dpgo_comm_create dpgo_comm_destroy dpgo_comm_rank dpgo_comm_
 dpgo_comm_allreduce_sum dpgo_comm_allreduce_max dpgo_team_attach_comm dpgo_team_detach_comm dpgo_team_exchange_all_ranks
 dpgo_team_run_ranks dpgo_comm_global_cost dpgo_team_comm_counters dpgo_team_set_iteration_log dpgo_team_run_simultaneous_ranks
 dpgo_team_run_group_ranks dpgo_rank_plan_simulate dpgo_team_set_uniform_schedule
-dpgo_team_certificate_apply dpgo_team_certify dpgo_escape_point dpgo_team_round
+dpgo_team_certificate_apply dpgo_team_certificate_precondition dpgo_team_certify dpgo_escape_point dpgo_team_round
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
@@ -956,6 +956,17 @@ class Team:
             own = _owner_array(owner_of_robot)
             _chk(lib().dpgo_team_certificate_apply_across(self.h, C.byref(transport.struct), _d(own), int(K), _d(V), _d(out)),
                  "certificate_apply_across")
+        return out
+
+    def certificate_precondition(self, V):
+        """T V for a K x 4N block (K in 3..8) in the layout of certificate_apply: the certificate eigensolver's block-Jacobi
+        preconditioner (Q_a + shift I)^-1 by agent (dense inverses or 4 x 4 diagonal inverses), for tests"""
+        N = int(sum(self.agents[i].n for i in self.ids))
+        V = np.ascontiguousarray(V, dtype=np.float64).reshape(-1)
+        K = V.size // (4 * N)
+        assert V.size == K * 4 * N
+        out = np.zeros_like(V)
+        _chk(lib().dpgo_team_certificate_precondition(self.h, int(K), _d(V), _d(out)), "certificate_precondition")
         return out
 
     def certify(self, eta=1e-6, tol=1e-8, max_iters=1000, block=0, deflate=True, precondition=True, eta_relative=True,

@@ -11,7 +11,9 @@
 // ld >= K lets one array hold several blocks (the basis [X; W; P] of the eigensolver is one 3K-row array).
 //
 // Every reduction is a Gram matrix A^T B: fixed column chunks per workgroup, one partial per chunk, summed in chunk
-// order by ONE workgroup of a second launch -- two calls on the same inputs give the same bits.
+// order by ONE workgroup of a second launch -- two calls on the same inputs give the same bits.  The eigensolver's own
+// Grams (gram_agents) chunk inside each agent and add the agents' totals in team order, so that robots split across
+// teams (certify_across.hip) give the single team's bits.
 // Nothing here writes a solver vector, a slab, a counter or a Nesterov state: the workspace is the team's d_cert.
 #include "certify_internal.h"
 
@@ -128,18 +130,20 @@ __global__ __launch_bounds__(256) void k_cert_lambda(const AgentDev *__restrict_
   if (threadIdx.x == 0) gmax[(size_t)ai * gstride + blockIdx.x] = red[0];
 }
 
-// partial Gram matrices: part[blk][p * kb + q] = sum over the block's columns of A[p] B[q]
+// partial Gram matrices: part[k][p * kb + q] = sum over chunk k's columns of A[p] B[q].  Chunk k covers the columns
+// [c0s[k], cends[k]) -- at most CG_CH of them --, or without a table [k CG_CH, min((k + 1) CG_CH, ncols))
 __global__ __launch_bounds__(256) void k_cert_gram(const double *__restrict__ A, int lda, int ka, const double *__restrict__ B,
-                                                   int ldb, int kb, int ncols, double *__restrict__ part) {
+                                                   int ldb, int kb, int ncols, const int *__restrict__ c0s,
+                                                   const int *__restrict__ cends, double *__restrict__ part) {
   __shared__ double As[CG_CH * CG_MAXK], Bs[CG_CH * CG_MAXK];
-  const int c0 = blockIdx.x * CG_CH, tid = threadIdx.x;
+  const int c0 = c0s ? c0s[blockIdx.x] : blockIdx.x * CG_CH, cend = c0s ? cends[blockIdx.x] : ncols, tid = threadIdx.x;
   for (int i = tid; i < CG_CH * ka; i += 256) {
     const int c = i / ka, p = i - c * ka;
-    As[i] = (c0 + c < ncols) ? A[(size_t)(c0 + c) * lda + p] : 0.0;
+    As[i] = (c0 + c < cend) ? A[(size_t)(c0 + c) * lda + p] : 0.0;
   }
   for (int i = tid; i < CG_CH * kb; i += 256) {
     const int c = i / kb, q = i - c * kb;
-    Bs[i] = (c0 + c < ncols) ? B[(size_t)(c0 + c) * ldb + q] : 0.0;
+    Bs[i] = (c0 + c < cend) ? B[(size_t)(c0 + c) * ldb + q] : 0.0;
   }
   __syncthreads();
   const int m = ka * kb;
@@ -151,11 +155,22 @@ __global__ __launch_bounds__(256) void k_cert_gram(const double *__restrict__ A,
   }
 }
 
-// ONE workgroup: out[o] = sum over the blocks, in block order
-__global__ __launch_bounds__(256) void k_cert_gram_sum(const double *__restrict__ part, int nblk, int m, double *__restrict__ out) {
+// ONE workgroup: group a's partials [gptr[a], gptr[a + 1]) in order into its total (kept in tot[a * m + o] when tot is
+// given: what a participant across teams sends for its robots), then the groups' totals in order, from 0, into out[o].
+// Without a table there is one group, the partials [0, ng): their plain sum in order.  With the agents as groups the
+// order of additions does not depend on how the robots are split across teams
+__global__ __launch_bounds__(256) void k_cert_gram_sum(const double *__restrict__ part, const int *__restrict__ gptr, int ng, int m,
+                                                       double *__restrict__ tot, double *__restrict__ out) {
+  const int groups = gptr ? ng : 1;
   for (int o = threadIdx.x; o < m; o += 256) {
     double s = 0.0;
-    for (int k = 0; k < nblk; ++k) s += part[(size_t)k * m + o];
+    for (int a = 0; a < groups; ++a) {
+      const int k0 = gptr ? gptr[a] : 0, k1 = gptr ? gptr[a + 1] : ng;
+      double sa = 0.0;
+      for (int k = k0; k < k1; ++k) sa += part[(size_t)k * m + o];
+      if (tot) tot[(size_t)a * m + o] = sa;
+      s += sa;
+    }
     out[o] = s;
   }
 }
@@ -350,11 +365,20 @@ int Cert::setup(int K_) {
   N = offs[na];
   L = 4 * N;
   nblk = (L + CG_CH - 1) / CG_CH;
+  // the chunks of the split-invariant Gram sums: 128 columns at a time inside each agent
+  std::vector<int> ach(na + 1, 0), cc0, cce;
+  for (int k = 0; k < na; ++k) {
+    for (int c = 4 * offs[k]; c < 4 * offs[k + 1]; c += CG_CH) { cc0.push_back(c); cce.push_back(std::min(c + CG_CH, 4 * offs[k + 1])); }
+    ach[k + 1] = (int)cc0.size();
+  }
+  nchunk = (int)cc0.size();
   gstride = (max_n + 255) / 256;
   const size_t Ls = (size_t)L;
   const size_t need = 2 * r * Ls + 9 * (size_t)N + 2 * (r + 1) * Ls + 4 * 3 * (size_t)K * Ls + 2 * (size_t)K * Ls +
-                      (size_t)nblk * SLOT + 8 * (size_t)SLOT + (size_t)na * gstride + (x ? x->dev_doubles() : 0);
-  if (t->d_cert.alloc(need) || t->d_cert_int.alloc(na + 1 + (x ? x->dev_ints() : 0)) ||
+                      (size_t)std::max(nblk, nchunk) * SLOT + 8 * (size_t)SLOT + (size_t)na * gstride +
+                      8 * (size_t)na * SLOT + (x ? x->dev_doubles() : 0);
+  const size_t ints = (size_t)2 * (na + 1) + 2 * (size_t)nchunk;
+  if (t->d_cert.alloc(need) || t->d_cert_int.alloc(ints + (x ? x->dev_ints() : 0)) ||
       t->h_cert.alloc(5 * SLOT + (size_t)K * L)) {
     set_err("certificate: workspace allocation failed");
     if (!x) return DPGO_ERR;
@@ -367,11 +391,17 @@ int Cert::setup(int K_) {
     Zr = take((r + 1) * Ls); Zo = take((r + 1) * Ls);
     for (int b = 0; b < 2; ++b) { U[b] = take(3 * K * Ls); AU[b] = take(3 * K * Ls); }
     T = take(K * Ls); T2 = take(K * Ls);
-    part = take((size_t)nblk * SLOT); G = take(8 * (size_t)SLOT); gmax = take((size_t)na * gstride);
+    part = take((size_t)std::max(nblk, nchunk) * SLOT); G = take(8 * (size_t)SLOT); gmax = take((size_t)na * gstride);
+    atot = take(8 * (size_t)na * SLOT);
     off = t->d_cert_int.p;
-    if (x) x->place(p, off + na + 1, t->stream);
+    achunk = off + na + 1; chunk0 = achunk + na + 1; chunkend = chunk0 + nchunk;
+    if (x) x->place(p, off + ints, t->stream);
   }
   CERT_CK(*this, hipMemcpyAsync(off, offs.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, t->stream));
+  CERT_CK(*this, hipMemcpyAsync(achunk, ach.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice, t->stream));
+  CERT_CK(*this, hipMemcpyAsync(chunk0, cc0.data(), sizeof(int) * nchunk, hipMemcpyHostToDevice, t->stream));
+  CERT_CK(*this, hipMemcpyAsync(chunkend, cce.data(), sizeof(int) * nchunk, hipMemcpyHostToDevice, t->stream));
+  CERT_CK(*this, hipStreamSynchronize(t->stream));  // (the tables are locals of this function)
   CERT_CK(*this, hipMemsetAsync(G, 0, sizeof(double) * 8 * SLOT, t->stream));
   // the team's iterate, gathered in team order (agent arrays are r x 4n each: ld r)
   for (int k = 0; k < na; ++k)
@@ -406,13 +436,23 @@ void Cert::apply(int k, const double *V, int ldv, double *out, int ldo, bool wit
 
 void Cert::gram(const double *A, int lda, int ka, const double *B, int ldb, int kb, double *out) {
   if (halted()) return;
-  k_cert_gram<<<nblk, 256, 0, t->stream>>>(A, lda, ka, B, ldb, kb, L, part);
-  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(part, nblk, ka * kb, out);
+  k_cert_gram<<<nblk, 256, 0, t->stream>>>(A, lda, ka, B, ldb, kb, L, nullptr, nullptr, part);
+  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(part, nullptr, nblk, ka * kb, nullptr, out);
+}
+
+void Cert::gram_agents(const double *A, int lda, int ka, const double *B, int ldb, int kb, int slot_) {
+  if (halted()) return;
+  k_cert_gram<<<nchunk, 256, 0, t->stream>>>(A, lda, ka, B, ldb, kb, L, chunk0, chunkend, part);
+  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(part, achunk, na, ka * kb, atot + (size_t)slot_ * na * SLOT, slot(slot_));
+}
+
+void Cert::reduce_agents(std::initializer_list<std::pair<int, int>> parts) {
+  if (x) x->reduce_agents(*this, parts);
 }
 
 void Cert::sum_partials(const double *p, int nblk_, int m, double *out) {
   if (halted()) return;
-  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(p, nblk_, m, out);
+  k_cert_gram_sum<<<1, 256, 0, t->stream>>>(p, nullptr, nblk_, m, nullptr, out);
 }
 
 void Cert::update(double *out, int ldo, int ko, double beta, std::initializer_list<CertTerm> terms) {
@@ -425,14 +465,14 @@ void Cert::update(double *out, int ldo, int ko, double beta, std::initializer_li
 
 void Cert::project(double *V, int ld, int k) {
   if (!deflate) return;
-  gram(Zo, nz, nz, V, ld, k, slot(5));
-  reduce({{slot(5), nz * k}});
+  gram_agents(Zo, nz, nz, V, ld, k, 5);
+  reduce_agents({{5, nz * k}});
   update(V, ld, k, 1.0, {CertTerm{Zo, slot(5), nz, nz, -1.0}});
 }
 
 void Cert::cholqr(double *V, int ld, int k, double *S) {
-  gram(V, ld, k, V, ld, k, slot(4));
-  reduce({{slot(4), k * k}});
+  gram_agents(V, ld, k, V, ld, k, 4);
+  reduce_agents({{4, k * k}});
   if (!halted()) k_cert_chol<<<1, 64, 0, t->stream>>>(slot(4), k, slot(6), slot(3));
   update(S, k, k, 0.0, {CertTerm{V, slot(6), ld, k, 1.0}});
   update(V, ld, k, 0.0, {CertTerm{S, nullptr, k, k, 1.0}});
@@ -488,9 +528,32 @@ int dpgo_team_certificate_apply(dpgo_team_t *t, int K, const double *V, double *
   return 0;
 }
 
+int dpgo_team_certificate_precondition(dpgo_team_t *t, int K, const double *V, double *out) {
+  if (!t || !V || !out) { set_err("certificate_precondition: null argument"); return DPGO_ERR; }
+  if (K < 3 || K > 8) { set_err("certificate_precondition: K must lie in 3..8"); return DPGO_ERR; }
+  if (check_team(t, "certificate_precondition")) return DPGO_ERR;
+  for (auto &a : t->ag)
+    if (!a->dev.M && !a->dev.Dinv) {
+      set_err("certificate_precondition: robot " + std::to_string(a->id) + " has the two-level form (no raw inverse to apply)");
+      return DPGO_ERR;
+    }
+  Cert c;
+  c.t = t;
+  if (c.setup(K)) return DPGO_ERR;
+  const size_t bytes = sizeof(double) * (size_t)K * c.L;
+  HIPC(hipMemcpyAsync(c.T, V, bytes, hipMemcpyHostToDevice, t->stream));
+  c.precondition(c.T, K, c.T2, K);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(out, c.T2, bytes, hipMemcpyDeviceToHost, t->stream));
+  HIPC(hipStreamSynchronize(t->stream));
+  return 0;
+}
+
 }  // extern "C"
 
 namespace dpgo_cert {
+
+constexpr double CERT_PC_OFF = 1e-3;  // the preconditioner is left out below -CERT_PC_OFF s (certify_body)
 
 // the state of the starting block's generator s <- 6364136223846793005 s + 1442695040888963407 after n steps, in O(log n)
 static unsigned long long lcg_skip(unsigned long long s, unsigned long long n) {
@@ -525,8 +588,8 @@ int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flag
   if (c.deflate) {
     const int z = r + 1;
     if (!c.halted()) k_cert_zbasis<<<(L + 255) / 256, 256, 0, t->stream>>>(c.Xt, r, c.Zr, L);
-    c.gram(c.Zr, z, z, c.Zr, z, z, c.slot(4));
-    c.reduce({{c.slot(4), z * z}});
+    c.gram_agents(c.Zr, z, z, c.Zr, z, z, 4);
+    c.reduce_agents({{4, z * z}});
     if (c.dead()) return x->fail();
     std::vector<double> gz((size_t)z * z);
     CK(hipMemcpyAsync(gz.data(), c.slot(4), sizeof(double) * z * z, hipMemcpyDeviceToHost, t->stream));
@@ -545,6 +608,20 @@ int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flag
     CK(hipMemcpyAsync(c.slot(7), hc, sizeof(double) * z * c.nz, hipMemcpyHostToDevice, t->stream));
     c.update(c.Zo, c.nz, c.nz, 0.0, {CertTerm{c.Zr, c.slot(7), z, z, 1.0}});
     c.cholqr(c.Zo, c.nz, c.nz, c.Zr);
+  }
+  // a block of K independent vectors needs K dimensions outside Z: a team of one to three poses may not have them (the
+  // projected starting block would be round-off, orthonormalised into vectors that are not in Z-perp at all).  Refused
+  // here, on numbers every participant holds alike, before anything is iterated
+  {
+    const long long Lg = x ? 4ll * x->nglob : (long long)L;
+    const long long dim = Lg - (c.deflate ? c.nz : 0);
+    if (dim < K) {
+      set_err("certify: the team is too small for the block size: 4N - nz = " + std::to_string(dim) + " dimensions (4N = " +
+              std::to_string(Lg) + (c.deflate ? ", nz = " + std::to_string(c.nz) + " deflated" : std::string(", no deflation")) +
+              ") are fewer than the block size " + std::to_string(K));
+      if (x) x->finish();
+      return DPGO_ERR;
+    }
   }
   // starting block: fixed pseudo-random numbers (the call is a function of the iterate alone).  Across teams each
   // participant draws its own columns of the single team's block: the generator skipped ahead to the global position
@@ -603,11 +680,17 @@ int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flag
     // AX = P S X;  R = AX - X (X^T AX)
     c.apply(K, X, K3, AX, K3, true);
     c.project(AX, K3, K);
-    c.gram(X, K3, K, AX, K3, K, c.slot(4));
-    c.reduce({{c.slot(4), K * K}});
+    c.gram_agents(X, K3, K, AX, K3, K, 4);
+    c.reduce_agents({{4, K * K}});
     c.update(W, K3, K, 0.0, {CertTerm{AX, nullptr, K3, K, 1.0}, CertTerm{X, c.slot(4), K3, K, -1.0}});
-    c.gram(W, K3, K, W, K3, K, c.slot(2));
-    if (c.precond) {
+    c.gram_agents(W, K3, K, W, K3, K, 2);
+    // T = (Q_a + shift I)^-1 stands for (S - theta I)^-1 near a critical point, where Lambda is small against Q and
+    // theta is about 0.  Far from one (a Ritz value below -CERT_PC_OFF s, a thousand times the default eta) it inverts
+    // another operator and slows the iteration: seeded random points with lambda_min = -0.3 s did not converge in 753
+    // iterations with it, and do in 37 .. 66 without.  The Ritz value is the last iteration's, from summed bits: the
+    // same decision on every participant.  Relative to s, so that neither the shift nor round-off about 0 decides it.
+    const bool far_from_critical = it > 0 && theta0 < -CERT_PC_OFF * s_bound;
+    if (c.precond && !far_from_critical) {
       c.precondition(W, K3, c.T, K);
       c.update(W, K3, K, 0.0, {CertTerm{c.T, nullptr, K, K, 1.0}});
     }
@@ -615,11 +698,11 @@ int certify_body(Cert &c, double eta, double tol, int max_iters, int K, int flag
     c.apply(K, W, K3, AW, K3, true);
     c.project(AW, K3, K);
     const int nb = it == 0 ? 2 * K : K3;
-    c.gram(U, K3, nb, AU, K3, nb, c.slot(0));
-    c.gram(U, K3, nb, U, K3, nb, c.slot(1));
+    c.gram_agents(U, K3, nb, AU, K3, nb, 0);
+    c.gram_agents(U, K3, nb, U, K3, nb, 1);
     // (across teams: the residual Gram of slot 2 travels with the basis Grams -- the Cholesky word of slot 3 needs no
     // reduction, it comes from summed Grams and is the same on every participant)
-    c.reduce({{c.slot(0), nb * nb}, {c.slot(1), nb * nb}, {c.slot(2), K * K}});
+    c.reduce_agents({{0, nb * nb}, {1, nb * nb}, {2, K * K}});
     if (c.dead()) return x->fail();
     CK(hipGetLastError());
     CK(hipMemcpyAsync(hG, c.G, sizeof(double) * 4 * Cert::SLOT, hipMemcpyDeviceToHost, t->stream));

@@ -154,6 +154,47 @@ int Across::reduce(Cert &c, std::initializer_list<std::pair<double *, int>> part
   return 0;
 }
 
+int Across::reduce_agents(Cert &c, std::initializer_list<std::pair<int, int>> parts) {
+  if (dead) return DPGO_ERR;
+  size_t m = 0;
+  for (auto &p : parts) m += (size_t)p.second;
+  const hipStream_t s = c.t->stream;
+  const int na = c.na;
+  std::vector<double> &h = hred[hflip];  // [status, robot 0's m sums, robot 1's, ...]: zeros for the robots held elsewhere
+  h.assign(1 + m * num_robots, 0.0);
+  if (!bad) {
+    std::vector<double> tot(m * na);
+    size_t o = 0;
+    for (auto &p : parts) {
+      note(hipMemcpyAsync(tot.data() + o * na, c.atot + (size_t)p.first * na * Cert::SLOT, sizeof(double) * p.second * na,
+                          hipMemcpyDeviceToHost, s), __LINE__);
+      o += (size_t)p.second;
+    }
+    note(hipStreamSynchronize(s), __LINE__);
+    o = 0;
+    for (auto &p : parts) {
+      for (int k = 0; k < na && !bad; ++k)
+        std::copy(tot.begin() + o * na + (size_t)k * p.second, tot.begin() + o * na + (size_t)(k + 1) * p.second,
+                  h.begin() + 1 + (size_t)c.t->ag[k]->id * m + o);
+      o += (size_t)p.second;
+    }
+  }
+  if (gather(h, hall)) return DPGO_ERR;
+  const size_t n = 1 + m * num_robots;
+  for (size_t o = 0; o < m; ++o) {
+    double v = 0.0;
+    for (int i = 0; i < num_robots; ++i) v += hall[(size_t)robot_holder[i] * n + 1 + (size_t)i * m + o];
+    h[1 + o] = v;
+  }
+  size_t o = 1;
+  for (auto &p : parts) {
+    if (!bad) note(hipMemcpyAsync(c.slot(p.first), h.data() + o, sizeof(double) * p.second, hipMemcpyHostToDevice, s), __LINE__);
+    o += (size_t)p.second;
+  }
+  hflip ^= 1;
+  return 0;
+}
+
 int Across::finish() {
   std::vector<double> m(1, 0.0);
   if (gather(m, hall)) return fail();

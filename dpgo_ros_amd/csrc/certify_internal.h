@@ -51,6 +51,11 @@ struct Cert {
   double *part = nullptr, *G = nullptr, *gmax = nullptr;
   int *off = nullptr;
   int gstride = 0, nblk = 0;
+  // the eigensolver's Gram sums (gram_agents): chunk k covers the team's columns [chunk0[k], chunkend[k]) of one agent,
+  // agent a owns chunks [achunk[a], achunk[a + 1]); atot: per slot, the agents' totals (na x ka kb) of its last Gram
+  int nchunk = 0;
+  int *achunk = nullptr, *chunk0 = nullptr, *chunkend = nullptr;
+  double *atot = nullptr;
   static constexpr int SLOT = CG_MAXK * CG_MAXK;
   // Gram slots: 0 basis x operator, 1 basis x basis, 2 residual x residual, 3 Cholesky failure word (read back together),
   // 4 X^T S X, 5 deflation products, 6 Cholesky coefficients, 7 coefficients from the host
@@ -59,6 +64,12 @@ struct Cert {
   int setup(int K_);
   void apply(int k, const double *V, int ldv, double *out, int ldo, bool with_lam);
   void gram(const double *A, int lda, int ka, const double *B, int ldb, int kb, double *out);
+  // A^T B into slot(slot_), summed agent by agent: inside an agent in chunks of 128 columns, then the agents' totals in
+  // team order.  The order does not depend on which team holds which robot, so a call split across teams (reduce_agents)
+  // gives the single team's bits (robots in id order in both)
+  void gram_agents(const double *A, int lda, int ka, const double *B, int ldb, int kb, int slot_);
+  // across teams: the listed slots (slot, count) of gram_agents summed over all robots in id order (no-op for one team)
+  void reduce_agents(std::initializer_list<std::pair<int, int>> parts);
   // out[o] = sum over the nblk partials part[k * m + o], in k order (one workgroup)
   void sum_partials(const double *p, int nblk_, int m, double *out);
   void update(double *out, int ldo, int ko, double beta, std::initializer_list<CertTerm> terms);
@@ -115,6 +126,9 @@ struct Across {
   int gather(std::vector<double> &mine, std::vector<double> &all);
   // the listed device arrays summed (or maximised) over the participants in rank order, in place
   int reduce(Cert &c, std::initializer_list<std::pair<double *, int>> parts, bool take_max = false);
+  // the slots of Cert::gram_agents: every robot's total from its holder, summed on the host in robot order from 0 -- the
+  // single team's order of additions
+  int reduce_agents(Cert &c, std::initializer_list<std::pair<int, int>> parts);
   const double *reduced() const { return hred[1 - hflip].data() + 1; }  // the host copy of the last reduce
   int finish();  // the closing status word: DPGO_ERR on every participant when any failed
   int fail();    // set_err(what: err), DPGO_ERR

@@ -283,12 +283,18 @@ typedef struct {
 } dpgo_certificate_t;
 /* flags of dpgo_team_certify.  Deflation (default) projects out Z = [rows of X; e_t], e_t = 1 on every translation
  * coordinate (S Z^T = 0 at a critical point); the preconditioner is the block-Jacobi (Q_a + shift I)^-1 by agent (off when
- * an agent has the two-level form); ETA_RELATIVE: eta is taken relative to s */
+ * an agent has the two-level form, and left out of an iteration whose last Ritz value is below -1e-3 s: far from a
+ * critical point it inverts another operator); ETA_RELATIVE: eta is taken relative to s */
 enum { DPGO_CERT_NO_DEFLATION = 1, DPGO_CERT_NO_PRECONDITIONER = 2, DPGO_CERT_ETA_RELATIVE = 4 };
 /* S(X) V for a K x 4N block in team order (agents by offsets), K in 3..8: the operator itself, for tests */
 int dpgo_team_certificate_apply(dpgo_team_t *t, int K, const double *V, double *out);
+/* T V for a K x 4N block in team order, K in 3..8: the eigensolver's preconditioner itself, (Q_a + shift I)^-1 by agent
+ * from its dense inverse or its 4 x 4 diagonal inverses, for tests.  DPGO_ERR where an agent has the two-level form */
+int dpgo_team_certificate_precondition(dpgo_team_t *t, int K, const double *V, double *out);
 /* verify the current iterate; v (4N doubles, team order) or NULL.  Converged: |S v - lambda v| <= tol * s; block 0 = r.
- * Changes no solver state. */
+ * A block of K vectors needs K dimensions to live in: when 4N - nz < K (nz = the rank of Z, 0 with NO_DEFLATION; teams of
+ * one to three poses) the call is refused with DPGO_ERR and a message that names 4N, nz and K -- pass a smaller block, or
+ * NO_DEFLATION.  Changes no solver state. */
 int dpgo_team_certify(dpgo_team_t *t, double eta, double tol, int max_iters, int block, int flags,
                       dpgo_certificate_t *out, double *v);
 /* staircase step, host arithmetic: X (r x 4n) and v (4n) -> the rank r+1 point [X; 0] + alpha [0; v^T],
