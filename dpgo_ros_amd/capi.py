@@ -101,6 +101,7 @@ ROUND_REFINE_TRANSLATIONS = 1
 COV_SCHUR = 1  # DPGO_COV_SCHUR
 COV_NESTED_DEFAULT_BLOCK = 256  # DPGO_COV_NESTED_DEFAULT_BLOCK
 GATE_DENSE, GATE_SCHUR, GATE_NESTED = 0, 1, 2  # DPGO_GATE_*
+JOINT_GREEDY, JOINT_GIVEN = 0, 1  # DPGO_JOINT_*
 PRECOND_AUTO, PRECOND_DENSE, PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL = 0, 1, 2, 3
 
 # every symbol include/dpgo_hip.h declares (checked by tests/test_abi.py)
@@ -129,7 +130,8 @@ dpgo_team_certificate_apply dpgo_team_certificate_precondition dpgo_team_certify
 dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_certify_across dpgo_team_round_across
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
-dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique""".split()
+dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
+dpgo_team_gate_candidates_jointly""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1185,6 +1187,62 @@ class Team:
                    accept=testable & (np.sqrt(d2) <= error_threshold_at_quantile(quantile, 6)), covariance=res)
         if sigma_loo:
             out["sigma_loo"] = sg
+        return out
+
+    def gate_jointly(self, candidates, T=None, method=None, max_block=None, quantile=0.99, order="greedy", innovation_covariance=False):
+        """A set of candidate measurements gated jointly, each given those already accepted.  candidates, T,
+        method and max_block as in gate, which tests every candidate against the covariance of the estimate before any of them
+        is taken; here M = A Sigma A^T + R is the joint covariance of all K innovations (A: the gate's Jacobians J_i, J_j of
+        every candidate in its row block, R: the block diagonal of the Sigma_meas), and candidate k is tested by its innovation
+        and covariance conditioned on the accepted set A: xi_k|A = xi_k - M_kA M_AA^-1 xi_A, S_k|A = M_kk - M_kA M_AA^-1 M_Ak,
+        d2_k|A = xi_k|A^T S_k|A^-1 xi_k|A -- to first order what gate would show for k once the candidates of A had been added
+        to the graph and the estimate updated.  order="greedy": at every step the remaining candidate of smallest d2_k|A (the
+        lower index on ties) is accepted if d2 <= error_threshold_at_quantile(quantile, 6)^2, else the call stops and all that
+        is left is rejected; order="given": k = 0 .. K - 1 in turn, accepted on the same test or skipped.  Returns a dict:
+            candidates     the records gated,
+            xi[K, 6], d2[K]  the marginal innovation and distance: gate's,
+            xi_cond[K, 6], d2_cond[K]  the conditional values at the moment k was decided (for what the greedy rule rejects at
+                           its stop: given the final set),
+            accept[K]      bool,
+            rank[K]        the position in the order of acceptance, -1 when rejected,
+            accepted       the indices of the accepted candidates in the order of acceptance,
+            num_accepted, d2_joint (the sum of d2_cond over the accepted set = xi_A^T M_AA^-1 xi_A), logdet_joint (log det M_AA),
+            joint_accept   sqrt(d2_joint) <= error_threshold_at_quantile(quantile, 6 num_accepted),
+            covariance     the Covariance record of the path,
+            M[6 K, 6 K]    with innovation_covariance=True: the joint innovation covariance, bitwise symmetric.
+        The covariance blocks, M and the factor stay on the device.  Raises DpgoError as gate does, and for a quantile outside
+        (0, 1) or a batch whose blocks, M and factor do not fit the device.  One team only.  Changes no solver state."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("gate_jointly: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        if order not in ("greedy", "given"):
+            raise ValueError("gate_jointly: order must be \"greedy\" or \"given\", not %r" % (order,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("gate_jointly: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        cand = np.ascontiguousarray(candidates, dtype=MEAS_DTYPE).reshape(-1)
+        K = len(cand)
+        res = Covariance()
+        xi, d2, xc, dc = np.zeros((K, 6)), np.zeros(K), np.zeros((K, 6)), np.zeros(K)
+        accept, rank = np.zeros(K, dtype=np.int32), np.full(K, -1, dtype=np.int32)
+        nacc, dj, lj = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        M = np.zeros((6 * K, 6 * K)) if innovation_covariance else None
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        p = lambda a: _d(a) if K else None
+        _chk(lib().dpgo_team_gate_candidates_jointly(self.h, _d(T), code, int(max_block or 0), K, p(cand),
+                                                     JOINT_GREEDY if order == "greedy" else JOINT_GIVEN, C.c_double(quantile),
+                                                     p(xi), p(d2), p(xc), p(dc), p(accept), p(rank), C.byref(nacc), C.byref(dj),
+                                                     C.byref(lj), p(M) if innovation_covariance else None, C.byref(res)),
+             "gate_candidates_jointly")
+        n = int(nacc.value)
+        accepted = np.argsort(np.where(rank >= 0, rank, K), kind="stable")[:n]
+        out = dict(candidates=cand, xi=xi, d2=d2, xi_cond=xc, d2_cond=dc, accept=accept != 0, rank=rank, accepted=accepted,
+                   num_accepted=n, d2_joint=float(dj.value), logdet_joint=float(lj.value),
+                   joint_accept=bool(n == 0 or np.sqrt(dj.value) <= error_threshold_at_quantile(quantile, 6 * n)), covariance=res)
+        if innovation_covariance:
+            out["M"] = M
         return out
 
 

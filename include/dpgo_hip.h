@@ -467,6 +467,48 @@ int dpgo_team_audit_measurements(dpgo_team_t *t, const double *T, int method /* 
                                  double *xi /* 6 num */, double *xi_loo /* 6 num */, double *d2 /* num */,
                                  double *rho /* num */, double *pmin /* num */,
                                  double *sigma_loo /* 36 num or NULL */, dpgo_covariance_t *res);
+/* ---- a set of candidates gated jointly, each given those already accepted (csrc/gate_joint.hip) ----
+ * dpgo_team_gate_candidates tests every candidate against the Sigma of the estimate before any of them is taken.  This call
+ * tests a batch of num = K candidates of one team against each other as well.  T, Sigma, the perturbation, R_ij, t_ij, J_i, J_j,
+ * xi, the logarithm and Sigma_meas are those of dpgo_team_gate_candidates; candidate k joins the team poses i_k != j_k.  With
+ * A the 6 K x 6 N matrix whose row block k holds J_i^k at pose i_k and J_j^k at pose j_k (nothing at pose 0), and R the block
+ * diagonal of the Sigma_meas,k:
+ *   M              A Sigma A^T + R, of order 6 K, row-major, bitwise symmetric; its diagonal block (k, k) is the S of the gate,
+ *                  stored (G + G^T) / 2.  Positive definite because R is, duplicated candidates included
+ *   conditional    given an accepted set A: xi_k|A = xi_k - M_kA M_AA^-1 xi_A, S_k|A = M_kk - M_kA M_AA^-1 M_Ak and
+ *                  d2_k|A = xi_k|A^T S_k|A^-1 xi_k|A: to first order at this T the innovation and distance that
+ *                  dpgo_team_gate_candidates would show for k after the candidates of A had been added to the graph and the
+ *                  estimate updated.  A non-positive pivot gives +inf, which is never accepted
+ *   order          thr = dpgo_error_threshold_at_quantile(quantile, 6).  DPGO_JOINT_GREEDY: at every step the remaining
+ *                  candidate of smallest d2_k|A, the lower index on ties; accepted when d2 <= thr^2, else the call stops and
+ *                  everything left is rejected.  DPGO_JOINT_GIVEN: k = 0 .. K - 1 in turn; accepted when d2_k|A <= thr^2,
+ *                  else skipped with A left as it is
+ *   outputs        xi (6 K), d2 (K): the marginal values, the definitions of dpgo_team_gate_candidates.  xi_cond (6 K),
+ *                  d2_cond (K): the conditional values at the moment k was decided; for what the greedy rule rejects at its
+ *                  stop, given the final A.  accept (K): 1 or 0.  rank (K): the position in the order of acceptance, -1 when
+ *                  rejected.  *num_accepted = |A|.  *d2_joint: the sum of d2_cond over A in the order of acceptance, which is
+ *                  xi_A^T M_AA^-1 xi_A.  *logdet_joint = log det M_AA.  The accepted set passes jointly when
+ *                  sqrt(d2_joint) <= dpgo_error_threshold_at_quantile(quantile, 6 |A|).  M (36 K^2) may be NULL: it then
+ *                  stays on the device.
+ * The covariance path `method` (max_block: DPGO_GATE_NESTED only) is asked for every unordered pair of the distinct endpoint
+ * poses, sorted; the blocks stay on the device.  One kernel forms xi, d2 and M, then one launch per step of a left-looking
+ * block-pivoted Cholesky of M in the order the pivots are taken updates the conditional diagonal blocks, xi_cond and d2_cond
+ * (M is only read; the stream order is the only synchronisation), and only the outputs come back.  No floating-point atomics:
+ * duplicated candidates have identical marginal bits, and two calls give the same bits.
+ * Refused with DPGO_ERR and a message before any device work, every output untouched: every refusal of
+ * dpgo_team_gate_candidates for a call with xi and d2 (a NULL among the required arguments -- all but M --, num <= 0, an unknown
+ * method, an endpoint that is not a robot or pose of the team, i == j, kappa <= 0 or tau <= 0, R~ outside SO(3)); an unknown
+ * order; quantile outside (0, 1); and pair blocks (288 bytes each), M and the factor (288 K^2 bytes each) that do not fit the
+ * free device memory, with the bytes named.  Every refusal of the chosen covariance path carries over with its own message;
+ * the outputs are then untouched and *res all zero.  *res: the path's own record.  Changes no solver state.  There is no call
+ * across teams. */
+enum { DPGO_JOINT_GREEDY = 0, DPGO_JOINT_GIVEN = 1 };
+int dpgo_team_gate_candidates_jointly(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */,
+                                      int num, const dpgo_measurement_t *cand, int order /* DPGO_JOINT_* */, double quantile,
+                                      double *xi /* 6 num */, double *d2 /* num */, double *xi_cond /* 6 num */,
+                                      double *d2_cond /* num */, int *accept /* num */, int *rank /* num */, int *num_accepted,
+                                      double *d2_joint, double *logdet_joint, double *M /* 36 num^2 or NULL */,
+                                      dpgo_covariance_t *res);
 /* ---- the pairwise-consistent set of candidates between two teams (csrc/consistency.hip, csrc/max_clique.cpp) ----
  * Pairwise consistency maximisation (Mangelson et al. 2018) for loop closures between two teams that are NOT joined yet, each
  * with a connected weighted graph of its own (they may be the same handle), trajectories T_a and T_b in their own gauges.
