@@ -131,7 +131,7 @@ dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_c
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
-dpgo_team_gate_candidates_jointly""".split()
+dpgo_team_gate_candidates_jointly dpgo_team_linear_update""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1244,6 +1244,47 @@ class Team:
         if innovation_covariance:
             out["M"] = M
         return out
+
+    def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None):
+        """The estimate and its covariances updated to first order for a set of new closures, without a re-solve (DESIGN.md
+        5j): the information-filter update of the whole trajectory.  closures, T, method and max_block as in gate_jointly, whose
+        A, R and M = A Sigma A^T + R these are: with B = Sigma A^T, dx = -B M^-1 xi, Sigma' = Sigma - B M^-1 B^T and
+        T' = T [+] dx (R_p <- R_p Exp(phi_p), t_p <- t_p + delta_p, pose 0 fixed) -- what a Gauss-Newton step from T on the graph
+        with the closures added gives, with the Laplace covariance there.  pairs: team-order pose pairs (a, b) whose blocks
+        Sigma'_ab are wanted beside the diagonal ones.  Returns a dict:
+            T                T' in the layout of chordal_init (12 doubles per pose in team order),
+            delta[N, 6]      dx_p = (phi_p, delta_p),
+            cov_diag[N, 6, 6]  the diagonal blocks of Sigma', bitwise symmetric,
+            cov_pairs[len(pairs), 6, 6]  the blocks Sigma'_ab,
+            xi[K, 6]         the innovations at T: gate's,
+            xi_post[K, 6]    R M^-1 xi = xi + A dx: the innovations at T' to first order,
+            d2_joint         xi^T M^-1 xi: gate_jointly's for the same set,
+            logdet_M, logdet_R, information_gain = (logdet_M - logdet_R) / 2,
+            covariance       the Covariance record of the path (of Sigma, not Sigma').
+        The covariance blocks, B, M and their products stay on the device.  Raises DpgoError as gate_jointly does, for a pair that
+        names a pose outside the team, and for a batch whose blocks and matrices do not fit the device.  One team only.
+        Changes no solver state."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("linear_update: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("linear_update: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        cand = np.ascontiguousarray(closures, dtype=MEAS_DTYPE).reshape(-1)
+        K = len(cand)
+        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        res = Covariance()
+        Tn, dx, diag, cross = np.zeros(12 * N), np.zeros((N, 6)), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
+        xi, xp, sc = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(3)
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        p = lambda a: _d(a) if K else None
+        _chk(lib().dpgo_team_linear_update(self.h, _d(T), code, int(max_block or 0), K, p(cand), len(pr), _d(pr) if len(pr) else None,
+                                           _d(Tn), _d(dx), _d(diag), _d(cross) if len(pr) else None, _d(xi), _d(xp), _d(sc),
+                                           C.byref(res)), "linear_update")
+        return dict(T=Tn, delta=dx, cov_diag=diag, cov_pairs=cross, xi=xi, xi_post=xp, d2_joint=float(sc[0]), logdet_M=float(sc[1]),
+                    logdet_R=float(sc[2]), information_gain=0.5 * float(sc[1] - sc[2]), covariance=res)
 
 
 def _adjacency_words(adjacency):

@@ -509,6 +509,47 @@ int dpgo_team_gate_candidates_jointly(dpgo_team_t *t, const double *T, int metho
                                       double *d2_cond /* num */, int *accept /* num */, int *rank /* num */, int *num_accepted,
                                       double *d2_joint, double *logdet_joint, double *M /* 36 num^2 or NULL */,
                                       dpgo_covariance_t *res);
+/* ---- the estimate and its covariances updated for new closures, no re-solve (csrc/linear_update.hip) ----
+ * The information-filter update (the EKF update in covariance form) of the whole trajectory for num = K closures of one team
+ * taken together, at the estimate T with covariance Sigma: B = Sigma A^T, M = A B + R, dx = -B M^-1 xi,
+ * Sigma' = Sigma - B M^-1 B^T, T' = T [+] dx.  (T', Sigma') is what a Gauss-Newton step from T on the graph with the closures
+ * added gives, together with the Laplace covariance there (the matrix-inversion lemma: Sigma' = (H + A^T R^-1 A)^-1,
+ * dx = -Sigma' A^T R^-1 xi).
+ *   T, Sigma, the perturbation, J_i, J_j, xi with no Log-Jacobian, and Sigma_meas are those of dpgo_team_gate_candidates: the
+ *                  perturbation is R_p <- R_p Exp(phi_p) in the body frame and t_p <- t_p + delta_p in the world frame, with
+ *                  pose 0 fixed.  As in the gate, the weight field of a closure is not read.
+ *   A and R        are those of dpgo_team_gate_candidates_jointly.
+ *   endpoints      there are K closures on m distinct endpoint poses e_0 < ... < e_{m-1}.
+ *   B_p,k          = Sigma_{p,i_k} J_i^k^T + Sigma_{p,j_k} J_j^k^T is a 6 x 6 block, for p = 0 ... N - 1.  Any Sigma block that
+ *                  names pose 0 is zero, so B_0 = 0.
+ *   M_kl           = J_i^k B_{i_k,l} + J_j^k B_{j_k,l} + delta_kl Sigma_meas,k.  The diagonal blocks are stored symmetrised.  M
+ *                  is stored bitwise symmetric: one lane writes a block and its transpose.  The side from which a block is
+ *                  formed is chosen by the endpoints, as in the joint gate.
+ *   G              = M^-1 comes from the library's dense SPD inverse.
+ *   z, U           z = G xi and U = B G.
+ *   dx_p           = -B_p z (delta, 6 per pose: phi_p, then delta_p).
+ *   xi_post        = R z, which equals xi + A dx.
+ *   Sigma'_pp      = Sigma_pp - U_p B_p^T, formed in the upper triangle and mirrored (cov_diag, 36 per pose, row-major).
+ *   Sigma'_pq      = Sigma_pq - U_p B_q^T for each requested pair (cov_pairs, 36 per pair of `pairs`, team pose indices).
+ *   T'_p           = (R_p Exp(phi_p), t_p + delta_p), by Rodrigues, with the series below a threshold angle (T_new, the layout
+ *                  of T).
+ *   scalars        d2_joint = xi^T z; logdet_M from the Cholesky factor; logdet_R = sum_k -3 log(2 kappa_k) - 3 log tau_k.
+ *                  The information the batch brings is (logdet_M - logdet_R) / 2.
+ * Every sum runs in index order with fused multiply-adds and there are no floating-point atomics, so two calls give the same
+ * bytes.  The covariance path `method` (max_block: DPGO_GATE_NESTED only) is asked for the rectangular set -- for each
+ * endpoint rank a and each pose p the block Sigma_{p, e_a}, N m pair blocks -- and for the caller's pairs behind them; the
+ * blocks, B, U, M and G stay on the device and only the outputs come back.
+ * Refused with DPGO_ERR and a message that begins "linear_update:", every output untouched: a NULL among the required
+ * arguments (all but pairs and cov_pairs when num_pairs is 0), num <= 0, num_pairs < 0, an unknown method, an endpoint that is
+ * not a robot or pose of the team, i == j, kappa or tau not positive and finite, R~ outside SO(3) by the 1e-8 rule, a pair
+ * index outside [0, N); the N m pair blocks (288 bytes each), B and U (288 N K bytes each) and the three matrices of order 6 K
+ * that do not fit the free device memory, or more than INT32_MAX pair blocks, with the bytes named; a non-positive pivot in M,
+ * with the pivot block named.  Every refusal of the chosen covariance path carries over with its own message; the outputs are
+ * then untouched and *res all zero.  *res: the path's own record.  Changes no solver state.  There is no call across teams. */
+int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block, int num,
+                            const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
+                            double *delta /* 6 N */, double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_post,
+                            double *scalars /* d2_joint, logdet_M, logdet_R */, dpgo_covariance_t *res);
 /* ---- the pairwise-consistent set of candidates between two teams (csrc/consistency.hip, csrc/max_clique.cpp) ----
  * Pairwise consistency maximisation (Mangelson et al. 2018) for loop closures between two teams that are NOT joined yet, each
  * with a connected weighted graph of its own (they may be the same handle), trajectories T_a and T_b in their own gauges.
