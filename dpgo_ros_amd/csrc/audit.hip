@@ -11,15 +11,13 @@
 //   an untestable record, or a non-positive pivot of B, gives d2 = +inf and xi_loo = 0; untestable also Sigma_loo = 0
 // The arithmetic is in audit_block.h.  The blocks are those a covariance path has staged on the device (certify_internal.h,
 // CovStage): k_audit is the step behind them, and only the per-record outputs go to the host.
-#include <map>
-
-#include "certify_internal.h"
+#include "closure_frame.h"
 #include "audit_block.h"
 
 namespace dpgo {
 
-// one record on the device: team poses i != j, the staged pair block that holds S_ij, and the measurement with its weight
-// (144 bytes: nine 16-byte loads; GateCand has no room for the weight)
+// one record on the device: the head of GateRec (team poses i != j, the staged pair block that holds S_ij) and the measurement
+// with its weight (144 bytes: nine 16-byte loads; GateRec has no room for the weight)
 struct AuditRec {
   int i, j, blk, pad;
   double m[AUDIT_REC];  // R~ row-major, t~, kappa, tau, w, padding
@@ -64,20 +62,17 @@ namespace dpgo_cert {
 
 namespace {
 
+const ClosureCall AUDIT = {"audit_measurements", "record"};
+
 // the step behind a covariance path's staged blocks: upload the records, run k_audit, queue the copies into staging vectors
-struct AuditEpilogue : CovEpilogue {
+struct AuditEpilogue : ClosureEpilogue {
   std::vector<AuditRec> rec;
   double min_redundancy = 0.0;
   bool want_sigma = false;
   DevBuf<AuditRec> d_rec;
   DevBuf<double> d_out;  // xi[6 K], xi_loo[6 K], d2[K], rho[K], pmin[K], sigma_loo[36 K] when it is formed
   std::vector<double> h_out;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ran = false;
-  ~AuditEpilogue() override {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  AuditEpilogue() : ClosureEpilogue(2) {}
   size_t doubles() const { return (size_t)(want_sigma ? 51 : 15) * rec.size(); }
   int alloc() {
     const size_t K = rec.size();
@@ -86,8 +81,7 @@ struct AuditEpilogue : CovEpilogue {
               std::to_string(K) + " records)");
       return DPGO_ERR;
     }
-    for (auto &e : ev) HIPC(hipEventCreate(&e));
-    return DPGO_OK;
+    return ev.create();
   }
   int run(const CovStage &st) override {
     const size_t K = rec.size();
@@ -113,11 +107,6 @@ struct AuditEpilogue : CovEpilogue {
   }
 };
 
-int audit_refuse(const std::string &m) {
-  set_err("audit_measurements: " + m);
-  return DPGO_ERR;
-}
-
 }  // namespace
 
 }  // namespace dpgo_cert
@@ -128,93 +117,40 @@ extern "C" int dpgo_team_audit_measurements(dpgo_team_t *t, const double *T, int
                                             const dpgo_measurement_t *meas, double min_redundancy, double *xi, double *xi_loo,
                                             double *d2, double *rho, double *pmin, double *sigma_loo, dpgo_covariance_t *res) {
   // ---- the refusals of the audit itself: on the host, before any device work, no output touched
-  if (!t || !T || !res || !xi || !xi_loo || !d2 || !rho || !pmin) return audit_refuse("null argument");
-  if (num <= 0) return audit_refuse("num must be positive, not " + std::to_string(num));
-  if (!meas) return audit_refuse("null argument");
-  if (method != DPGO_GATE_DENSE && method != DPGO_GATE_SCHUR && method != DPGO_GATE_NESTED)
-    return audit_refuse("method must be DPGO_GATE_DENSE, DPGO_GATE_SCHUR or DPGO_GATE_NESTED, not " + std::to_string(method));
+  if (!t || !T || !res || !xi || !xi_loo || !d2 || !rho || !pmin) return AUDIT.refuse("null argument");
+  if (num <= 0) return AUDIT.refuse("num must be positive, not " + std::to_string(num));
+  if (!meas) return AUDIT.refuse("null argument");
+  if (AUDIT.check_method(method)) return DPGO_ERR;
   if (!(min_redundancy > 0.0 && min_redundancy < 1.0)) {
     char buf[120];
     std::snprintf(buf, sizeof buf, "min_redundancy must lie in (0, 1), not %.6g", min_redundancy);
-    return audit_refuse(buf);
+    return AUDIT.refuse(buf);
   }
-  if (check_team_local(t, "audit_measurements")) return DPGO_ERR;
-  const int na = (int)t->ag.size();
-  std::vector<int> offs(na + 1, 0);
-  for (int k = 0; k < na; ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
+  if (check_team_local(t, AUDIT.name)) return DPGO_ERR;
+  const std::vector<int> offs = pose_offsets(t);
   AuditEpilogue epi;
   epi.min_redundancy = min_redundancy;
   epi.want_sigma = sigma_loo != nullptr;
   epi.rec.resize(num);
-  std::map<std::pair<int, int>, int> blk_of;  // the pair list handed to the path: each (i, j) once, in order of first use
-  std::vector<int> pairs;
+  FirstUsePairs pairs;  // the pair list handed to the path
   for (int k = 0; k < num; ++k) {
     const dpgo_measurement_t &m = meas[k];
     int g[2];
-    for (int e = 0; e < 2; ++e) {
-      const int r = e ? m.r2 : m.r1, p = e ? m.p2 : m.p1;
-      const auto l = t->id2local.find(r);
-      if (l == t->id2local.end()) return audit_refuse("record " + std::to_string(k) + " names robot " + std::to_string(r) + ", which is not in the team");
-      if (p < 0 || p >= t->ag[l->second]->n)
-        return audit_refuse("record " + std::to_string(k) + " names pose " + std::to_string(p) + " of robot " + std::to_string(r) +
-                            ", outside [0, " + std::to_string(t->ag[l->second]->n) + ")");
-      g[e] = offs[l->second] + p;
-    }
-    if (g[0] == g[1]) return audit_refuse("record " + std::to_string(k) + " joins a pose to itself");
-    if (!(m.kappa > 0.0) || !(m.tau > 0.0) || !std::isfinite(m.kappa) || !std::isfinite(m.tau)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "record %d has kappa = %.6g, tau = %.6g: both must be positive", k, m.kappa, m.tau);
-      return audit_refuse(buf);
-    }
-    if (!(m.weight >= 0.0) || !std::isfinite(m.weight)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "record %d has weight = %.6g: it must be finite and not negative", k, m.weight);
-      return audit_refuse(buf);
-    }
-    // R~ in SO(3) by the rule of T (covariance_host_checks); row-major here, which changes neither figure
-    const double *R = m.R;
-    double orth = 0.0;
-    for (int p = 0; p < 3; ++p)
-      for (int q = 0; q < 3; ++q) {
-        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
-        orth = std::max(orth, std::fabs(d));
-      }
-    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
-    bool finite = true;
-    for (int q = 0; q < 9; ++q) finite = finite && std::isfinite(R[q]);
-    for (int q = 0; q < 3; ++q) finite = finite && std::isfinite(m.t[q]);
-    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "the measurement of record %d is not in SE(3) (|R R^T - I| = %.3g, det R = %.12g)", k, orth, det);
-      return audit_refuse(buf);
-    }
+    if (AUDIT.endpoints(t, offs, k, m, g) || AUDIT.check(k, m, true)) return DPGO_ERR;
     AuditRec &c = epi.rec[k];
     std::memset(&c, 0, sizeof c);
     c.i = g[0]; c.j = g[1];
-    const auto ins = blk_of.insert({{g[0], g[1]}, (int)blk_of.size()});
-    if (ins.second) { pairs.push_back(g[0]); pairs.push_back(g[1]); }
-    c.blk = ins.first->second;
-    std::memcpy(c.m, m.R, sizeof m.R);
-    std::memcpy(c.m + 9, m.t, sizeof m.t);
-    c.m[12] = m.kappa; c.m[13] = m.tau; c.m[14] = m.weight;
+    c.blk = pairs.block(g[0], g[1]);
+    pack_measurement(m, c.m);
+    c.m[14] = m.weight;
   }
   HIPC(hipSetDevice(t->device));
   if (epi.alloc()) return DPGO_ERR;
-  // ---- the covariance path, with its own refusals and messages; its blocks stay on the device for the epilogue
-  const int np = (int)pairs.size() / 2;
-  const int rc = method == DPGO_GATE_NESTED ? marginal_covariances_nested_call(t, T, max_block, np, pairs.data(), nullptr, nullptr, res, &epi)
-                                            : marginal_covariances_call(t, T, method == DPGO_GATE_SCHUR ? DPGO_COV_SCHUR : 0, np, pairs.data(),
-                                                                        nullptr, nullptr, res, &epi);
-  if (rc != DPGO_OK) return rc;
-  if (!epi.ran) {  // (a team of the anchor alone has no two poses to join: the endpoint checks have refused already)
-    std::memset(res, 0, sizeof *res);
-    return audit_refuse("the covariance path staged no blocks");
-  }
-  float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, epi.ev[0], epi.ev[1]));
+  const int np = pairs.count();
+  if (const int rc = AUDIT.path(t, T, method, max_block, np, pairs.pairs.data(), res, epi)) return rc;
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
-    std::fprintf(stderr, "audit_measurements: %d records on %d pair blocks, audit kernel %.3f ms\n", num, np, ms);
+    std::fprintf(stderr, "audit_measurements: %d records on %d pair blocks, audit kernel %.3f ms\n", num, np, epi.ev.ms());
   const size_t K = (size_t)num;
   const double *h = epi.h_out.data();
   std::memcpy(xi, h, sizeof(double) * 6 * K);

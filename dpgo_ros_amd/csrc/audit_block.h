@@ -1,7 +1,6 @@
 // audit_block.h -- the per-record arithmetic of the leave-one-out audit of measurements that are in the graph,
-// behind gate_relative: what k_audit (audit.hip) does with the relative pose and its covariance.  It compiles for the device
-// (16-byte global loads) and for the host with plain loads, so the same text is checked on a machine without a GPU
-// (tests/test_audit_host.py).
+// behind gate_relative: what k_audit (audit.hip) does with the relative pose and its covariance, in the primitives of gate_block.h.
+// It compiles for the device and for the host, so the same text is checked on a machine without a GPU (tests/test_audit_host.py).
 //
 // A record is a measurement (i -> j, R~, t~, kappa, tau) that IS in the weighted graph, at weight w >= 0.  With R_ij, t_ij,
 // Sigma_rel and xi of the gate (gate.hip):
@@ -24,12 +23,6 @@
 
 namespace dpgo {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define AUDIT_LOAD2(p, lo, hi) do { const double2 w_ = ld2(p); (lo) = w_.x; (hi) = w_.y; } while (0)
-#else
-#define AUDIT_LOAD2(p, lo, hi) do { (lo) = (p)[0]; (hi) = (p)[1]; } while (0)
-#endif
-
 constexpr int AUDIT_REC = 16;  // doubles of the measurement part of a record: R~ row-major (9), t~ (3), kappa, tau, w, one of padding
 
 // what one record gives; sigma_loo is formed only where it is asked for
@@ -38,68 +31,15 @@ struct AuditOut {
   bool testable;
 };
 
-// Cholesky of the symmetric S in place (lower triangle).  ok: every pivot > floor.  pmin: the smallest pivot, those behind a
-// non-positive one left out
-DPGO_HD void audit_cholesky(double S[6][6], double floor, bool &ok, double &pmin) {
-  bool alive = true;
-  ok = true;
-  pmin = INFINITY;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double p = S[c][c];
-#pragma unroll
-    for (int q = 0; q < c; ++q) p = __builtin_fma(-S[c][q], S[c][q], p);
-    ok = ok && p > floor;
-    pmin = alive && !(p >= pmin) ? p : pmin;  // (a NaN pivot is kept: it compares false with every floor)
-    alive = alive && p > 0.0;
-    const double l = sqrt(p), inv = 1.0 / l;
-    S[c][c] = inv;  // (the reciprocal of the diagonal of L is what the solves use)
-#pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
-      double v = S[r][c];
-#pragma unroll
-      for (int q = 0; q < c; ++q) v = __builtin_fma(-S[r][q], S[c][q], v);
-      S[r][c] = v * inv;
-    }
-  }
-}
-
-// x <- (L L^T)^-1 x with the factor audit_cholesky leaves (reciprocals on the diagonal)
-DPGO_HD void audit_solve(const double L[6][6], double x[6]) {
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double v = x[c];
-#pragma unroll
-    for (int q = 0; q < c; ++q) v = __builtin_fma(-L[c][q], x[q], v);
-    x[c] = v * L[c][c];
-  }
-#pragma unroll
-  for (int c = 5; c >= 0; --c) {
-    double v = x[c];
-#pragma unroll
-    for (int q = c + 1; q < 6; ++q) v = __builtin_fma(-L[q][c], x[q], v);
-    x[c] = v * L[c][c];
-  }
-}
-
 // One record.  M = R_ij, tij = t_ij, S = Sigma_rel (bitwise symmetric; overwritten), rec the AUDIT_REC doubles of the measurement.
 // SIGMA: SL receives Sigma_loo, bitwise symmetric (else it is not touched).
 template <bool SIGMA>
 DPGO_HD void audit_record(const double M[3][3], const double tij[3], double S[6][6], const double *rec, double min_redundancy,
                           AuditOut &o, double SL[6][6]) {
-  double v[16];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) AUDIT_LOAD2(rec + 2 * q, v[2 * q], v[2 * q + 1]);
-  const double *Rm = v, *tm = v + 9;
+  double v[AUDIT_REC];
+  gate_load_pairs<AUDIT_REC / 2>(rec, v);
   const double w = v[14];
-  double E[3][3];  // E = R~^T R_ij
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) E[a][b] = __builtin_fma(Rm[6 + a], M[2][b], __builtin_fma(Rm[3 + a], M[1][b], Rm[a] * M[0][b]));
-  gate_log_so3(E, o.xi);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) o.xi[3 + a] = tij[a] - tm[a];
+  gate_innovation(M, tij, v, o.xi);
   const double sr = sqrt(2.0 * v[12]), st = sqrt(v[13]);
   const double s[6] = {sr, sr, sr, st, st, st};
   const double isr = 1.0 / sr, ist = 1.0 / st;
@@ -119,14 +59,13 @@ DPGO_HD void audit_record(const double M[3][3], const double tij[3], double S[6]
     }
   o.rho = __builtin_fma(-w, tr / 6.0, 1.0);
   bool okb;
-  double pb;
-  audit_cholesky(A, min_redundancy, o.testable, o.pmin);
-  audit_cholesky(B, 0.0, okb, pb);
+  gate_cholesky(A, min_redundancy, o.testable, o.pmin);
+  gate_cholesky(B, okb);
   double u[6], y[6];
 #pragma unroll
   for (int a = 0; a < 6; ++a) u[a] = y[a] = s[a] * o.xi[a];
-  audit_solve(A, u);
-  audit_solve(B, y);
+  gate_solve(A, u);
+  gate_solve(B, y);
   double dd = 0.0;
 #pragma unroll
   for (int a = 0; a < 6; ++a) dd = __builtin_fma(u[a], y[a], dd);
@@ -141,7 +80,7 @@ DPGO_HD void audit_record(const double M[3][3], const double tij[3], double S[6]
       double col[6];
 #pragma unroll
       for (int a = 0; a < 6; ++a) col[a] = S[a][b];
-      audit_solve(A, col);
+      gate_solve(A, col);
 #pragma unroll
       for (int a = 0; a < 6; ++a) X[a][b] = col[a];
     }

@@ -11,7 +11,7 @@
 #include <chrono>
 #include <unordered_map>
 
-#include "certify_internal.h"
+#include "closure_frame.h"
 #include "consistency_block.h"
 
 namespace dpgo {
@@ -70,17 +70,14 @@ namespace dpgo_cert {
 
 namespace {
 
+const ClosureCall PCM = {"pairwise_consistency", "candidate"};
+
 // the step behind one team's staged blocks: the segment records into the buffer of the call
-struct SegEpilogue : CovEpilogue {
+struct SegEpilogue : ClosureEpilogue {
   std::vector<int> ij;  // team poses (i, j) of every segment, the pair list handed to the path
   DevBuf<int> d_ij;
   double *rec = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ran = false;
-  ~SegEpilogue() override {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  SegEpilogue() : ClosureEpilogue(2) {}
   int run(const CovStage &st) override {
     const size_t n = ij.size() / 2;
     if ((size_t)st.num_pairs != n) {
@@ -94,7 +91,7 @@ struct SegEpilogue : CovEpilogue {
       }
     hipStream_t s = st.stream;
     if (d_ij.upload(ij, s)) { set_err("pairwise_consistency: device allocation failed (segment list)"); return DPGO_ERR; }
-    for (auto &e : ev) HIPC(hipEventCreate(&e));
+    if (ev.create()) return DPGO_ERR;
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 256);
     HIPC(hipEventRecord(ev[0], s));
     k_segments<<<grid, 256, 0, s>>>(st.Td, st.diag, st.pairs, d_ij.p, (int)n, rec);
@@ -102,42 +99,6 @@ struct SegEpilogue : CovEpilogue {
     HIPC(hipEventRecord(ev[1], s));
     ran = true;
     return DPGO_OK;
-  }
-};
-
-int pcm_refuse(const std::string &m) {
-  set_err("pairwise_consistency: " + m);
-  return DPGO_ERR;
-}
-
-// the team pose of (robot, pose) or a refusal that names the candidate
-int pcm_endpoint(dpgo_team_t *t, const std::vector<int> &offs, const char *team, int k, int r, int p, int *g) {
-  const auto l = t->id2local.find(r);
-  if (l == t->id2local.end())
-    return pcm_refuse("candidate " + std::to_string(k) + " names robot " + std::to_string(r) + ", which is not in team " + team);
-  if (p < 0 || p >= t->ag[l->second]->n)
-    return pcm_refuse("candidate " + std::to_string(k) + " names pose " + std::to_string(p) + " of robot " + std::to_string(r) +
-                      " of team " + team + ", outside [0, " + std::to_string(t->ag[l->second]->n) + ")");
-  *g = offs[l->second] + p;
-  return DPGO_OK;
-}
-
-std::vector<int> pose_offsets(dpgo_team_t *t) {
-  std::vector<int> offs(t->ag.size() + 1, 0);
-  for (size_t k = 0; k < t->ag.size(); ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
-  return offs;
-}
-
-struct Span {  // the device time between two points of a stream
-  hipEvent_t e[2] = {nullptr, nullptr};
-  ~Span() {
-    for (auto &x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  float ms() const {
-    float v = 0.f;
-    if (e[0] && e[1]) (void)hipEventElapsedTime(&v, e[0], e[1]);
-    return v;
   }
 };
 
@@ -152,53 +113,28 @@ extern "C" int dpgo_team_pairwise_consistency(dpgo_team_t *a, const double *T_a,
                                               long long max_nodes, double *d2, uint64_t *adj, int *members, int *size, int *proven,
                                               dpgo_covariance_t *res_a, dpgo_covariance_t *res_b) {
   // ---- the refusals of the call itself: on the host, before any device work, no output touched
-  if (!a || !b || !T_a || !T_b || !members || !size || !proven || !res_a || !res_b) return pcm_refuse("null argument");
-  if (num <= 0) return pcm_refuse("num must be positive, not " + std::to_string(num));
-  if (!cand) return pcm_refuse("null argument");
-  if (method != DPGO_GATE_DENSE && method != DPGO_GATE_SCHUR && method != DPGO_GATE_NESTED)
-    return pcm_refuse("method must be DPGO_GATE_DENSE, DPGO_GATE_SCHUR or DPGO_GATE_NESTED, not " + std::to_string(method));
+  if (!a || !b || !T_a || !T_b || !members || !size || !proven || !res_a || !res_b) return PCM.refuse("null argument");
+  if (num <= 0) return PCM.refuse("num must be positive, not " + std::to_string(num));
+  if (!cand) return PCM.refuse("null argument");
+  if (PCM.check_method(method)) return DPGO_ERR;
   if (!(quantile > 0.0 && quantile < 1.0)) {
     char buf[120];
     std::snprintf(buf, sizeof buf, "quantile must lie inside (0, 1), not %.6g", quantile);
-    return pcm_refuse(buf);
+    return PCM.refuse(buf);
   }
-  if (max_nodes < 0) return pcm_refuse("max_nodes must not be negative (0: no limit), not " + std::to_string(max_nodes));
-  if (check_team_local(a, "pairwise_consistency") || check_team_local(b, "pairwise_consistency")) return DPGO_ERR;
+  if (max_nodes < 0) return PCM.refuse("max_nodes must not be negative (0: no limit), not " + std::to_string(max_nodes));
+  if (check_team_local(a, PCM.name) || check_team_local(b, PCM.name)) return DPGO_ERR;
   if (a->device != b->device)
-    return pcm_refuse("the teams are on different devices (" + std::to_string(a->device) + " and " + std::to_string(b->device) + ")");
+    return PCM.refuse("the teams are on different devices (" + std::to_string(a->device) + " and " + std::to_string(b->device) + ")");
   const std::vector<int> offs_a = pose_offsets(a), offs_b = pose_offsets(b);
   const size_t K = (size_t)num, W = (K + 63) / 64;
   std::vector<int> pi(K), pj(K);
   std::vector<double> h_cand(dpgo::PCM_CAND * K, 0.0);
   for (int k = 0; k < num; ++k) {
     const dpgo_measurement_t &m = cand[k];
-    if (pcm_endpoint(a, offs_a, "A", k, m.r1, m.p1, &pi[k]) || pcm_endpoint(b, offs_b, "B", k, m.r2, m.p2, &pj[k])) return DPGO_ERR;
-    if (!(m.kappa > 0.0) || !(m.tau > 0.0) || !std::isfinite(m.kappa) || !std::isfinite(m.tau)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "candidate %d has kappa = %.6g, tau = %.6g: both must be positive", k, m.kappa, m.tau);
-      return pcm_refuse(buf);
-    }
-    // R~ in SO(3) by the rule of T (covariance_host_checks)
-    const double *R = m.R;
-    double orth = 0.0;
-    for (int p = 0; p < 3; ++p)
-      for (int q = 0; q < 3; ++q) {
-        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
-        orth = std::max(orth, std::fabs(d));
-      }
-    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
-    bool finite = true;
-    for (int q = 0; q < 9; ++q) finite = finite && std::isfinite(R[q]);
-    for (int q = 0; q < 3; ++q) finite = finite && std::isfinite(m.t[q]);
-    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "the measurement of candidate %d is not in SE(3) (|R R^T - I| = %.3g, det R = %.12g)", k, orth, det);
-      return pcm_refuse(buf);
-    }
-    double *c = h_cand.data() + dpgo::PCM_CAND * (size_t)k;
-    std::memcpy(c, m.R, sizeof m.R);
-    std::memcpy(c + 9, m.t, sizeof m.t);
-    c[12] = m.kappa; c[13] = m.tau;
+    if (PCM.endpoint(a, offs_a, k, m.r1, m.p1, &pi[k], "A") || PCM.endpoint(b, offs_b, k, m.r2, m.p2, &pj[k], "B") || PCM.check(k, m))
+      return DPGO_ERR;
+    pack_measurement(m, h_cand.data() + dpgo::PCM_CAND * (size_t)k);
   }
   // ---- the segments: per team the distinct ordered pose pairs in order of first use, and the table of their indices
   SegEpilogue epi_a, epi_b;
@@ -231,33 +167,28 @@ extern "C" int dpgo_team_pairwise_consistency(dpgo_team_t *a, const double *T_a,
       char buf[300];
       std::snprintf(buf, sizeof buf, "%d candidates with %zu + %zu segments stage %.0f bytes, %.0f are available on the device", num, na,
                     nb, staged, avail);
-      return pcm_refuse(buf);
+      return PCM.refuse(buf);
     }
   }
   DevBuf<double> d_cand, d_rec, d_d2;
   DevBuf<int> d_seg;
   DevBuf<unsigned long long> d_adj;
   if (d_cand.alloc(h_cand.size()) || d_rec.alloc(rec_doubles) || d_d2.alloc(K * K) || d_seg.alloc(K * K) || d_adj.alloc(K * W))
-    return pcm_refuse("device allocation failed (" + std::to_string(num) + " candidates, " + std::to_string(na + nb) + " segments)");
+    return PCM.refuse("device allocation failed (" + std::to_string(num) + " candidates, " + std::to_string(na + nb) + " segments)");
   epi_a.rec = d_rec.p;
   epi_b.rec = d_rec.p + (size_t)dpgo::PCM_SEG * std::max<size_t>(na, 1);
   // ---- each team's covariance path, with its own refusals and messages; a team that needs no segment is not asked
   dpgo_covariance_t ra, rb;
   std::memset(&ra, 0, sizeof ra);
   std::memset(&rb, 0, sizeof rb);
-  Span span_a, span_b, span_k;
-  auto path = [&](dpgo_team_t *t, const double *T, SegEpilogue &epi, dpgo_covariance_t *res, Span &span) -> int {
+  Events span_a(2), span_b(2), span_k(2);
+  auto path = [&](dpgo_team_t *t, const double *T, SegEpilogue &epi, dpgo_covariance_t *res, Events &span) -> int {
     const int np = (int)(epi.ij.size() / 2);
     if (np == 0) return DPGO_OK;
-    for (auto &e : span.e) HIPC(hipEventCreate(&e));
-    HIPC(hipEventRecord(span.e[0], t->stream));
-    const int rc = method == DPGO_GATE_NESTED
-                       ? marginal_covariances_nested_call(t, T, max_block, np, epi.ij.data(), nullptr, nullptr, res, &epi)
-                       : marginal_covariances_call(t, T, method == DPGO_GATE_SCHUR ? DPGO_COV_SCHUR : 0, np, epi.ij.data(), nullptr, nullptr,
-                                                   res, &epi);
-    if (rc != DPGO_OK) return rc;
-    if (!epi.ran) return pcm_refuse("the covariance path staged no blocks");
-    HIPC(hipEventRecord(span.e[1], t->stream));
+    if (span.create()) return DPGO_ERR;
+    HIPC(hipEventRecord(span[0], t->stream));
+    if (const int rc = PCM.path(t, T, method, max_block, np, epi.ij.data(), res, epi)) return rc;
+    HIPC(hipEventRecord(span[1], t->stream));
     HIPC(hipStreamSynchronize(t->stream));
     return DPGO_OK;
   };
@@ -270,13 +201,13 @@ extern "C" int dpgo_team_pairwise_consistency(dpgo_team_t *a, const double *T_a,
   static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "adjacency words");
   HIPC(hipMemcpyAsync(d_cand.p, h_cand.data(), sizeof(double) * h_cand.size(), hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d_seg.p, seg.data(), sizeof(int) * seg.size(), hipMemcpyHostToDevice, s));
-  for (auto &e : span_k.e) HIPC(hipEventCreate(&e));
-  HIPC(hipEventRecord(span_k.e[0], s));
+  if (span_k.create()) return DPGO_ERR;
+  HIPC(hipEventRecord(span_k[0], s));
   // at most one workgroup per CU of an MI355X, four tiles in flight each: the waves beyond stride over the rest
   const unsigned grid = (unsigned)std::min<size_t>((K * W + 3) / 4, 256);
   dpgo::k_consistency<<<grid, 256, 0, s>>>(d_cand.p, d_seg.p, epi_a.rec, epi_b.rec, num, (int)W, thr2, d_d2.p, d_adj.p);
   HIPC(hipGetLastError());
-  HIPC(hipEventRecord(span_k.e[1], s));
+  HIPC(hipEventRecord(span_k[1], s));
   if (d2) HIPC(hipMemcpyAsync(h_d2.data(), d_d2.p, sizeof(double) * K * K, hipMemcpyDeviceToHost, s));
   HIPC(hipMemcpyAsync(h_adj.data(), d_adj.p, sizeof(uint64_t) * K * W, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
@@ -288,13 +219,10 @@ extern "C" int dpgo_team_pairwise_consistency(dpgo_team_t *a, const double *T_a,
   const double clique_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing) {
-    float seg_a = 0.f, seg_b = 0.f;
-    if (epi_a.ran) (void)hipEventElapsedTime(&seg_a, epi_a.ev[0], epi_a.ev[1]);
-    if (epi_b.ran) (void)hipEventElapsedTime(&seg_b, epi_b.ev[0], epi_b.ev[1]);
     std::fprintf(stderr,
                  "pairwise_consistency: %d candidates, %zu + %zu segments, path A %.3f ms, path B %.3f ms, segment kernels %.3f + %.3f ms, "
                  "k_consistency %.3f ms, clique %.3f ms on the host (%d members, %s), %.0f bytes staged\n",
-                 num, na, nb, span_a.ms(), span_b.ms(), seg_a, seg_b, span_k.ms(), clique_ms, sz, prv ? "proven" : "not proven",
+                 num, na, nb, span_a.ms(), span_b.ms(), epi_a.ev.ms(), epi_b.ev.ms(), span_k.ms(), clique_ms, sz, prv ? "proven" : "not proven",
                  staged);
   }
   if (d2) std::memcpy(d2, h_d2.data(), sizeof(double) * K * K);
@@ -311,20 +239,15 @@ extern "C" int dpgo_team_pairwise_consistency(dpgo_team_t *a, const double *T_a,
 // forms them, for the tests -- rec receives 48 doubles per pair (R row-major, t, Sigma_rel), pairs as in the covariance calls.
 extern "C" int dpgo_internal_segment_records(dpgo_team_t *t, const double *T, int method, int max_block, int num_pairs, const int *pairs,
                                              double *rec, dpgo_covariance_t *res) {
-  if (!t || !T || !pairs || !rec || !res || num_pairs <= 0) return pcm_refuse("segment_records: null argument or no pairs");
+  if (!t || !T || !pairs || !rec || !res || num_pairs <= 0) return PCM.refuse("segment_records: null argument or no pairs");
   if (check_team_local(t, "pairwise_consistency")) return DPGO_ERR;
   HIPC(hipSetDevice(t->device));
   SegEpilogue epi;
   epi.ij.assign(pairs, pairs + 2 * (size_t)num_pairs);
   DevBuf<double> d_rec;
-  if (d_rec.alloc((size_t)dpgo::PCM_SEG * num_pairs)) return pcm_refuse("segment_records: device allocation failed");
+  if (d_rec.alloc((size_t)dpgo::PCM_SEG * num_pairs)) return PCM.refuse("segment_records: device allocation failed");
   epi.rec = d_rec.p;
-  const int rc = method == DPGO_GATE_NESTED
-                     ? marginal_covariances_nested_call(t, T, max_block, num_pairs, pairs, nullptr, nullptr, res, &epi)
-                     : marginal_covariances_call(t, T, method == DPGO_GATE_SCHUR ? DPGO_COV_SCHUR : 0, num_pairs, pairs, nullptr, nullptr, res,
-                                                 &epi);
-  if (rc != DPGO_OK) return rc;
-  if (!epi.ran) return pcm_refuse("the covariance path staged no blocks");
+  if (const int rc = PCM.path(t, T, method, max_block, num_pairs, pairs, res, epi)) return rc;
   HIPC(hipMemcpy(rec, d_rec.p, sizeof(double) * dpgo::PCM_SEG * (size_t)num_pairs, hipMemcpyDeviceToHost));
   return DPGO_OK;
 }

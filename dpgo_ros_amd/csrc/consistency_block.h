@@ -1,7 +1,7 @@
 // consistency_block.h -- the per-pair arithmetic of pairwise consistency maximisation: the loop through two
 // candidates and the two robots' own trajectories, its Jacobians, its covariance and the Mahalanobis distance of its residual.
-// It compiles for the device (k_consistency, consistency.hip: 16-byte global loads) and for the host with plain loads, so the
-// same text is checked on a machine without a GPU (tests/test_consistency_host.py).
+// It compiles for the device (k_consistency, consistency.hip) and for the host, with the loads of gate_block.h, so the same
+// text is checked on a machine without a GPU (tests/test_consistency_host.py).
 //
 // Every factor X = (R, t) is perturbed as R <- R Exp(phi), t <- t + delta, and so is the loop E.  For candidates p < q
 //   E = X1 X2 X3 X4,  X1 = Z_q^-1,  X2 = A = (T^A_{i_q})^-1 T^A_{i_p},  X3 = Z_p,  X4 = B = (T^B_{j_p})^-1 T^B_{j_q}.
@@ -12,12 +12,6 @@
 #include "gate_block.h"
 
 namespace dpgo {
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PCM_LOAD2(p, lo, hi) do { const double2 w_ = ld2(p); (lo) = w_.x; (hi) = w_.y; } while (0)
-#else
-#define PCM_LOAD2(p, lo, hi) do { (lo) = (p)[0]; (hi) = (p)[1]; } while (0)
-#endif
 
 constexpr int PCM_CAND = 16;  // doubles of a candidate record: R~ row-major (9), t~ (3), kappa, tau, two of padding
 constexpr int PCM_SEG = 48;   // doubles of a segment record: R row-major (9), t (3), Sigma_rel row-major (36)
@@ -32,9 +26,8 @@ struct PcmSeg {
 };
 
 DPGO_HD void pcm_load_cand(const double *rec, PcmCand &z) {
-  double v[14];
-#pragma unroll
-  for (int q = 0; q < 7; ++q) PCM_LOAD2(rec + 2 * q, v[2 * q], v[2 * q + 1]);
+  double v[GATE_MEAS];
+  gate_load_meas(rec, v);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -49,8 +42,7 @@ DPGO_HD void pcm_load_cand(const double *rec, PcmCand &z) {
 // point at a record)
 DPGO_HD void pcm_load_seg(const double *rec, bool present, PcmSeg &s) {
   double v[12];
-#pragma unroll
-  for (int q = 0; q < 6; ++q) PCM_LOAD2(rec + 2 * q, v[2 * q], v[2 * q + 1]);
+  gate_load_pairs<6>(rec, v);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -60,8 +52,7 @@ DPGO_HD void pcm_load_seg(const double *rec, bool present, PcmSeg &s) {
 }
 DPGO_HD void pcm_load_sigma(const double *rec, bool present, double rr[3][3], double rt[3][3], double tt[3][3]) {
   double v[36];
-#pragma unroll
-  for (int q = 0; q < 18; ++q) PCM_LOAD2(rec + 12 + 2 * q, v[2 * q], v[2 * q + 1]);
+  gate_load_pairs<18>(rec + 12, v);
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll

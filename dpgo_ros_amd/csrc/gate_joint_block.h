@@ -1,7 +1,7 @@
 // gate_joint_block.h -- the block arithmetic of the joint gate of a set of candidates: what k_joint_blocks and
-// k_joint_step (gate_joint.hip) do with the staged covariance blocks and with the rows of the factor.  It compiles for the
-// device (global loads through gp) and for the host with plain loads, so the same text is checked on a machine without a
-// GPU (tests/test_gate_joint_host.py).
+// k_joint_step (gate_joint.hip) do with the staged covariance blocks and with the rows of the factor, in the primitives of
+// gate_block.h (poses, Jacobians, sandwich, innovation, Cholesky, solves, distance).  It compiles for the device and for the
+// host, so the same text is checked on a machine without a GPU (tests/test_gate_joint_host.py).
 //
 // K candidates, candidate k joining the team poses i_k != j_k; R_ij, t_ij, J_i, J_j, xi and Sigma_meas of the gate (gate.hip).
 //   blocks       the distinct endpoint poses sorted, pose of rank a < b: the staged pair block a m - a (a + 1) / 2 + b - a - 1
@@ -19,14 +19,6 @@
 
 namespace dpgo {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define JOINT_LD(p, i) (gp(p)[i])
-#else
-#define JOINT_LD(p, i) ((p)[i])
-#endif
-
-constexpr int JOINT_REC = 16;  // doubles of a record: the four ints (i, j, rank of i, rank of j), R~ row-major (9), t~ (3), kappa, tau
-
 // the staged pair block of the poses of rank a < b among m
 DPGO_HD size_t joint_pair_index(int m, int a, int b) { return (size_t)a * m - (size_t)a * (a + 1) / 2 + (size_t)(b - a - 1); }
 
@@ -37,66 +29,7 @@ DPGO_HD void joint_load_sigma(const double *diag, const double *pairs, int m, in
 #pragma unroll
   for (int x = 0; x < 6; ++x)
 #pragma unroll
-    for (int y = 0; y < 6; ++y) B[x][y] = JOINT_LD(p, tr ? 6 * y + x : 6 * x + y);
-}
-
-// pose g of T: R[b][c] = T[(4 g + c) 3 + b], t[b] = T[(4 g + 3) 3 + b]
-DPGO_HD void joint_load_pose(const double *T, int g, double R[3][3], double t[3]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) R[b][c] = JOINT_LD(T, (size_t)12 * g + 3 * c + b);
-#pragma unroll
-  for (int b = 0; b < 3; ++b) t[b] = JOINT_LD(T, (size_t)12 * g + 9 + b);
-}
-
-// the relative pose (M = R_ij, tij) of the poses (Ri, ti), (Rj, tj) and its Jacobians; the arithmetic of gate_relative
-DPGO_HD void joint_jacobians(const double Ri[3][3], const double ti[3], const double Rj[3][3], const double tj[3], double M[3][3],
-                             double tij[3], double Ji[6][6], double Jj[6][6]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) M[a][b] = __builtin_fma(Ri[2][a], Rj[2][b], __builtin_fma(Ri[1][a], Rj[1][b], Ri[0][a] * Rj[0][b]));
-    tij[a] = __builtin_fma(Ri[2][a], tj[2] - ti[2], __builtin_fma(Ri[1][a], tj[1] - ti[1], Ri[0][a] * (tj[0] - ti[0])));
-  }
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = 0; b < 6; ++b) { Ji[a][b] = 0.0; Jj[a][b] = a == b && a < 3 ? 1.0 : 0.0; }
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      Ji[a][b] = -M[b][a];
-      Ji[3 + a][3 + b] = -Ri[b][a];
-      Jj[3 + a][3 + b] = Ri[b][a];
-    }
-  Ji[3][1] = -tij[2]; Ji[3][2] = tij[1];
-  Ji[4][0] = tij[2];  Ji[4][2] = -tij[0];
-  Ji[5][0] = -tij[1]; Ji[5][1] = tij[0];
-}
-
-// A += X B Y^T (6 x 6; the text of gate_sandwich, for both compilers)
-DPGO_HD void joint_sandwich(const double X[6][6], const double B[6][6], const double Y[6][6], double A[6][6]) {
-  double P[6][6];
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) s = __builtin_fma(X[a][k], B[k][b], s);
-      P[a][b] = s;
-    }
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-      double s = A[a][b];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) s = __builtin_fma(P[a][k], Y[b][k], s);
-      A[a][b] = s;
-    }
+    for (int y = 0; y < 6; ++y) B[x][y] = GATE_LD(p, tr ? 6 * y + x : 6 * x + y);
 }
 
 // one candidate's endpoints as a block needs them
@@ -113,13 +46,13 @@ DPGO_HD void joint_block(const double *diag, const double *pairs, int m, const J
     for (int b = 0; b < 6; ++b) G[a][b] = 0.0;
   double B[6][6];
   joint_load_sigma(diag, pairs, m, k.i, k.ri, l.ri, B);
-  joint_sandwich(k.Ji, B, l.Ji, G);
+  gate_sandwich(k.Ji, B, l.Ji, G);
   joint_load_sigma(diag, pairs, m, k.i, k.ri, l.rj, B);
-  joint_sandwich(k.Ji, B, l.Jj, G);
+  gate_sandwich(k.Ji, B, l.Jj, G);
   joint_load_sigma(diag, pairs, m, k.j, k.rj, l.ri, B);
-  joint_sandwich(k.Jj, B, l.Ji, G);
+  gate_sandwich(k.Jj, B, l.Ji, G);
   joint_load_sigma(diag, pairs, m, k.j, k.rj, l.rj, B);
-  joint_sandwich(k.Jj, B, l.Jj, G);
+  gate_sandwich(k.Jj, B, l.Jj, G);
 }
 
 // How the block of two different candidates is formed, by their endpoints and not by their indices, so that duplicated
@@ -149,74 +82,12 @@ DPGO_HD void joint_diagonal(const double G[6][6], double kappa, double tau, doub
     }
 }
 
-// xi = (Log(R~^T R_ij), t_ij - t~) from the 14 doubles of the measurement (R~ row-major, t~, kappa, tau)
-DPGO_HD void joint_innovation(const double M[3][3], const double tij[3], const double *v, double x[6]) {
-  const double *Rm = v, *tm = v + 9;
-  double E[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) E[a][b] = __builtin_fma(Rm[6 + a], M[2][b], __builtin_fma(Rm[3 + a], M[1][b], Rm[a] * M[0][b]));
-  gate_log_so3(E, x);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) x[3 + a] = tij[a] - tm[a];
-}
-
-// Cholesky of the symmetric S in place: the lower triangle receives L with the RECIPROCALS of its diagonal.  ok: every pivot
-// positive
-DPGO_HD void joint_cholesky(double S[6][6], bool &ok) {
-  ok = true;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double p = S[c][c];
-#pragma unroll
-    for (int q = 0; q < c; ++q) p = __builtin_fma(-S[c][q], S[c][q], p);
-    ok = ok && p > 0.0;
-    const double inv = 1.0 / sqrt(p);
-    S[c][c] = inv;
-#pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
-      double v = S[r][c];
-#pragma unroll
-      for (int q = 0; q < c; ++q) v = __builtin_fma(-S[r][q], S[c][q], v);
-      S[r][c] = v * inv;
-    }
-  }
-}
-
-// log det S = 2 sum log L_cc from the factor joint_cholesky leaves
+// log det S = 2 sum log L_cc from the factor gate_cholesky leaves
 DPGO_HD double joint_logdet(const double L[6][6]) {
   double s = 0.0;
 #pragma unroll
   for (int c = 0; c < 6; ++c) s -= log(L[c][c]);
   return 2.0 * s;
-}
-
-// y = L^-1 x with the factor joint_cholesky leaves; returns |y|^2
-DPGO_HD double joint_forward(const double L[6][6], const double x[6], double y[6]) {
-  double dd = 0.0;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double v = x[c];
-#pragma unroll
-    for (int q = 0; q < c; ++q) v = __builtin_fma(-L[c][q], y[q], v);
-    y[c] = v * L[c][c];
-    dd = __builtin_fma(y[c], y[c], dd);
-  }
-  return dd;
-}
-
-// d2 = x^T D^-1 x of the symmetric D, which is left alone; +inf for a non-positive pivot
-DPGO_HD double joint_distance(const double D[6][6], const double x[6]) {
-  double L[6][6], y[6];
-  bool ok;
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = 0; b < 6; ++b) L[a][b] = D[a][b];
-  joint_cholesky(L, ok);
-  const double dd = joint_forward(L, x, y);
-  return ok && dd >= 0.0 ? dd : (double)INFINITY;  // (a NaN is no distance either)
 }
 
 // G -= A B^T, A and B 36 doubles row-major in memory (one earlier column of the factor at this row and at the pivot's)
@@ -225,7 +96,7 @@ DPGO_HD void joint_subtract_product(const double *A, const double *B, double G[6
 #pragma unroll
   for (int x = 0; x < 6; ++x)
 #pragma unroll
-    for (int y = 0; y < 6; ++y) { a[x][y] = JOINT_LD(A, 6 * x + y); b[x][y] = JOINT_LD(B, 6 * x + y); }
+    for (int y = 0; y < 6; ++y) { a[x][y] = GATE_LD(A, 6 * x + y); b[x][y] = GATE_LD(B, 6 * x + y); }
 #pragma unroll
   for (int x = 0; x < 6; ++x)
 #pragma unroll
@@ -263,8 +134,69 @@ DPGO_HD double joint_row_update(double G[6][6], const double L[6][6], const doub
       D[a][b] = D[b][a] = s;
     }
   }
-  return joint_distance(D, x);
+  return gate_distance(D, x);
 }
+
+#if defined(__HIPCC__)
+
+// the endpoints of the record c (w0, w1: the ranks of its poses), their Jacobians, and the relative pose (Rij, tij)
+__device__ __forceinline__ void joint_ends(const double *T, const GateRec *c, JointEnds &e, double Rij[3][3], double tij[3]) {
+  typedef int v4i_t __attribute__((ext_vector_type(4)));
+  const v4i_t ids = *(const __attribute__((address_space(1))) v4i_t *)c;
+  e.i = ids.x; e.j = ids.y; e.ri = ids.z; e.rj = ids.w;
+  double Ri[3][3], Rj[3][3], ti[3], tj[3];
+  gate_load_pose(T, e.i, Ri, ti);
+  gate_load_pose(T, e.j, Rj, tj);
+  gate_jacobians(Ri, ti, Rj, tj, Rij, tij, e.Ji, e.Jj);
+}
+
+// The assembly of M = A Sigma A^T + R (order 6 K, leading dimension 6 K) and of xi, the body of a kernel of 256 lanes: one lane
+// per block (k, l) with k <= l, K^2 lanes of which the lower triangle rests, grid-stride.  fp64 in registers, no LDS, no
+// atomics: the lane writes the block and its transpose, so M is bitwise symmetric.  Which of the two a lane forms, (kk, ll),
+// follows from the endpoints (joint_orientation).  form(ek, ll, G): G = the block (kk, ll) less Sigma_meas, ek the ends of
+// record kk.  The lanes of the diagonal hand S = (G + G^T) / 2 + Sigma_meas and xi_k to diagonal(k, S, x) for what the kernel
+// writes beside them, and store both.
+template <class Form, class Diagonal>
+__device__ __forceinline__ void joint_assemble(const double *__restrict__ T, const GateRec *__restrict__ cand, int K, double *__restrict__ M,
+                                               double *__restrict__ xi, Form form, Diagonal diagonal) {
+  const size_t total = (size_t)K * K, ld = (size_t)6 * K;
+  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+    const int k = (int)(t / K), l = (int)(t % K);
+    if (l < k) continue;
+    typedef int v2i_t __attribute__((ext_vector_type(2)));
+    const v2i_t pk = *(const __attribute__((address_space(1))) v2i_t *)(cand + k), pl = *(const __attribute__((address_space(1))) v2i_t *)(cand + l);
+    const int way = joint_orientation(pk.x, pk.y, pl.x, pl.y);
+    const int kk = way < 0 ? l : k, ll = way < 0 ? k : l;
+    JointEnds ek;
+    double Rij[3][3], tij[3], G[6][6];
+    joint_ends(T, cand + kk, ek, Rij, tij);
+    form(ek, ll, G);
+    if (k != l) {
+      if (way == 0) joint_symmetrise(G);
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+          gp(M)[((size_t)6 * kk + a) * ld + (size_t)6 * ll + b] = G[a][b];
+          gp(M)[((size_t)6 * ll + b) * ld + (size_t)6 * kk + a] = G[a][b];
+        }
+      continue;
+    }
+    double v[GATE_MEAS], S[6][6], x[6];
+    gate_load_meas(cand[k].m, v);
+    joint_diagonal(G, v[12], v[13], S);
+    gate_innovation(Rij, tij, v, x);
+    diagonal(k, S, x);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int b = 0; b < 6; ++b) gp(M)[((size_t)6 * k + a) * ld + (size_t)6 * k + b] = S[a][b];
+      gp(xi)[(size_t)6 * k + a] = x[a];
+    }
+  }
+}
+
+#endif  // __HIPCC__
 
 // the candidate that a greedy step takes: the smaller d2, the lower index on ties; an index < 0 is no candidate
 DPGO_HD void joint_better(double d, int k, double &best, int &arg) {

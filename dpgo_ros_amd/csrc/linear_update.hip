@@ -26,43 +26,25 @@
 #include <algorithm>
 #include <chrono>
 
-#include "certify_internal.h"
-#include "covariance_frame.h"
+#include "closure_frame.h"
 #include "covariance_schur.h"
 #include "linear_update_block.h"
 
 namespace dpgo {
 
-// one closure on the device: team poses i != j, their ranks among the sorted distinct endpoints, and the measurement
-struct UpdCand {
-  int i, j, ri, rj;
-  double m[14];  // R~ row-major, t~, kappa, tau
-};
-static_assert(sizeof(UpdCand) == 8 * JOINT_REC, "UpdCand is read in 16-byte loads");
-
-__device__ __forceinline__ void upd_ends(const double *T, const UpdCand *c, JointEnds &e, double Rij[3][3], double tij[3]) {
-  typedef int v4i_t __attribute__((ext_vector_type(4)));
-  const v4i_t ids = *(const __attribute__((address_space(1))) v4i_t *)c;
-  e.i = ids.x; e.j = ids.y; e.ri = ids.z; e.rj = ids.w;
-  double Ri[3][3], Rj[3][3], ti[3], tj[3];
-  joint_load_pose(T, e.i, Ri, ti);
-  joint_load_pose(T, e.j, Rj, tj);
-  joint_jacobians(Ri, ti, Rj, tj, Rij, tij, e.Ji, e.Jj);
-}
-
 // One lane per (p, k), p the faster index, grid-stride: the closure's Jacobians from T, the two staged blocks Sigma_{p,i_k}
 // and Sigma_{p,j_k}, the two products, and the block B_p,k.  Consecutive lanes read consecutive staged blocks and store
 // consecutive runs of 48 bytes of every column of B.
 __global__ __launch_bounds__(256) void k_upd_b(const double *__restrict__ T, const double *__restrict__ blocks,
-                                               const UpdCand *__restrict__ cand, int N, int K, double *__restrict__ B) {
+                                               const GateRec *__restrict__ cand, int N, int K, double *__restrict__ B) {
   const size_t total = (size_t)N * K, ld = (size_t)6 * N;
   for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
     const int k = (int)(t / N), p = (int)(t % N);
     JointEnds e;
     double Rij[3][3], tij[3], Si[6][6], Sj[6][6], Bk[6][6];
-    upd_ends(T, cand + k, e, Rij, tij);
-    upd_load36(blocks + 36 * upd_block_index(N, e.ri, p), Si);
-    upd_load36(blocks + 36 * upd_block_index(N, e.rj, p), Sj);
+    joint_ends(T, cand + k, e, Rij, tij);
+    gate_load36(blocks + 36 * upd_block_index(N, e.ri, p), Si);
+    gate_load36(blocks + 36 * upd_block_index(N, e.rj, p), Sj);
     upd_b_block(Si, Sj, e.Ji, e.Jj, Bk);
     double *o = B + (size_t)6 * k * ld + (size_t)6 * p;
 #pragma unroll
@@ -72,50 +54,14 @@ __global__ __launch_bounds__(256) void k_upd_b(const double *__restrict__ T, con
   }
 }
 
-// One lane per block (k, l) with k <= l of M, K^2 lanes of which the lower triangle rests.  The lane reads B, writes the block
-// and its transpose; the lanes of the diagonal add Sigma_meas to the symmetrised block and write xi.
-__global__ __launch_bounds__(256) void k_upd_m(const double *__restrict__ T, const UpdCand *__restrict__ cand, int K, int N,
+// M by joint_assemble from B (upd_m_block), and xi; the lanes of the diagonal write nothing else
+__global__ __launch_bounds__(256) void k_upd_m(const double *__restrict__ T, const GateRec *__restrict__ cand, int K, int N,
                                                const double *__restrict__ B, double *__restrict__ M, double *__restrict__ xi) {
-  const size_t total = (size_t)K * K, ld = (size_t)6 * K, ldb = (size_t)6 * N;
-  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
-    const int k = (int)(t / K), l = (int)(t % K);
-    if (l < k) continue;
-    typedef int v2i_t __attribute__((ext_vector_type(2)));
-    const v2i_t pk = *(const __attribute__((address_space(1))) v2i_t *)(cand + k), pl = *(const __attribute__((address_space(1))) v2i_t *)(cand + l);
-    const int way = joint_orientation(pk.x, pk.y, pl.x, pl.y);
-    const int kk = way < 0 ? l : k, ll = way < 0 ? k : l;
-    JointEnds ek;
-    double Rij[3][3], tij[3], G[6][6];
-    upd_ends(T, cand + kk, ek, Rij, tij);
-    upd_m_block(B, ldb, ek, ll, G);
-    if (k != l) {
-      if (way == 0) joint_symmetrise(G);
-#pragma unroll
-      for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = 0; b < 6; ++b) {
-          gp(M)[((size_t)6 * kk + a) * ld + (size_t)6 * ll + b] = G[a][b];
-          gp(M)[((size_t)6 * ll + b) * ld + (size_t)6 * kk + a] = G[a][b];
-        }
-      continue;
-    }
-    const double *rec = (const double *)(cand + k);
-    double v[14], S[6][6], x[6];
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-      const double2 w = ld2(rec + 2 + 2 * q);
-      v[2 * q] = w.x;
-      v[2 * q + 1] = w.y;
-    }
-    joint_diagonal(G, v[12], v[13], S);
-    joint_innovation(Rij, tij, v, x);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-#pragma unroll
-      for (int b = 0; b < 6; ++b) gp(M)[((size_t)6 * k + a) * ld + (size_t)6 * k + b] = S[a][b];
-      gp(xi)[(size_t)6 * k + a] = x[a];
-    }
-  }
+  const size_t ldb = (size_t)6 * N;
+  joint_assemble(
+      T, cand, K, M, xi,
+      [=](const JointEnds &ek, int ll, double G[6][6]) __attribute__((always_inline)) { upd_m_block(B, ldb, ek, ll, G); },
+      [](int, const double[6][6], const double[6]) __attribute__((always_inline)) {});
 }
 
 // U = B G: B 6 N x 6 K and U column-major with leading dimension 6 N, G of order 6 K; one workgroup per 64 x 64 tile of U
@@ -125,7 +71,7 @@ __global__ __launch_bounds__(256) void k_upd_u(const double *__restrict__ B, con
 
 // z = G xi, one lane per row, the sum over the columns in index order (G is bitwise symmetric: the element (r, c) is read at
 // (c, r), consecutive lanes consecutive addresses), and xi_post = R z beside it
-__global__ __launch_bounds__(256) void k_upd_z(const double *__restrict__ G, const double *__restrict__ xi, const UpdCand *__restrict__ cand,
+__global__ __launch_bounds__(256) void k_upd_z(const double *__restrict__ G, const double *__restrict__ xi, const GateRec *__restrict__ cand,
                                                int n, double *__restrict__ z, double *__restrict__ xi_post) {
   for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
     double s = 0.0;
@@ -137,7 +83,7 @@ __global__ __launch_bounds__(256) void k_upd_z(const double *__restrict__ G, con
 }
 
 // the three figures by one lane: d2_joint = xi^T z and logdet_R in index order, logdet_M as k_cov_logdet left it in ld
-__global__ __launch_bounds__(64) void k_upd_scalars(const double *__restrict__ xi, const double *__restrict__ z, const UpdCand *__restrict__ cand,
+__global__ __launch_bounds__(64) void k_upd_scalars(const double *__restrict__ xi, const double *__restrict__ z, const GateRec *__restrict__ cand,
                                                     int K, const double *__restrict__ ld, double *__restrict__ scal) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   double d = 0.0, lr = 0.0;
@@ -150,16 +96,6 @@ __global__ __launch_bounds__(64) void k_upd_scalars(const double *__restrict__ x
   gp(scal)[1] = gp(ld)[0];
   gp(scal)[2] = lr;
   gp(scal)[3] = 0.0;
-}
-
-// six consecutive doubles at a 16-byte aligned address
-__device__ __forceinline__ void upd_load6(const double *p, double v[6]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const double2 w = ld2(p + 2 * q);
-    v[2 * q] = w.x;
-    v[2 * q + 1] = w.y;
-  }
 }
 
 // The reduction over the 6 K columns, one wave per pose and, in a second range of waves, per requested pair.  Lane l takes
@@ -182,8 +118,8 @@ __global__ __launch_bounds__(256) void k_upd_finish(const double *__restrict__ T
     for (int q = 0; q < UPD_SUMS; ++q) acc[q] = 0.0;
     for (int c = lane; c < n; c += 64) {
       double u[6], b[6];
-      upd_load6(U + (size_t)c * ld + (size_t)6 * p, u);
-      upd_load6(B + (size_t)c * ld + (size_t)6 * p, b);
+      gate_load_pairs<3>(U + (size_t)c * ld + (size_t)6 * p, u);
+      gate_load_pairs<3>(B + (size_t)c * ld + (size_t)6 * p, b);
       upd_accumulate(u, b, gp(z)[c], acc);
     }
 #pragma unroll
@@ -193,7 +129,7 @@ __global__ __launch_bounds__(256) void k_upd_finish(const double *__restrict__ T
     if (lane != 0) return;
     double Sn[6][6], dx[6], R[3][3], t[3], Rn[3][3], tn[3], P[12];
     upd_close_pose(diag + (size_t)36 * p, acc, Sn, dx);
-    joint_load_pose(T, p, R, t);
+    gate_load_pose(T, p, R, t);
     upd_retract(R, t, dx, Rn, tn);
     upd_store_pose(Rn, tn, P);
 #pragma unroll
@@ -213,8 +149,8 @@ __global__ __launch_bounds__(256) void k_upd_finish(const double *__restrict__ T
   for (int x = 0; x < 36; ++x) acc[x] = 0.0;
   for (int c = lane; c < n; c += 64) {
     double u[6], b[6];
-    upd_load6(U + (size_t)c * ld + (size_t)6 * p, u);
-    upd_load6(B + (size_t)c * ld + (size_t)6 * q, b);
+    gate_load_pairs<3>(U + (size_t)c * ld + (size_t)6 * p, u);
+    gate_load_pairs<3>(B + (size_t)c * ld + (size_t)6 * q, b);
     upd_accumulate_pair(u, b, acc);
   }
 #pragma unroll
@@ -232,22 +168,19 @@ namespace dpgo_cert {
 
 namespace {
 
+const ClosureCall UPDATE = {"linear_update", "closure"};
+
 // the step behind a covariance path's staged blocks: upload the records, form B and M, invert, multiply, reduce, queue the
 // copy of the outputs
-struct UpdateEpilogue : CovEpilogue {
-  std::vector<UpdCand> cand;
+struct UpdateEpilogue : ClosureEpilogue {
+  std::vector<GateRec> cand;  // w0, w1: the ranks of i and j among the endpoints
   std::vector<int> user_pairs;  // the caller's pairs, behind the N m blocks of the call
   int m = 0, N = 0;
-  DevBuf<UpdCand> d_cand;
+  DevBuf<GateRec> d_cand;
   DevBuf<double> d_B, d_U, d_M, d_W, d_G, d_work, d_out;
   DevBuf<int> d_pairs;
   std::vector<double> h_out;  // T' (12 N), dx (6 N), Sigma' diagonal (36 N), Sigma' pairs (36 P), xi (6 K), xi_post (6 K), 4 figures
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool ran = false;
-  ~UpdateEpilogue() override {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  UpdateEpilogue() : ClosureEpilogue(7) {}
   size_t K() const { return cand.size(); }
   size_t P() const { return user_pairs.size() / 2; }
   size_t out_doubles() const { return (size_t)54 * N + 36 * P() + 12 * K() + 4; }
@@ -264,8 +197,7 @@ struct UpdateEpilogue : CovEpilogue {
       set_err(buf);
       return DPGO_ERR;
     }
-    for (auto &e : ev) HIPC(hipEventCreate(&e));
-    return DPGO_OK;
+    return ev.create();
   }
   int run(const CovStage &st) override {
     const size_t k = K(), np = P();
@@ -273,8 +205,8 @@ struct UpdateEpilogue : CovEpilogue {
       set_err("linear_update: the staged blocks are not the rectangular set of the endpoints");
       return DPGO_ERR;
     }
-    for (const UpdCand &c : cand)
-      if (c.i < 0 || c.i >= N || c.j < 0 || c.j >= N || c.ri < 0 || c.ri >= m || c.rj < 0 || c.rj >= m || c.ri == c.rj) {
+    for (const GateRec &c : cand)
+      if (c.i < 0 || c.i >= N || c.j < 0 || c.j >= N || c.w0 < 0 || c.w0 >= m || c.w1 < 0 || c.w1 >= m || c.w0 == c.w1) {
         set_err("linear_update: a closure lies outside the staged blocks");
         return DPGO_ERR;
       }
@@ -285,7 +217,7 @@ struct UpdateEpilogue : CovEpilogue {
       }
     hipStream_t s = st.stream;
     const int n = (int)(6 * k);
-    HIPC(hipMemcpyAsync(d_cand.p, cand.data(), sizeof(UpdCand) * k, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(d_cand.p, cand.data(), sizeof(GateRec) * k, hipMemcpyHostToDevice, s));
     if (np) HIPC(hipMemcpyAsync(d_pairs.p, user_pairs.data(), sizeof(int) * 2 * np, hipMemcpyHostToDevice, s));
     double *oT = d_out.p, *odx = oT + (size_t)12 * N, *odiag = odx + (size_t)6 * N, *opairs = odiag + (size_t)36 * N;
     double *oxi = opairs + 36 * np, *opost = oxi + 6 * k, *oscal = opost + 6 * k;
@@ -326,11 +258,6 @@ struct UpdateEpilogue : CovEpilogue {
   }
 };
 
-int update_refuse(const std::string &msg) {
-  set_err("linear_update: " + msg);
-  return DPGO_ERR;
-}
-
 }  // namespace
 
 }  // namespace dpgo_cert
@@ -343,77 +270,31 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
                                        dpgo_covariance_t *res) {
   const auto t_begin = std::chrono::steady_clock::now();
   // ---- the refusals of the call itself: on the host, before any device work, no output touched
-  if (!t || !T || !res || !T_new || !delta || !cov_diag || !xi || !xi_post || !scalars) return update_refuse("null argument");
-  if (num <= 0) return update_refuse("num must be positive, not " + std::to_string(num));
-  if (!closures) return update_refuse("null argument");
-  if (num_pairs < 0) return update_refuse("num_pairs must not be negative, not " + std::to_string(num_pairs));
-  if (num_pairs > 0 && (!pairs || !cov_pairs)) return update_refuse("null argument");
-  if (method != DPGO_GATE_DENSE && method != DPGO_GATE_SCHUR && method != DPGO_GATE_NESTED)
-    return update_refuse("method must be DPGO_GATE_DENSE, DPGO_GATE_SCHUR or DPGO_GATE_NESTED, not " + std::to_string(method));
-  if (check_team_local(t, "linear_update")) return DPGO_ERR;
-  const int na = (int)t->ag.size();
-  std::vector<int> offs(na + 1, 0);
-  for (int k = 0; k < na; ++k) offs[k + 1] = offs[k] + t->ag[k]->n;
-  const int N = offs[na];
+  if (!t || !T || !res || !T_new || !delta || !cov_diag || !xi || !xi_post || !scalars) return UPDATE.refuse("null argument");
+  if (num <= 0) return UPDATE.refuse("num must be positive, not " + std::to_string(num));
+  if (!closures) return UPDATE.refuse("null argument");
+  if (num_pairs < 0) return UPDATE.refuse("num_pairs must not be negative, not " + std::to_string(num_pairs));
+  if (num_pairs > 0 && (!pairs || !cov_pairs)) return UPDATE.refuse("null argument");
+  if (UPDATE.check_method(method)) return DPGO_ERR;
+  if (check_team_local(t, UPDATE.name)) return DPGO_ERR;
+  const std::vector<int> offs = pose_offsets(t);
+  const int N = offs.back();
   UpdateEpilogue epi;
   epi.N = N;
   epi.cand.resize(num);
-  std::vector<int> poses;  // the endpoints, then sorted and distinct
   for (int k = 0; k < num; ++k) {
-    const dpgo_measurement_t &c = closures[k];
     int g[2];
-    for (int e = 0; e < 2; ++e) {
-      const int r = e ? c.r2 : c.r1, p = e ? c.p2 : c.p1;
-      const auto l = t->id2local.find(r);
-      if (l == t->id2local.end()) return update_refuse("closure " + std::to_string(k) + " names robot " + std::to_string(r) + ", which is not in the team");
-      if (p < 0 || p >= t->ag[l->second]->n)
-        return update_refuse("closure " + std::to_string(k) + " names pose " + std::to_string(p) + " of robot " + std::to_string(r) +
-                             ", outside [0, " + std::to_string(t->ag[l->second]->n) + ")");
-      g[e] = offs[l->second] + p;
-    }
-    if (g[0] == g[1]) return update_refuse("closure " + std::to_string(k) + " joins a pose to itself");
-    if (!(c.kappa > 0.0) || !(c.tau > 0.0) || !std::isfinite(c.kappa) || !std::isfinite(c.tau)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "closure %d has kappa = %.6g, tau = %.6g: both must be positive", k, c.kappa, c.tau);
-      return update_refuse(buf);
-    }
-    // R~ in SO(3) by the rule of T (covariance_host_checks); row-major here, which changes neither figure
-    const double *R = c.R;
-    double orth = 0.0;
-    for (int p = 0; p < 3; ++p)
-      for (int q = 0; q < 3; ++q) {
-        const double d = R[3 * p] * R[3 * q] + R[3 * p + 1] * R[3 * q + 1] + R[3 * p + 2] * R[3 * q + 2] - (p == q ? 1.0 : 0.0);
-        orth = std::max(orth, std::fabs(d));
-      }
-    const double det = R[0] * (R[4] * R[8] - R[7] * R[5]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
-    bool finite = true;
-    for (int q = 0; q < 9; ++q) finite = finite && std::isfinite(R[q]);
-    for (int q = 0; q < 3; ++q) finite = finite && std::isfinite(c.t[q]);
-    if (!finite || !(orth <= 1e-8) || !(std::fabs(det - 1.0) <= 1e-8)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "the measurement of closure %d is not in SE(3) (|R R^T - I| = %.3g, det R = %.12g)", k, orth, det);
-      return update_refuse(buf);
-    }
-    UpdCand &uc = epi.cand[k];
-    std::memset(&uc, 0, sizeof uc);
-    uc.i = g[0]; uc.j = g[1];
-    std::memcpy(uc.m, c.R, sizeof c.R);
-    std::memcpy(uc.m + 9, c.t, sizeof c.t);
-    uc.m[12] = c.kappa; uc.m[13] = c.tau;
-    poses.push_back(g[0]);
-    poses.push_back(g[1]);
+    if (UPDATE.endpoints(t, offs, k, closures[k], g) || UPDATE.check(k, closures[k])) return DPGO_ERR;
+    GateRec &c = epi.cand[k];
+    std::memset(&c, 0, sizeof c);
+    c.i = g[0]; c.j = g[1];
+    pack_measurement(closures[k], c.m);
   }
   for (int k = 0; k < 2 * num_pairs; ++k)
     if (pairs[k] < 0 || pairs[k] >= N)
-      return update_refuse("pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " + std::to_string(N) + ")");
-  std::sort(poses.begin(), poses.end());
-  poses.erase(std::unique(poses.begin(), poses.end()), poses.end());
-  const int m = (int)poses.size();
-  epi.m = m;
-  for (UpdCand &uc : epi.cand) {
-    uc.ri = (int)(std::lower_bound(poses.begin(), poses.end(), uc.i) - poses.begin());
-    uc.rj = (int)(std::lower_bound(poses.begin(), poses.end(), uc.j) - poses.begin());
-  }
+      return UPDATE.refuse("pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " + std::to_string(N) + ")");
+  const std::vector<int> poses = rank_endpoints(epi.cand);
+  const int m = epi.m = (int)poses.size();
   const size_t K = (size_t)num, nb = (size_t)N * m, np = nb + (size_t)num_pairs;
   HIPC(hipSetDevice(t->device));
   {
@@ -422,7 +303,7 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
     const double blocks = 288.0 * (double)np, bu = 288.0 * (double)N * (double)K, mat = 288.0 * (double)K * (double)K;
     const double need = blocks + UpdateEpilogue::bytes(N, (double)K, num_pairs);
     double avail = 0.0;
-    if (!cov_device_avail(t, &avail)) return update_refuse("hipMemGetInfo failed");
+    if (UPDATE.device_avail(t, &avail)) return DPGO_ERR;
     if (need > avail || np > (size_t)INT32_MAX || 36 * K * K > (size_t)1 << 40 || 6 * K > (size_t)INT32_MAX / 2) {
       char buf[480];
       std::snprintf(buf, sizeof buf,
@@ -430,7 +311,7 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
                     "%.0f bytes (%.0f + 2 x %.0f + 3 x %.0f and the working arrays), %.0f are available on the device; the pair blocks must "
                     "number at most %d",
                     num, m, N, np, 6 * K, need, blocks, bu, mat, avail, INT32_MAX);
-      return update_refuse(buf);
+      return UPDATE.refuse(buf);
     }
   }
   // the rectangular set: block a N + p = Sigma_{p, e_a} (the paths check a pair for range only: p = e_a and p = 0 pass, the
@@ -442,19 +323,11 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
   all.insert(all.end(), pairs, pairs + 2 * (size_t)num_pairs);
   epi.user_pairs.assign(pairs, pairs + 2 * (size_t)num_pairs);
   if (epi.alloc()) return DPGO_ERR;
-  // ---- the covariance path, with its own refusals and messages; its blocks stay on the device for the epilogue
-  const int rc = method == DPGO_GATE_NESTED ? marginal_covariances_nested_call(t, T, max_block, (int)np, all.data(), nullptr, nullptr, res, &epi)
-                                            : marginal_covariances_call(t, T, method == DPGO_GATE_SCHUR ? DPGO_COV_SCHUR : 0, (int)np, all.data(),
-                                                                        nullptr, nullptr, res, &epi);
-  if (rc != DPGO_OK) return rc;
-  if (!epi.ran) {  // (a team of the anchor alone has no two poses to join: the endpoint checks have refused already)
-    std::memset(res, 0, sizeof *res);
-    return update_refuse("the covariance path staged no blocks");
-  }
+  if (const int rc = UPDATE.path(t, T, method, max_block, (int)np, all.data(), res, epi)) return rc;
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing) {
-    float ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int q = 0; q < 6; ++q) HIPC(hipEventElapsedTime(&ms[q], epi.ev[q], epi.ev[q + 1]));
+    float ms[6];
+    for (int q = 0; q < 6; ++q) ms[q] = epi.ev.ms(q, q + 1);
     const double whole = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     std::fprintf(stderr, "linear_update: %d closures on %d of %d poses (%zu pair blocks), k_upd_b %.3f ms, k_upd_m %.3f ms, inverse %.3f ms, "
                          "k_upd_u %.3f ms, k_upd_z and figures %.3f ms, k_upd_finish %.3f ms, the whole call %.3f ms\n",

@@ -1,7 +1,7 @@
 // linear_update_block.h -- the block arithmetic of the first-order update of a trajectory and its covariances for a set of
 // new closures: what k_upd_b, k_upd_m and k_upd_finish (linear_update.hip) do with the staged covariance blocks,
-// with B and with U.  In the idiom of gate_joint_block.h: statically indexed 6 x 6 arrays, global loads through gp() / ld2 on
-// the device and plain loads on the host, so the same text is checked on a machine without a GPU
+// with B and with U.  In the idiom of gate_block.h and gate_joint_block.h, whose primitives it uses: statically indexed 6 x 6
+// arrays, compiled for the device and for the host, so the same text is checked on a machine without a GPU
 // (tests/test_linear_update_host.py).
 //
 // T, Sigma, the perturbation, J_i, J_j, xi (no Log-Jacobian) and Sigma_meas are the gate's (gate.hip); A and R are the joint
@@ -24,14 +24,6 @@ namespace dpgo {
 // the staged block of (pose p, endpoint of rank a) among N poses
 DPGO_HD size_t upd_block_index(int N, int a, int p) { return (size_t)a * N + (size_t)p; }
 
-// X = the 36 doubles at p, row-major
-DPGO_HD void upd_load36(const double *p, double X[6][6]) {
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = 0; b < 6; ++b) X[a][b] = JOINT_LD(p, 6 * a + b);
-}
-
 // Bk = Si Ji^T + Sj Jj^T: element [a][c] the twelve terms Si[a][y] Ji[c][y], y = 0 .. 5, then Sj[a][y] Jj[c][y]
 DPGO_HD void upd_b_block(const double Si[6][6], const double Sj[6][6], const double Ji[6][6], const double Jj[6][6], double Bk[6][6]) {
 #pragma unroll
@@ -52,7 +44,7 @@ DPGO_HD void upd_load_b(const double *B, size_t ld, int p, int l, double X[6][6]
 #pragma unroll
   for (int c = 0; c < 6; ++c)
 #pragma unroll
-    for (int a = 0; a < 6; ++a) X[a][c] = JOINT_LD(B, ((size_t)6 * l + c) * ld + (size_t)6 * p + a);
+    for (int a = 0; a < 6; ++a) X[a][c] = GATE_LD(B, ((size_t)6 * l + c) * ld + (size_t)6 * p + a);
 }
 
 // G = J_i^k B_{i_k,l} + J_j^k B_{j_k,l}: element [a][c] the twelve terms Ji[a][y] Bi[y][c], then Jj[a][y] Bj[y][c]
@@ -101,7 +93,7 @@ DPGO_HD void upd_close_pose(const double *Spp, const double acc[UPD_SUMS], doubl
 #pragma unroll
   for (int a = 0; a < 6; ++a)
 #pragma unroll
-    for (int c = a; c < 6; ++c, ++q) Sn[a][c] = Sn[c][a] = JOINT_LD(Spp, 6 * a + c) - acc[q];
+    for (int c = a; c < 6; ++c, ++q) Sn[a][c] = Sn[c][a] = GATE_LD(Spp, 6 * a + c) - acc[q];
 #pragma unroll
   for (int a = 0; a < 6; ++a) dx[a] = -acc[UPD_TRI + a];
 }

@@ -50,9 +50,9 @@ int main(int argc, char **argv) {
     JointEnds &e = ends[k];
     e.i = ids[0]; e.j = ids[1]; e.ri = ids[2]; e.rj = ids[3];
     double Ri[3][3], Rj[3][3], ti[3], tj[3];
-    joint_load_pose(T, e.i, Ri, ti);
-    joint_load_pose(T, e.j, Rj, tj);
-    joint_jacobians(Ri, ti, Rj, tj, *(double(*)[3][3])&Rij[9 * k], &tij[3 * k], e.Ji, e.Jj);
+    gate_load_pose(T, e.i, Ri, ti);
+    gate_load_pose(T, e.j, Rj, tj);
+    gate_jacobians(Ri, ti, Rj, tj, *(double(*)[3][3])&Rij[9 * k], &tij[3 * k], e.Ji, e.Jj);
   }
   for (int k = 0; k < K; ++k)
     for (int l = k; l < K; ++l) {
@@ -69,12 +69,12 @@ int main(int argc, char **argv) {
       const double *v = recs + 16 * k + 2;
       double S[6][6], x[6];
       joint_diagonal(Gb, v[12], v[13], S);
-      joint_innovation(*(double(*)[3][3])&Rij[9 * k], &tij[3 * k], v, x);
+      gate_innovation(*(double(*)[3][3])&Rij[9 * k], &tij[3 * k], v, x);
       for (int a = 0; a < 6; ++a) {
         for (int b = 0; b < 6; ++b) M[(6 * k + a) * ld + 6 * k + b] = D[36 * k + 6 * a + b] = S[a][b];
         xi[6 * k + a] = xc[6 * k + a] = x[a];
       }
-      d2[k] = d2c[k] = joint_distance(S, x);
+      d2[k] = d2c[k] = gate_distance(S, x);
     }
   for (int s = 0; s < K; ++s) {  // greedy
     double dp = INFINITY;
@@ -85,8 +85,8 @@ int main(int argc, char **argv) {
     double L[6][6], y[6];
     bool ok;
     std::memcpy(L, &D[36 * p], sizeof L);
-    joint_cholesky(L, ok);
-    (void)joint_forward(L, &xc[6 * p], y);
+    gate_cholesky(L, ok);
+    (void)gate_forward(L, &xc[6 * p], y);
     state[p] = 1;
     rank[p] = s;
     for (int r = 0; r < K; ++r) {

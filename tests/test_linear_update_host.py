@@ -51,13 +51,13 @@ int main(int argc, char **argv) {
     JointEnds &e = ends[k];
     e.i = ids[0]; e.j = ids[1]; e.ri = ids[2]; e.rj = ids[3];
     double Ri[3][3], Rj[3][3], ti[3], tj[3];
-    joint_load_pose(T, e.i, Ri, ti);
-    joint_load_pose(T, e.j, Rj, tj);
-    joint_jacobians(Ri, ti, Rj, tj, *(double(*)[3][3])&Rij[9 * k], &tij[3 * k], e.Ji, e.Jj);
+    gate_load_pose(T, e.i, Ri, ti);
+    gate_load_pose(T, e.j, Rj, tj);
+    gate_jacobians(Ri, ti, Rj, tj, *(double(*)[3][3])&Rij[9 * k], &tij[3 * k], e.Ji, e.Jj);
     for (int p = 0; p < N; ++p) {
       double Si[6][6], Sj[6][6], Bk[6][6];
-      upd_load36(rect + 36 * upd_block_index(N, e.ri, p), Si);
-      upd_load36(rect + 36 * upd_block_index(N, e.rj, p), Sj);
+      gate_load36(rect + 36 * upd_block_index(N, e.ri, p), Si);
+      gate_load36(rect + 36 * upd_block_index(N, e.rj, p), Sj);
       upd_b_block(Si, Sj, e.Ji, e.Jj, Bk);
       for (int c = 0; c < 6; ++c)
         for (int a = 0; a < 6; ++a) B[(6 * (size_t)k + c) * ld + 6 * p + a] = Bk[a][c];
@@ -78,7 +78,7 @@ int main(int argc, char **argv) {
       const double *v = recs + 16 * k + 2;
       double S[6][6], x[6];
       joint_diagonal(Gb, v[12], v[13], S);
-      joint_innovation(*(double(*)[3][3])&Rij[9 * k], &tij[3 * k], v, x);
+      gate_innovation(*(double(*)[3][3])&Rij[9 * k], &tij[3 * k], v, x);
       for (int a = 0; a < 6; ++a) {
         for (int b = 0; b < 6; ++b) M[(6 * k + a) * n + 6 * k + b] = S[a][b];
         xi[6 * k + a] = x[a];
@@ -134,7 +134,7 @@ int main(int argc, char **argv) {
     for (size_t c = 0; c < n; ++c) upd_accumulate(&U[c * ld + 6 * p], &B[c * ld + 6 * p], z[c], acc);
     double Sn[6][6], d[6], Rp[3][3], tp[3], Rn[3][3], tn[3];
     upd_close_pose(diag + 36 * p, acc, Sn, d);
-    joint_load_pose(T, p, Rp, tp);
+    gate_load_pose(T, p, Rp, tp);
     upd_retract(Rp, tp, d, Rn, tn);
     upd_store_pose(Rn, tn, &Tn[12 * p]);
     std::memcpy(&Sd[36 * p], Sn, sizeof Sn);
