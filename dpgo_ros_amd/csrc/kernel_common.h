@@ -24,6 +24,7 @@
 #include "device_math.h"
 #include "dpgo_dev.h"
 #include "kernels.h"
+#include "nesterov_step.h"
 
 namespace dpgo {
 
@@ -225,15 +226,7 @@ __device__ __forceinline__ void g_row(const AgentDev *__restrict__ agents, const
 __device__ __forceinline__ void advance_agent(const AgentDev &ag, int accel, int num_robots, int restart_interval,
                                               int inc = 1) {
   NestState ns = *ag.nest;
-  if (accel) {
-    const double Nr = (double)num_robots;
-    const bool restart = ((ns.iter + 2) % restart_interval) == 0;
-    if (restart) { ns.gamma = 0; ns.alpha = 0; }
-    else {
-      ns.gamma = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * ns.gamma * ns.gamma)) / (2.0 * Nr);
-      ns.alpha = 1.0 / (ns.gamma * Nr);
-    }
-  }
+  if (accel) nest_books(ns, (double)num_robots, restart_interval);
   ns.iter += inc;
   *ag.nest = ns;
 }
@@ -447,7 +440,7 @@ __device__ __forceinline__ void nest_pre_body(const AgentDev *__restrict__ agent
   const bool optimizing = (ai == selected);
   const NestState ns = *ag.nest;
   const double Nr = (double)num_robots;
-  const double gamma = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * ns.gamma * ns.gamma)) / (2.0 * Nr);
+  const double gamma = nest_gamma_step(ns.gamma, Nr);
   const double alpha = 1.0 / (gamma * Nr);
   const bool restart = ((ns.iter + 2) % restart_interval) == 0;  // iter is pre-increment: (iter+1)+1
   if (bx == 0 && tid == 0) ag.scal[6] = gamma;  // read by the fused RGD tail instead of the (mutable) NestState
@@ -463,9 +456,7 @@ __device__ __forceinline__ void nest_pre_body(const AgentDev *__restrict__ agent
   if (tid < cnt) {
     tile_get<R>(TX, tid, x);
     tile_get<R>(TV, tid, v);
-#pragma unroll
-    for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - alpha) * x[i] + alpha * v[i];
-    polar_inplace<R>(y);
+    lookahead_map<R>(x, v, alpha, y);
     if (!optimizing && !restart) {
       polar_inplace<R>(v);
 #pragma unroll

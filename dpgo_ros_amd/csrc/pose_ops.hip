@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64) void k_nest_post(const AgentDev *__restrict__ a
   const int cnt = min(64, ag.n - j0);
   const NestState ns = *ag.nest;
   const double Nr = (double)num_robots;
-  const double gamma = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * ns.gamma * ns.gamma)) / (2.0 * Nr);
+  const double gamma = nest_gamma_step(ns.gamma, Nr);
   const bool restart = ((ns.iter + 2) % restart_interval) == 0;
   __shared__ Tile<R> TX, TV, TY;
   if (restart) {

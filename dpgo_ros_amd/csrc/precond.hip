@@ -216,16 +216,15 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
       // the NestState describes iteration k-1 (it is advanced by the next k_eval_stats): gamma of this iteration,
       // and gamma / alpha / selected agent of iteration k+1 for the look-ahead Nesterov step of the epilogue
       const NestState ns = nest_all ? nest_all[agent_index] : *ag.nest;  // (one round trip less than through the descriptor)
-      const double Nr = (double)num_robots;
       // restart iterations are part of the uniform sequence: iteration k restarts when (iter + 2) % interval == 0
       // (the test of k_nest_pre / advance_agent); its step is a plain RGD step from X with V = Y = X afterwards
       // and gamma = 0 for what follows.  (The reference also runs -- and discards -- an accelerated solve first; it
       // has no observable effect and is skipped here.)
-      restart_now = ((ns.iter + 2) % restart_interval) == 0;
-      restart_next = ((ns.iter + 3) % restart_interval) == 0;
-      nest_gamma = restart_now ? 0.0 : (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * ns.gamma * ns.gamma)) / (2.0 * Nr);
-      const double g2 = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * nest_gamma * nest_gamma)) / (2.0 * Nr);
-      ahead_alpha = 1.0 / (g2 * Nr);
+      const NestAhead nn = nest_ahead(ns, num_robots, restart_interval);
+      restart_now = nn.restart_now;
+      restart_next = nn.restart_next;
+      nest_gamma = nn.nest_gamma;
+      ahead_alpha = nn.ahead_alpha;
       ahead_opt = team->sched[(team->iter + 1) % team->sched_len] == sel_cur(team, sel);
     } else {
       nest_gamma = ag.scal[6];
@@ -426,9 +425,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
         // V of an agent that does not optimize is re-projected by the reference (V = proj(V)); V left its last update
         // as a polar factor, so the projection is the identity up to round-off and V is neither read nor written here
         double y[4 * R];
-#pragma unroll
-        for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - ahead_alpha) * la_x[i] + ahead_alpha * la_v[i];
-        polar_inplace<R>(y);
+        lookahead_map<R>(la_x, la_v, ahead_alpha, y);
         if (la_status && !la_opt) {
           double r2 = 0;
 #pragma unroll
@@ -502,9 +499,7 @@ __global__ __launch_bounds__(256) void k_precond(const AgentDev *__restrict__ ag
           if (la_status && !ahead_opt) gp(ag.part)[PART_D + (lp ? pj1 : pj0)] = 0.0;
         } else {
           double y[4 * R];
-#pragma unroll
-          for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - ahead_alpha) * x[i] + ahead_alpha * v[i];
-          polar_inplace<R>(y);
+          lookahead_map<R>(x, v, ahead_alpha, y);
           PC_STAMP(11);
 #pragma unroll
           for (int i = 0; i < 4 * R; ++i) { gp(ag.buf[B_Y])[o + i] = y[i]; gp(ag.buf[B_X])[o + i] = y[i]; }

@@ -33,8 +33,8 @@
 //     waves 0-3  streamers: the carried gradient of c's last chunks -> LDS (C); then the whole P part on their own (N: their
 //                own hand-off; they start their product behind F, the chain's -- the two share the LDS)
 //     waves 4-5  the chain: one public pose per lane (G_j from LDS, projection; rows -> LDS: D) -> their quarters of the
-//                product over the last chunks (F) -> wave 4: reduction, step of the two poses on 16 lanes each (as
-//                k_step_fe); wave 5: W
+//                product over the last chunks (F) -> wave 4: reduction, step of the two poses on 16 lanes each
+//                (step_two_poses); wave 5: W
 //     wave 6     neighbour poses of the shared edges -> LDS (E); its quarter of the product behind D (F); the books
 //     wave 7     coefficients of the shared edges -> LDS (E); its quarter of the product (F); look-ahead of the other
 //                agents' poses + Y
@@ -45,14 +45,19 @@
 // 2.2 from the last workgroup's end to the next launch's first instruction.  The stream (128 KB per CU) lands under all
 // of it: the streamers are done 3 us before the tail.
 // Same arithmetic on the same operands in the same order as k_step_fe / the two-launch sequence: the iterates are BITWISE
-// theirs (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).
+// theirs (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).  The Nesterov scalars (nest_ahead), the books
+// (step_books), the look-ahead map (lookahead_map) and the step of the two poses (step_two_poses) are the text of
+// nesterov_step.h, which k_step_fe calls too: for the scalars, the map and the tail "bitwise the two-launch sequence" holds
+// BY CONSTRUCTION; for the gradient and the product it holds by test only.  (Wave 7's look-ahead of the other agents' poses
+// keeps its own control flow around the shared map: as a function shared with k_step_fe's second wave it cost this kernel
+// 2-4 % more instructions and 0.14 us per launch, profiles/r19_nesterov_step.md.)
 #include "kernel_common.h"
 #include <algorithm>
 
 namespace dpgo {
 
 // ---- device helpers of k_step_fd: hand-offs between the waves of a workgroup through counters in LDS, the chunk-ordered
-// layout, the staging of the shared edges' operands, the product over the last chunks, the Nesterov scalars
+// layout, the staging of the shared edges' operands, the product over the last chunks
 constexpr int FD_KC = 2048;
 // build switches of the experiments recorded in profiles/r06_deep_carry.md (every one measured SLOWER than the defaults but
 // the last): DPGO_FD_HEAD -- 16-byte loads per lane of the next agent's slab requested in front of the request hand-off;
@@ -193,32 +198,6 @@ __device__ __forceinline__ void fd_cf_to_lds(const AgentDev &ag, int ln, const F
     const int t = 64 * j + ln;
     if (64 * j < nit && t < nit) *reinterpret_cast<double2 *>(Es + (size_t)(t >> 3) * EPE + 4 * R + 2 * (t & 7)) = cr.v[j];
   }
-}
-
-// Nesterov scalars of the iterations this launch looks at, from the state BEFORE iteration k (the recurrences of
-// k_step_fe, one step further): every wave that needs them derives them from the same NestState
-struct FdNest {
-  bool restart_now, restart_next, restart_next2, restart_next3;
-  double nest_gamma, ahead_alpha, ahead2_alpha, ahead3_alpha;
-};
-
-__device__ __forceinline__ FdNest fd_nest(const NestState &ns, int num_robots, int restart_interval) {
-  FdNest o;
-  const double Nr = (double)num_robots;
-  o.restart_now = ((ns.iter + 2) % restart_interval) == 0;
-  o.restart_next = ((ns.iter + 3) % restart_interval) == 0;
-  o.restart_next2 = ((ns.iter + 4) % restart_interval) == 0;
-  o.restart_next3 = ((ns.iter + 5) % restart_interval) == 0;
-  o.nest_gamma = o.restart_now ? 0.0 : (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * ns.gamma * ns.gamma)) / (2.0 * Nr);
-  const double g2 = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * o.nest_gamma * o.nest_gamma)) / (2.0 * Nr);
-  o.ahead_alpha = 1.0 / (g2 * Nr);
-  const double gamma_next = o.restart_next ? 0.0 : g2;
-  const double g3 = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * gamma_next * gamma_next)) / (2.0 * Nr);
-  o.ahead2_alpha = 1.0 / (g3 * Nr);
-  const double gamma_next2 = o.restart_next2 ? 0.0 : g3;
-  const double g4 = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * gamma_next2 * gamma_next2)) / (2.0 * Nr);
-  o.ahead3_alpha = 1.0 / (g4 * Nr);
-  return o;
 }
 
 // the last NC chunks of one column per lane of waves 4-7 (lane l of the four: column group (l >> 5) & 7, k-lane l & 31 -- the
@@ -574,91 +553,13 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     }
     FD_STAMP(6);
     WSYNC();
-    const FdNest nn = fd_nest(ns, num_robots, restart_interval);
-    const bool restart_now = nn.restart_now, restart_next = nn.restart_next;
-    const double nest_gamma = nn.nest_gamma, ahead_alpha = nn.ahead_alpha;
+    const NestAhead nn = nest_ahead(ns, num_robots, restart_interval);
     const bool ahead_opt = next_sel == sel;
     const bool stats = in && (flags & FD_STATS) != 0, lastat = in && (flags & FD_LASTAT) != 0;
     if (ln < 2) tl_rel[ln] = 0.0;
-    // ---- the step of the workgroup's two poses: one pose on 16 lanes, the pose in LDS (k_step_fe's tail, device_math.h
-    // lane-parallel forms: bitwise the serial routines)
-    {
-      const int lp = ln >> 4, s = ln & 15;
-      if (lp < npose) {
-        const size_t o = (size_t)(lp ? pj1 : pj0) * 4 * R;
-        double *xs = tl_x + lp * 4 * R, *vsv = tl_v + lp * 4 * R, *ys = tl_y + lp * 4 * R, *Ss = tl_s + lp * 16;
-        double *zz = zs + lp * 4 * R;
-        const double *x0 = Ysh + lp * 4 * R, *v0 = Esh[0] + lp * 4 * R, *y0 = Esh[1] + lp * 4 * R;
-        const int i0 = s, i1 = s + 16;
-        const bool h0 = i0 < 4 * R, h1 = i1 < 4 * R;
-        tangent_lanes<R>(x0, zz, Ss, s);
-        if (h0) xs[i0] = x0[i0] - step * zz[i0];
-        if (h1) xs[i1] = x0[i1] - step * zz[i1];
-        lanes_sync();
-        qf_lanes<R>(xs, Ss, s);
-        FD_STAMP(7);
-        if (stats) {
-          // what k_precond's bit 3 leaves: the snapshot the closing statistics evaluate, |X - XPrev|^2 of the pose (one lane,
-          // the serial loop's order)
-          if (h0) gp(ag.buf[B_X2])[o + i0] = xs[i0];
-          if (h1) gp(ag.buf[B_X2])[o + i1] = xs[i1];
-          if (s == 0) {
-            const double *p0 = Psh + lp * 4 * R;
-            double rel = 0;
-#pragma unroll
-            for (int i = 0; i < 4 * R; ++i) { const double d = xs[i] - p0[i]; rel += d * d; }
-            tl_rel[lp] = rel;
-          }
-        }
-        if (lastat) {
-          if (h0) gp(ag.buf[B_XPREV])[o + i0] = xs[i0];
-          if (h1) gp(ag.buf[B_XPREV])[o + i1] = xs[i1];
-        }
-        const bool reset = restart_now;
-        if (reset) {
-          if (h0) vsv[i0] = xs[i0];
-          if (h1) vsv[i1] = xs[i1];
-          lanes_sync();
-        } else {
-          const double gamma = nest_gamma;
-          if (h0) vsv[i0] = v0[i0] + gamma * (xs[i0] - y0[i0]);
-          if (h1) vsv[i1] = v0[i1] + gamma * (xs[i1] - y0[i1]);
-          lanes_sync();
-          polar_lanes<R>(vsv, Ss, s);
-        }
-        FD_STAMP(8);
-        if (restart_next) {
-          if (h0 && in) {
-            Xw[o + i0] = xs[i0];
-            if (!ahead_opt) { Yw[o + i0] = xs[i0]; vsv[i0] = xs[i0]; }
-            else Yw[o + i0] = reset ? xs[i0] : y0[i0];
-          }
-          if (h1 && in) {
-            Xw[o + i1] = xs[i1];
-            if (!ahead_opt) { Yw[o + i1] = xs[i1]; vsv[i1] = xs[i1]; }
-            else Yw[o + i1] = reset ? xs[i1] : y0[i1];
-          }
-          if (lastat && !ahead_opt && s == 0) gp(ag.part)[PART_D + (lp ? pj1 : pj0)] = 0.0;
-        } else {
-          if (h0) ys[i0] = (1.0 - ahead_alpha) * xs[i0] + ahead_alpha * vsv[i0];
-          if (h1) ys[i1] = (1.0 - ahead_alpha) * xs[i1] + ahead_alpha * vsv[i1];
-          lanes_sync();
-          polar_lanes<R>(ys, Ss, s);
-          FD_STAMP(9);
-          if (h0 && in) { Yw[o + i0] = ys[i0]; Xw[o + i0] = ys[i0]; }
-          if (h1 && in) { Yw[o + i1] = ys[i1]; Xw[o + i1] = ys[i1]; }
-          if (lastat && !ahead_opt && s == 0) {  // look-ahead steps leave |Y' - X|^2 per pose
-            double rel2 = 0;
-#pragma unroll
-            for (int i = 0; i < 4 * R; ++i) { const double d = ys[i] - xs[i]; rel2 += d * d; }
-            gp(ag.part)[PART_D + (lp ? pj1 : pj0)] = rel2;
-          }
-        }
-        lanes_sync();
-        if (h0 && in) ag.buf[B_V][o + i0] = vsv[i0];
-        if (h1 && in) ag.buf[B_V][o + i1] = vsv[i1];
-      }
-    }
+    // ---- the step of the workgroup's two poses, one pose on 16 lanes
+    const TwoPoseLds tl2 = {zs, Ysh, Esh[0], Esh[1], Psh, tl_x, tl_v, tl_y, tl_s, tl_rel};
+    step_two_poses<R>(ag, Xw, Yw, tl2, ln, npose, pj0, pj1, step, nn, ahead_opt, in, stats, lastat, [&](int k) { FD_STAMP(k); });
     if (stats) {
       // (k_precond: the two poses' sums through wave_sum, lane 0 stores)
       WSYNC();
@@ -690,28 +591,8 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     fd_wait(&sy[FD_SY_D], 2);  // this wave's quarter of the product over the last chunks
     fd_cur_product<R, M0, NC>(cu, vs, red, tid - 256);
     fd_signal(&sy[FD_SY_F]);
-    if (bx == 0 && ln < LOOKAHEAD_MAX_AGENTS && in) {
-      // the books (advance_agent, accelerated) into the OTHER state buffer: every workgroup of this launch reads nest_src
-      const int k = ln;
-      const double Nr = (double)num_robots;
-      if (k < num_agents) {
-        NestState s2 = nest_src[k];
-        const bool restart = ((s2.iter + 2) % restart_interval) == 0;
-        if (restart) { s2.gamma = 0; s2.alpha = 0; }
-        else {
-          s2.gamma = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * s2.gamma * s2.gamma)) / (2.0 * Nr);
-          s2.alpha = 1.0 / (s2.gamma * Nr);
-        }
-        s2.iter += 1;
-        nest_dst[k] = s2;
-      }
-      if (k == 0) {
-        team->iter += 1;
-        team->stats_sel = sel;
-        team->next_sel = next_sel;
-        team->cur_sel = next_sel;
-      }
-    }
+    if (bx == 0 && ln < LOOKAHEAD_MAX_AGENTS && in)  // the books, one lane per agent
+      step_books(team, nest_src, nest_dst, ln, num_agents, sel, next_sel, num_robots, restart_interval);
     FD_STAMP(14);
     FD_FLUSH();
     return;
@@ -781,7 +662,7 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     fd_cur_product<R, M0, NC>(cu, vs, red, tid - 256);
     fd_signal(&sy[FD_SY_F]);
     __builtin_amdgcn_s_setprio(0);
-    const FdNest nn = fd_nest(ns, num_robots, restart_interval);
+    const NestAhead nn = nest_ahead(ns, num_robots, restart_interval);
     if (lact) {
       const bool st = in, lastat = in && (flags & FD_LASTAT) != 0;
       double *pa_ = fb.part[0];
@@ -803,9 +684,7 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
         if (lastat && !la_opt) gp(pa_)[PART_D + la_pose] = 0.0;
       } else {
         double y[4 * R];
-#pragma unroll
-        for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - nn.ahead_alpha) * la_x[i] + nn.ahead_alpha * la_v[i];
-        polar_inplace<R>(y);
+        lookahead_map<R>(la_x, la_v, nn.ahead_alpha, y);
         if (lastat && !la_opt) {
           double r2 = 0;
 #pragma unroll
@@ -825,17 +704,13 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
           for (int i = 0; i < 4 * R; ++i) la_v[i] = la_x[i];  // (k+2 restarts: X stays, V = Y = X)
         } else {
           double y[4 * R];
-#pragma unroll
-          for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - nn.ahead2_alpha) * la_x[i] + nn.ahead2_alpha * la_v[i];
-          polar_inplace<R>(y);
+          lookahead_map<R>(la_x, la_v, nn.ahead2_alpha, y);
 #pragma unroll
           for (int i = 0; i < 4 * R; ++i) la_x[i] = y[i];
         }
         if (!nn.restart_next3) {
           double y[4 * R];
-#pragma unroll
-          for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - nn.ahead3_alpha) * la_x[i] + nn.ahead3_alpha * la_v[i];
-          polar_inplace<R>(y);
+          lookahead_map<R>(la_x, la_v, nn.ahead3_alpha, y);
 #pragma unroll
           for (int i = 0; i < 4 * R; ++i) la_x[i] = y[i];
         }
@@ -864,16 +739,14 @@ __global__ __launch_bounds__(64) void k_fd_prime(const AgentDev *__restrict__ ag
   double x[4 * R], v[4 * R];
 #pragma unroll
   for (int i = 0; i < 4 * R; ++i) { x[i] = gp(ag.buf[B_X])[o + i]; v[i] = gp(ag.buf[B_V])[o + i]; }
-  const FdNest nn = fd_nest(nest_src[s0], num_robots, restart_interval);
+  const NestAhead nn = nest_ahead(nest_src[s0], num_robots, restart_interval);
   if (role == 2) {
     if (nn.restart_next) {
 #pragma unroll
       for (int i = 0; i < 4 * R; ++i) v[i] = x[i];
     } else {
       double y[4 * R];
-#pragma unroll
-      for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - nn.ahead_alpha) * x[i] + nn.ahead_alpha * v[i];
-      polar_inplace<R>(y);
+      lookahead_map<R>(x, v, nn.ahead_alpha, y);
 #pragma unroll
       for (int i = 0; i < 4 * R; ++i) x[i] = y[i];
     }
@@ -883,9 +756,7 @@ __global__ __launch_bounds__(64) void k_fd_prime(const AgentDev *__restrict__ ag
     const double al = role == 1 ? nn.ahead_alpha : nn.ahead2_alpha;
     if (!rs) {
       double y[4 * R];
-#pragma unroll
-      for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - al) * x[i] + al * v[i];
-      polar_inplace<R>(y);
+      lookahead_map<R>(x, v, al, y);
 #pragma unroll
       for (int i = 0; i < 4 * R; ++i) x[i] = y[i];
     }

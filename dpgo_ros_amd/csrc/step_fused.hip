@@ -37,6 +37,14 @@
 //   (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).  19.8 -> 14.1 us per launch on sphere2500 / 5
 //   (profiles/r05_carried_rows.md has the phase traces and what each step bought).
 //
+// The text the three forms of the iteration must agree on lives once, in nesterov_step.h: the Nesterov recurrence and the
+// scalars of the iterations ahead (nest_ahead), the books (step_books), the look-ahead map (lookahead_map) and the step of the
+// workgroup's two poses on 16 lanes each (step_two_poses); k_step_fd (step_deep.hip) calls the same text.  "Bitwise the
+// two-launch sequence" holds BY CONSTRUCTION for the scalars, the map and the tail (k_precond takes nest_ahead and
+// lookahead_map too; its serial tail stores in place and keeps its own control flow); for the gradient and the product it
+// holds by test only.  (The look-ahead wave keeps its own control flow around the shared map, as k_step_fd's does: shared
+// as one function it slowed k_step_fd down, profiles/r19_nesterov_step.md.)
+//
 // What was learned building it (profiles/r03_fused_step.md, profiles/r05_carried_rows.md):
 //   * a CU serves its vector-memory requests in order.  A slab requested first holds every later load of the same CU
 //     back until it has landed (X staged at 6.5 us instead of 2): the evaluation cannot hide under the stream, its loads
@@ -482,27 +490,8 @@ __global__ __launch_bounds__(512) void k_step_fe(const AgentDev *__restrict__ ag
     // product's partial sums back -- workgroup 0, which keeps the books, used to finish 1.6 us behind all the others)
     lds_barrier();  // #4: (the stream waves' partial sums)
     if (bx == 0 && tid < 256 + LOOKAHEAD_MAX_AGENTS) {
-      // what the bookkeeping workgroup of the next k_eval_stats would do (advance_agent, accelerated): into the OTHER
-      // state buffer -- every workgroup of this launch reads nest_src.  One lane per agent (one round trip for all of them)
-      const int na = team->num_agents, k = tid - 256;
-      const double Nr = (double)num_robots;
-      if (k < na) {
-        NestState s2 = nest_src[k];
-        const bool restart = ((s2.iter + 2) % restart_interval) == 0;
-        if (restart) { s2.gamma = 0; s2.alpha = 0; }
-        else {
-          s2.gamma = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * s2.gamma * s2.gamma)) / (2.0 * Nr);
-          s2.alpha = 1.0 / (s2.gamma * Nr);
-        }
-        s2.iter += 1;
-        nest_dst[k] = s2;
-      }
-      if (k == 0) {
-        team->iter += 1;
-        team->stats_sel = sel;
-        team->next_sel = next_sel;
-        team->cur_sel = next_sel;
-      }
+      // what the bookkeeping workgroup of the next k_eval_stats would do.  One lane per agent (one round trip for all of them)
+      step_books(team, nest_src, nest_dst, tid - 256, team->num_agents, sel, next_sel, num_robots, restart_interval);
     }
     if (flags & FE_CARRY_W) {
       // ---- the row products of the NEXT agent (carried rows): W_p = sum_i X_i Q_ip at the point the next launch will
@@ -566,17 +555,8 @@ __global__ __launch_bounds__(512) void k_step_fe(const AgentDev *__restrict__ ag
     return;
   }
 
-  const double Nr = (double)num_robots;
-  const bool restart_now = ((ns.iter + 2) % restart_interval) == 0;
-  const bool restart_next = ((ns.iter + 3) % restart_interval) == 0;
-  const double nest_gamma = restart_now ? 0.0 : (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * ns.gamma * ns.gamma)) / (2.0 * Nr);
-  const double g2 = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * nest_gamma * nest_gamma)) / (2.0 * Nr);
-  const double ahead_alpha = 1.0 / (g2 * Nr);
-  // (two iterations ahead, carried rows: the scalars the NEXT launch will look ahead with)
-  const bool restart_next2 = ((ns.iter + 4) % restart_interval) == 0;
-  const double gamma_next = restart_next ? 0.0 : g2;
-  const double g3 = (1.0 + sqrt(1.0 + 4.0 * Nr * Nr * gamma_next * gamma_next)) / (2.0 * Nr);
-  const double ahead2_alpha = 1.0 / (g3 * Nr);
+  // (this iteration's scalars and, two iterations ahead, carried rows: those the NEXT launch will look ahead with)
+  const NestAhead nn = nest_ahead(ns, num_robots, restart_interval);
   const bool ahead_opt = next_sel == sel;
   double acc[R];
 #pragma unroll
@@ -653,7 +633,7 @@ __global__ __launch_bounds__(512) void k_step_fe(const AgentDev *__restrict__ ag
       double la_x[4 * R], la_v[4 * R];
 #pragma unroll
       for (int i = 0; i < 4 * R; ++i) { la_x[i] = xr[o + i]; la_v[i] = va[o + i]; }
-      if (restart_next) {
+      if (nn.restart_next) {
         // (X stays; Y = V = X unless the agent optimizes next -- then Y stays too: both are carried into the other copy)
 #pragma unroll
         for (int i = 0; i < 4 * R; ++i) {
@@ -662,9 +642,7 @@ __global__ __launch_bounds__(512) void k_step_fe(const AgentDev *__restrict__ ag
         }
       } else {
         double y[4 * R];
-#pragma unroll
-        for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - ahead_alpha) * la_x[i] + ahead_alpha * la_v[i];
-        polar_inplace<R>(y);
+        lookahead_map<R>(la_x, la_v, nn.ahead_alpha, y);
 #pragma unroll
         for (int i = 0; i < 4 * R; ++i) { oY[o + i] = y[i]; oX[o + i] = y[i]; la_x[i] = y[i]; }
       }
@@ -674,11 +652,9 @@ __global__ __launch_bounds__(512) void k_step_fe(const AgentDev *__restrict__ ag
         // launch early, so that the next launch finds it complete and can form the row products on the side.  (The agent
         // moves in neither launch: it is neither this launch's nor the next one's.  la_x / la_v hold its X and V after
         // iteration k+1 here.)
-        if (!restart_next2) {
+        if (!nn.restart_next2) {
           double y[4 * R];
-#pragma unroll
-          for (int i = 0; i < 4 * R; ++i) y[i] = (1.0 - ahead2_alpha) * la_x[i] + ahead2_alpha * la_v[i];
-          polar_inplace<R>(y);
+          lookahead_map<R>(la_x, la_v, nn.ahead2_alpha, y);
 #pragma unroll
           for (int i = 0; i < 4 * R; ++i) la_x[i] = y[i];
         }
@@ -691,64 +667,12 @@ __global__ __launch_bounds__(512) void k_step_fe(const AgentDev *__restrict__ ag
     return;
   }
 
-  // ---- the step of the workgroup's two poses (k_precond<PM_RGD>, advance = 2, ahead bit 0, no statistics): one pose on 16
-  // lanes, the pose in LDS (device_math.h, lane-parallel forms: bitwise the serial routines) -- the six Gram sums of a QF /
-  // polar factor side by side, the entries of a product on 3R lanes.  Serial, this tail was 2.2 us of dependent fp64
-  // arithmetic on two lanes of the wave.  (The look-ahead wave next to it keeps one lane per pose: its single polar factor
-  // is off the critical path -- spreading it over lanes as well was measured and changes nothing.)
-  {
-    const int lp = tid >> 4, s = tid & 15;
-    if (lp < npose) {
-      const size_t o = (size_t)(lp ? pj1 : pj0) * 4 * R;
-      double *xs = tl_x + lp * 4 * R, *vsv = tl_v + lp * 4 * R, *ys = tl_y + lp * 4 * R, *Ss = tl_s + lp * 16;
-      double *zz = zs + lp * 4 * R;
-      const double *x0 = Ysh + lp * 4 * R, *v0 = Esh[0] + lp * 4 * R, *y0 = Esh[1] + lp * 4 * R;
-      const int i0 = s, i1 = s + 16;  // the (at most two) entries of the pose this lane moves
-      const bool h0 = i0 < 4 * R, h1 = i1 < 4 * R;
-      tangent_lanes<R>(x0, zz, Ss, s);
-      if (h0) xs[i0] = x0[i0] - step * zz[i0];
-      if (h1) xs[i1] = x0[i1] - step * zz[i1];
-      lanes_sync();
-      qf_lanes<R>(xs, Ss, s);
-      FE_STAMP(7);
-      const bool reset = restart_now;  // restart iteration: V = Y = X
-      if (reset) {
-        if (h0) vsv[i0] = xs[i0];
-        if (h1) vsv[i1] = xs[i1];
-        lanes_sync();
-      } else {
-        const double gamma = nest_gamma;
-        if (h0) vsv[i0] = v0[i0] + gamma * (xs[i0] - y0[i0]);
-        if (h1) vsv[i1] = v0[i1] + gamma * (xs[i1] - y0[i1]);
-        lanes_sync();
-        polar_lanes<R>(vsv, Ss, s);
-      }
-      FE_STAMP(8);
-      if (restart_next) {
-        if (h0) {
-          Xw[o + i0] = xs[i0];
-          if (!ahead_opt) { Yw[o + i0] = xs[i0]; vsv[i0] = xs[i0]; }
-          else Yw[o + i0] = reset ? xs[i0] : y0[i0];  // (else Y stays: carried into the other copy)
-        }
-        if (h1) {
-          Xw[o + i1] = xs[i1];
-          if (!ahead_opt) { Yw[o + i1] = xs[i1]; vsv[i1] = xs[i1]; }
-          else Yw[o + i1] = reset ? xs[i1] : y0[i1];
-        }
-      } else {
-        if (h0) ys[i0] = (1.0 - ahead_alpha) * xs[i0] + ahead_alpha * vsv[i0];
-        if (h1) ys[i1] = (1.0 - ahead_alpha) * xs[i1] + ahead_alpha * vsv[i1];
-        lanes_sync();
-        polar_lanes<R>(ys, Ss, s);
-        FE_STAMP(9);
-        if (h0) { Yw[o + i0] = ys[i0]; Xw[o + i0] = ys[i0]; }
-        if (h1) { Yw[o + i1] = ys[i1]; Xw[o + i1] = ys[i1]; }
-      }
-      lanes_sync();
-      if (h0) ag.buf[B_V][o + i0] = vsv[i0];
-      if (h1) ag.buf[B_V][o + i1] = vsv[i1];
-    }
-  }
+  // ---- the step of the workgroup's two poses (k_precond<PM_RGD>, advance = 2, ahead bit 0, no statistics) on 16 lanes each.
+  // Serial, this tail was 2.2 us of dependent fp64 arithmetic on two lanes of the wave.  (The look-ahead wave next to it
+  // keeps one lane per pose: its single polar factor is off the critical path -- spreading it over lanes as well was measured
+  // and changes nothing.)
+  const TwoPoseLds tl = {zs, Ysh, Esh[0], Esh[1], nullptr, tl_x, tl_v, tl_y, tl_s, nullptr};
+  step_two_poses<R>(ag, Xw, Yw, tl, tid, npose, pj0, pj1, step, nn, ahead_opt, true, false, false, [&](int k) { FE_STAMP(k); });
   FE_STAMP(15);
   FE_FLUSH();
 }
