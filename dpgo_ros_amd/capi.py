@@ -131,7 +131,7 @@ dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_c
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
-dpgo_team_gate_candidates_jointly dpgo_team_linear_update""".split()
+dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1244,6 +1244,70 @@ class Team:
         if innovation_covariance:
             out["M"] = M
         return out
+
+    def candidates_from_pairs(self, pairs, kappa, tau):
+        """MEAS_DTYPE records for the team-order pose pairs[k] = (i, j), i != j, with no measurement: R = I, t = 0, the expected
+        noise kappa and tau (scalars or one per pair) and weight 1 -- what select_closures takes for a pool of proposals.  Robots
+        and poses are resolved as relative_covariances resolves them."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        offs = np.cumsum([0] + [self.agents[i].n for i in self.ids])
+        N = int(offs[-1])
+        if len(pr) and (pr.min() < 0 or pr.max() >= N):
+            raise ValueError("candidates_from_pairs: a pair names a pose outside [0, %d)" % N)
+        cand = np.zeros(len(pr), dtype=MEAS_DTYPE)
+        ids = np.asarray(self.ids, dtype=np.int64)
+        for e, (r, p) in enumerate((("r1", "p1"), ("r2", "p2"))):
+            k = np.searchsorted(offs, pr[:, e], side="right") - 1
+            cand[r], cand[p] = ids[k], pr[:, e] - offs[k]
+        cand["R"] = np.eye(3).reshape(-1)
+        cand["kappa"], cand["tau"], cand["weight"] = kappa, tau, 1.0
+        return cand
+
+    def select_closures(self, candidates, budget, T=None, method=None, max_block=None, order="greedy", min_gain=None):
+        """The most informative of a pool of candidate closures under a budget, chosen before any of them is measured (DESIGN.md
+        5k).  candidates: MEAS_DTYPE records of which only the endpoints, kappa and tau are read (candidates_from_pairs builds
+        them); T, method and max_block as in gate_jointly, whose M = A Sigma A^T + R this call eliminates without forming it.
+        Given the selected set A, gain_k|A = (log det S_k|A - log det Sigma_meas,k) / 2 with S_k|A = M_kk - M_kA M_AA^-1 M_Ak is
+        the mutual information between measurement k and the trajectory once A has been measured.  order="greedy": at every
+        step the open candidate of largest gain_k|A (the lower index on ties); order="given": k = 0 .. budget - 1 in turn, the
+        price of a caller's own plan.  A candidate is taken while its gain exceeds min_gain (None: no threshold) and fewer
+        than `budget` are selected; otherwise the call stops.  Returns a dict:
+            candidates     the records,
+            gain[P]        the marginal gain_k|{},
+            gain_cond[P]   the gain at the moment k was selected; for the rest, given the final set: what is still on the table,
+            rank[P]        the position in the order of selection, -1 when not selected,
+            selected       the indices of the selected candidates in selection order,
+            num_selected, gain_total (the sum of gain_cond over `selected` in order = (log det M_AA - log det R_A) / 2, the
+                           information_gain of linear_update for the same set), logdet_joint (log det M_AA),
+            covariance     the Covariance record of the path.
+        Greedy's gain_total is at least (1 - 1 / e) of the best set of the same size.  The covariance blocks and the factor
+        (budget x P blocks) stay on the device.  Raises DpgoError as gate does (R and t are not checked), and for a budget outside
+        [1, P] or blocks and factor that do not fit the device.  One team only.  Changes no solver state."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("select_closures: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        if order not in ("greedy", "given"):
+            raise ValueError("select_closures: order must be \"greedy\" or \"given\", not %r" % (order,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("select_closures: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        cand = np.ascontiguousarray(candidates, dtype=MEAS_DTYPE).reshape(-1)
+        P = len(cand)
+        res = Covariance()
+        gain, gc, rank = np.zeros(P), np.zeros(P), np.full(P, -1, dtype=np.int32)
+        nsel, gt, lj = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        p = lambda a: _d(a) if P else None
+        _chk(lib().dpgo_team_select_candidates(self.h, _d(T), code, int(max_block or 0), P, p(cand),
+                                               JOINT_GREEDY if order == "greedy" else JOINT_GIVEN, int(budget),
+                                               C.c_double(-np.inf if min_gain is None else min_gain), p(gain), p(gc), p(rank),
+                                               C.byref(nsel), C.byref(gt), C.byref(lj), C.byref(res)), "select_candidates")
+        n = int(nsel.value)
+        selected = np.argsort(np.where(rank >= 0, rank, P), kind="stable")[:n]
+        return dict(candidates=cand, gain=gain, gain_cond=gc, rank=rank, selected=selected, num_selected=n,
+                    gain_total=float(gt.value), logdet_joint=float(lj.value), covariance=res)
 
     def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None):
         """The estimate and its covariances updated to first order for a set of new closures, without a re-solve (DESIGN.md

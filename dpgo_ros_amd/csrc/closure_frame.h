@@ -1,7 +1,7 @@
 // closure_frame.h -- the host-side frame of a call that takes a list of measurements and works behind a covariance path's
-// staged blocks (DESIGN.md 5f-5j): gate_candidates (gate.hip), pairwise_consistency (consistency.hip), audit_measurements
-// (audit.hip), gate_candidates_jointly (gate_joint.hip) and linear_update (linear_update.hip).  One layer above
-// covariance_frame.h: how a call words its refusals, resolves and checks a record, packs it for the device, lists the pairs it
+// staged blocks (DESIGN.md 5f-5k): gate_candidates (gate.hip), pairwise_consistency (consistency.hip), audit_measurements
+// (audit.hip), gate_candidates_jointly (gate_joint.hip), linear_update (linear_update.hip) and select_candidates
+// (select.hip).  One layer above covariance_frame.h: how a call words its refusals, resolves and checks a record, packs it for the device, lists the pairs it
 // asks the path for, dispatches to the path, and times its own kernels.  A call keeps its own argument checks, the shape of
 // its pair list, its budget and its copy-out; the ORDER of its refusals is the call's own too, and the tests see it.
 #pragma once

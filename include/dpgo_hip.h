@@ -550,6 +550,41 @@ int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method /* DPGO_
                             const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
                             double *delta /* 6 N */, double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_post,
                             double *scalars /* d2_joint, logdet_M, logdet_R */, dpgo_covariance_t *res);
+/* ---- the most informative candidate closures under a budget (csrc/select.hip) ----
+ * Asked before anything is measured: of num = P proposed pose pairs of one team, which `budget` would tighten the estimate
+ * most.  T, Sigma, the perturbation, J_i, J_j and Sigma_meas are those of dpgo_team_gate_candidates, A, R and
+ * M = A Sigma A^T + R those of dpgo_team_gate_candidates_jointly.  The Jacobians depend on T alone, so of a record only the two
+ * endpoints and the expected noise (kappa, tau) are read: R~, t~ and weight are not.
+ *   conditional    given a selected set A: S_k|A = M_kk - M_kA M_AA^-1 M_Ak and
+ *                  gain_k|A = (log det S_k|A - log det Sigma_meas,k) / 2, log det Sigma_meas,k = -3 log(2 kappa_k) - 3 log tau_k:
+ *                  the mutual information between measurement k and the trajectory once A has been measured, which is
+ *                  (log det H' - log det H) / 2 for adding k to the graph that already holds A.  A non-positive pivot gives
+ *                  -inf, which is never taken
+ *   order          DPGO_JOINT_GREEDY: at every step the open candidate of largest gain_k|A, the lower index on ties;
+ *                  DPGO_JOINT_GIVEN: k = 0 .. budget - 1 in turn.  Either way the candidate is taken while gain > min_gain
+ *                  (-INFINITY: no threshold) and fewer than `budget` are selected; otherwise the call stops.  The set function
+ *                  is monotone submodular, so the greedy value is at least (1 - 1 / e) of the best set of the same size
+ *   outputs        gain (P): the marginal gain_k|{}.  gain_cond (P): the gain at the moment k was selected; for the rest, given
+ *                  the final set: what is still on the table.  rank (P): the position in the order of selection, -1 when not
+ *                  selected.  *num_selected = |A|.  *gain_total: the sum of the gains at selection in selection order, which
+ *                  is (log det M_AA - log det R_A) / 2, the information_gain of dpgo_team_linear_update for the same set.
+ *                  *logdet_joint = log det M_AA.
+ * The covariance path `method` (max_block: DPGO_GATE_NESTED only) is asked for every unordered pair of the distinct endpoint
+ * poses, sorted; the blocks stay on the device.  One kernel forms the diagonal blocks and the marginal gains, then one launch
+ * per selected candidate -- `budget` launches, not P -- forms the pivot's block column of M on the fly, bit for bit what
+ * dpgo_team_gate_candidates_jointly stores there, and updates the conditional blocks and gains by a left-looking block-pivoted
+ * Cholesky whose factor has budget x P blocks of 288 bytes.  M is never formed.  Every sum runs in index order with fused
+ * multiply-adds and there are no atomics: two calls give the same bytes.
+ * Refused with DPGO_ERR and a message that begins "select_candidates:" before any device work, every output untouched: a NULL
+ * argument, num <= 0, budget outside [1, num], an unknown method or order, a NaN min_gain, an endpoint that is not a robot or pose
+ * of the team, i == j, kappa or tau not positive and finite; and pair blocks, factor and working arrays that do not fit the free
+ * device memory, or more than INT32_MAX pair blocks, with the bytes named.  Every refusal of the chosen covariance path
+ * carries over with its own message; the outputs are then untouched and *res all zero.  *res: the path's own record.  Changes no
+ * solver state.  There is no call across teams. */
+int dpgo_team_select_candidates(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */,
+                                int num, const dpgo_measurement_t *cand, int order /* DPGO_JOINT_* */, int budget, double min_gain,
+                                double *gain /* num */, double *gain_cond /* num */, int *rank /* num */, int *num_selected,
+                                double *gain_total, double *logdet_joint, dpgo_covariance_t *res);
 /* ---- the pairwise-consistent set of candidates between two teams (csrc/consistency.hip, csrc/max_clique.cpp) ----
  * Pairwise consistency maximisation (Mangelson et al. 2018) for loop closures between two teams that are NOT joined yet, each
  * with a connected weighted graph of its own (they may be the same handle), trajectories T_a and T_b in their own gauges.
