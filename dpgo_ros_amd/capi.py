@@ -131,7 +131,7 @@ dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_c
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
-dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates""".split()
+dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1349,6 +1349,69 @@ class Team:
                                            C.byref(res)), "linear_update")
         return dict(T=Tn, delta=dx, cov_diag=diag, cov_pairs=cross, xi=xi, xi_post=xp, d2_joint=float(sc[0]), logdet_M=float(sc[1]),
                     logdet_R=float(sc[2]), information_gain=0.5 * float(sc[1] - sc[2]), covariance=res)
+
+    def linear_removal(self, measurements, new_weight=None, T=None, method=None, max_block=None, pairs=None, min_redundancy=1e-6,
+                       quantile=0.99):
+        """Measurements that are in the graph removed or down-weighted in the estimate and its covariances, to first order and
+        without a re-solve: the counterpart of linear_update for weight taken out of the graph, and the joint
+        leave-K-out test audit does not give.  measurements: MEAS_DTYPE records as in audit, whose weight w > 0 says at which
+        weight each is in the graph (taken on trust; the flags are ignored).  new_weight[K]: the weights w' they drop to,
+        0 <= w' < w; None: all 0, the edges removed.  T must be a minimum of the graph that holds the records; T, method and
+        max_block as in gate, pairs as in linear_update.  With dw = w - w', R_k = Sigma_meas,k / dw_k, A of gate_jointly and
+        B = Sigma A^T: N = R - A B, dx = +B N^-1 xi, Sigma' = Sigma + B N^-1 B^T, T' = T [+] dx.  Returns a dict:
+            measurements, new_weight  the records and the weights they go to,
+            T, delta[N, 6], cov_diag[N, 6, 6], cov_pairs[len(pairs), 6, 6]  as in linear_update, of the graph without the weight,
+            xi[K, 6]         the innovations at T: gate's,
+            xi_loo[K, 6]     R N^-1 xi = xi + A dx: the innovations the records show against the graph without that weight; at
+                             K = 1 audit's xi_loo,
+            pivot_min[K]     the smallest Cholesky pivot of each record's own block of the whitened N: audit's pivot_min at
+                             weight dw,
+            d2_joint         xi^T N^-1 xi, twice the drop of the optimal cost.  At K = 1, w = 1, w' = 0 it is audit's d2; for
+                             K > 1 at full weight the joint normalised-residual statistic, chi^2 with 6 K degrees of freedom
+                             when the set is sound; with a fractional dw it is the cost the removed weight accounted for and
+                             NOT audit's d2,
+            logdet_N, logdet_R, information_loss = (logdet_R - logdet_N) / 2 = (log det H - log det H') / 2 >= 0,
+            pivot_min_joint  the smallest pivot of the factor of the whitened N, in (0, 1]; the errors of every output grow
+                             like its reciprocal,
+            joint_accept     sqrt(d2_joint) <= error_threshold_at_quantile(quantile, 6 K): the set passes, and its removal is
+                             not called for (gate_jointly's use of the threshold),
+            covariance       the Covariance record of the path (of Sigma, not Sigma').
+        What audit flags goes straight in:
+            aud = team.audit(); mm = aud["measurements"]
+            bad = mm[aud["testable"] & ~aud["accept"]]
+            out = team.linear_removal(bad)            # T', Sigma' and the joint verdict now;
+            # then agent.set_measurement_weight(..., 0.0) for each, team.set_initial(out["T"], ...) warm-starts the re-solve
+        Raises DpgoError as linear_update does; for a weight that is not finite and positive, a new_weight that is negative, not
+        finite or not below its weight, a min_redundancy outside (0, 1); and, behind the covariance path, for a record whose
+        pivot_min is not above min_redundancy (a bridge: the record is named), a non-positive pivot of N, or a pivot_min_joint
+        not above min_redundancy (the records together leave no redundancy: a cut).  One team only.  Changes no solver state,
+        the team's weights included."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("linear_removal: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("linear_removal: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        meas = np.ascontiguousarray(measurements, dtype=MEAS_DTYPE).reshape(-1)
+        K = len(meas)
+        nw = np.zeros(K) if new_weight is None else np.ascontiguousarray(np.broadcast_to(np.asarray(new_weight, dtype=np.float64), (K,)))
+        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        res = Covariance()
+        Tn, dx, diag, cross = np.zeros(12 * N), np.zeros((N, 6)), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
+        xi, xl, pm, sc = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(K), np.zeros(4)
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        p = lambda a: _d(a) if K else None
+        _chk(lib().dpgo_team_linear_removal(self.h, _d(T), code, int(max_block or 0), K, p(meas), p(nw), C.c_double(min_redundancy),
+                                            len(pr), _d(pr) if len(pr) else None, _d(Tn), _d(dx), _d(diag),
+                                            _d(cross) if len(pr) else None, _d(xi), _d(xl), _d(pm), _d(sc), C.byref(res)),
+             "linear_removal")
+        d2 = float(sc[0])
+        return dict(measurements=meas, new_weight=nw, T=Tn, delta=dx, cov_diag=diag, cov_pairs=cross, xi=xi, xi_loo=xl, pivot_min=pm,
+                    d2_joint=d2, logdet_N=float(sc[1]), logdet_R=float(sc[2]), pivot_min_joint=float(sc[3]),
+                    information_loss=0.5 * float(sc[2] - sc[1]),
+                    joint_accept=bool(np.sqrt(d2) <= error_threshold_at_quantile(quantile, 6 * K)), covariance=res)
 
 
 def _adjacency_words(adjacency):

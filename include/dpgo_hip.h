@@ -550,6 +550,43 @@ int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method /* DPGO_
                             const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
                             double *delta /* 6 N */, double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_post,
                             double *scalars /* d2_joint, logdet_M, logdet_R */, dpgo_covariance_t *res);
+/* ---- measurements removed or down-weighted in the estimate and its covariances, no re-solve (csrc/linear_removal.hip;
+ * DESIGN.md 5l) ----
+ * The counterpart of dpgo_team_linear_update for weight taken OUT of the graph.  num = K records of one team are in the
+ * weighted graph, record k at records[k].weight = w_k > 0 (taken on trust, as in dpgo_team_audit_measurements), and T is a
+ * minimum of that graph.  Their weights drop to new_weight[k] = w'_k with 0 <= w'_k < w_k (NULL: all 0, the edges removed).
+ * With dw_k = w_k - w'_k, R_k = Sigma_meas,k / dw_k, A of dpgo_team_gate_candidates_jointly and B = Sigma A^T:
+ *   H' = H - A^T R^-1 A,  N = R - A B (of order 6 K: the covariance of the post-fit residuals of the set),
+ *   Sigma' = Sigma + B N^-1 B^T,  dx = +B N^-1 xi,  T' = T [+] dx (the retraction of dpgo_team_linear_update),
+ *   xi_loo = xi + A dx = R N^-1 xi: the innovations the K records show against the graph without that weight,
+ *   d2_joint = xi^T N^-1 xi: twice the drop of the optimal cost, f'(T') = f(T) - d2_joint / 2,
+ *   log det H' - log det H = logdet_N - logdet_R, so the information lost is (logdet_R - logdet_N) / 2 >= 0.
+ * At K = 1 xi_loo is the audit's; at K = 1, w = 1, w' = 0 d2_joint is the audit's d2, the classical normalised residual; for
+ * K > 1 at full weight d2_joint is the joint normalised-residual statistic, chi^2 with 6 K degrees of freedom when the set is
+ * sound.  With a fractional dw d2_joint is still the cost the removed weight accounted for, but it is NOT the audit's d2.
+ * The work is whitened: s_k = (sqrt(2 kappa_k dw_k) x 3, sqrt(tau_k dw_k) x 3), D = diag(s), B~ = B D, xi~ = D xi and
+ * N~ = D N D = I - (D A) B~, stored bitwise symmetric, whose pivots lie in (0, 1] and whose diagonal block is the audit's
+ * I - dw C (several records may join one ordered pair of poses with noise that is not proportional: no block off the
+ * diagonal is symmetrised); logdet_N = log det N~ + logdet_R, logdet_R = sum_k -3 log(2 kappa_k) - 3 log tau_k - 6 log dw_k.
+ *   outputs        T_new, delta (6 N), cov_diag (36 N, bitwise symmetric), cov_pairs (36 per pair of `pairs`): as in
+ *                  dpgo_team_linear_update; xi, xi_loo (6 K); pivot_min (K): the smallest Cholesky pivot of record k's own
+ *                  block of N~, the audit's pivot_min at weight dw_k; scalars: d2_joint, logdet_N, logdet_R and
+ *                  pivot_min_joint, the smallest pivot of the Cholesky factor of N~.  The errors of every output grow like
+ *                  1 / pivot_min_joint.  fixed_weight and is_known_inlier are ignored.
+ * A set whose removal leaves the graph without another way to some relative pose (a bridge; two edges that form a cut) makes
+ * N~ singular.  Refused behind the covariance path, in this order, every output untouched and *res all zero: a record whose
+ * pivot_min is not above min_redundancy, the record named; a non-positive pivot of N~, the pivot block named; a
+ * pivot_min_joint not above min_redundancy ("the records together leave no redundancy").
+ * Refused before any device work with a message that begins "linear_removal:", every output untouched: every refusal of
+ * dpgo_team_linear_update; a weight that is not finite and positive; a new_weight that is negative, not finite or not below
+ * the weight; min_redundancy outside (0, 1).  Every refusal of the chosen covariance path carries over with its own message.
+ * Every sum runs in index order with fused multiply-adds and there are no floating-point atomics: two calls give the same
+ * bytes.  Changes no solver state, the team's weights included.  There is no call across teams. */
+int dpgo_team_linear_removal(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block, int num,
+                             const dpgo_measurement_t *records, const double *new_weight /* num, or NULL: all 0 */,
+                             double min_redundancy, int num_pairs, const int *pairs, double *T_new, double *delta /* 6 N */,
+                             double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_loo, double *pivot_min /* num */,
+                             double *scalars /* d2_joint, logdet_N, logdet_R, pivot_min_joint */, dpgo_covariance_t *res);
 /* ---- the most informative candidate closures under a budget (csrc/select.hip) ----
  * Asked before anything is measured: of num = P proposed pose pairs of one team, which `budget` would tighten the estimate
  * most.  T, Sigma, the perturbation, J_i, J_j and Sigma_meas are those of dpgo_team_gate_candidates, A, R and
