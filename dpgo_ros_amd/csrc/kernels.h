@@ -97,6 +97,8 @@ int step_fe_carry_max_poses();
 // dpgo_dev.h).  m0: leading chunks of every agent's order that are private (step_fd_pick_m0 of the team's minimum; 0: the
 // team cannot run it).  pacc_in / pacc_out: the partial sums this launch continues / leaves, [workgroup][r][256]
 int step_fd_pick_m0(int min_private_chunks);
+// the launch's head (step_head.h: the leading arguments its first requests are formed from) can stand for this descriptor
+bool step_fd_head_ok(const AgentDev &d, int r, int m0);
 // (K deep-carried iterations in ONE persistent launch was built, measured slower than one launch per iteration, and
 // removed: profiles/r06_deep_carry.md)
 // behind k_fd_prime: the row products of the run's first two agents and the private partial sums of the first

@@ -39,11 +39,24 @@
 //     wave 7     coefficients of the shared edges -> LDS (E); its quarter of the product (F); look-ahead of the other
 //                agents' poses + Y
 //   Waves 4-7 run at raised priority while they are on the chain.
-// Where a launch's 12.6 us go (profiles/r06_deep_carry.md): 2.8 until everything is requested (134 KB per CU in front of
+// The launch's arguments are a HEAD of thirteen plain dwords (step_head.h: the agent's first work vector, M, the partial
+// sums, the packed coefficients, n | npub, nshared | parity | flags, the ids of the last chunks, the workgroup count) and,
+// behind it, everything else in one struct (FdArgs: the descriptor, what the launch needs of the next two agents, ...).  The
+// head is delivered in SGPRs at wave launch (the object is built with -amdgpu-kernarg-preload-count=14; where the firmware
+// does not preload, a prologue the compiler emits fetches the same dwords), FdArgs sits in memory nobody has touched.  So
+// every role forms its FIRST requests from the head alone -- the streamers the carried rows; the chain waves W / X, their
+// quarter of the last chunks, the operands of the tail; wave 6 its quarter; wave 7 the coefficients and its quarter -- and
+// only then calls fd_args_behind_requests: one word of every line of FdArgs touched, all in flight at once, and no load of
+// the struct can be moved above that point (where the wait for it would stand in front of those requests: the kernel's one
+// barrier, whose LDS write shares the scalar loads' counter, waited for the arguments in every wave).  Nothing in front of
+// the barrier reads memory: the workgroup's place in the grid follows from the head too (profiles/r21_step_head.md).
+// Where a launch's 12.6 us went in round 6 (profiles/r06_deep_carry.md): 2.8 until everything is requested (134 KB per CU in front of
 // the stream -- every workgroup finishes ALL public poses itself, the price of no exchange inside the launch), 1.0 until the
 // edges' operands have landed, 1.9 gradient of the public poses, 0.9 product over the last chunks, 0.5 reduction, 3.2 tail,
 // 2.2 from the last workgroup's end to the next launch's first instruction.  The stream (128 KB per CU) lands under all
-// of it: the streamers are done 3 us before the tail.
+// of it: the streamers are done 3 us before the tail.  With the head the launch takes 11.3 us dispatch to dispatch
+// (12.5 without, same session): the first requests of every role moved forward by 0.1-0.2 us only -- a data trip remains --,
+// most of the gain is in front of the first instruction and behind the last (r21_step_head.md: stamps of both builds).
 // Same arithmetic on the same operands in the same order as k_step_fe / the two-launch sequence: the iterates are BITWISE
 // theirs (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).  The Nesterov scalars (nest_ahead), the books
 // (step_books), the look-ahead map (lookahead_map) and the step of the two poses (step_two_poses) are the text of
@@ -52,6 +65,7 @@
 // keeps its own control flow around the shared map: as a function shared with k_step_fe's second wave it cost this kernel
 // 2-4 % more instructions and 0.14 us per launch, profiles/r19_nesterov_step.md.)
 #include "kernel_common.h"
+#include "step_head.h"
 #include <algorithm>
 
 namespace dpgo {
@@ -60,13 +74,11 @@ namespace dpgo {
 // layout, the staging of the shared edges' operands, the product over the last chunks
 constexpr int FD_KC = 2048;
 // build switches of the experiments recorded in profiles/r06_deep_carry.md (every one measured SLOWER than the defaults but
-// the last): DPGO_FD_HEAD -- 16-byte loads per lane of the next agent's slab requested in front of the request hand-off;
+// the last; a fifth, 16-byte loads per lane of the next agent's slab requested in front of the request hand-off, is gone):
 // DPGO_FD_GC_LATE -- the carried rows of the current agent requested behind it; DPGO_FD_PACC_WT -- partial sums stored
 // write-through; DPGO_FD_E_EARLY -- wave 7 hands the coefficients over before it requests its look-ahead operands;
-// DPGO_FD_KA_PREFETCH (default on) -- one word of every line of the kernel arguments touched up front
-#ifndef DPGO_FD_HEAD
-#define DPGO_FD_HEAD 0
-#endif
+// DPGO_FD_KA_PREFETCH (default on) -- one word of every line of the launch's argument struct touched as soon as the requests
+// formed from the head are out (fd_args_behind_requests)
 #ifndef DPGO_FD_GC_LATE
 #define DPGO_FD_GC_LATE 0
 #endif
@@ -79,7 +91,6 @@ constexpr int FD_KC = 2048;
 #ifndef DPGO_FD_KA_PREFETCH
 #define DPGO_FD_KA_PREFETCH 1
 #endif
-constexpr int FD_HEAD = DPGO_FD_HEAD;  // 16-byte loads per lane of the NEXT agent's private chunks requested in front of the request hand-off
 
 // hand-offs between the waves of the workgroup: counters in LDS (see the head of the file)
 enum { FD_SY_C = 0, FD_SY_E, FD_SY_D, FD_SY_F, FD_SY_N, FD_SY_RQ, FD_SY_COUNT = 8 };
@@ -135,23 +146,41 @@ struct FdXn {
 
 template <int R>
 __device__ __forceinline__ void fd_xn_request(const AgentDev &ag, const FeBases &fb, int parity, int ln, FdXn<R> &xr) {
+  // the agents' bases and pose counts as scalar VALUES in front of the selects.  (Left as expressions of the arguments the
+  // compiler selects the ADDRESS instead and fetches the base with a vector load from the argument segment, the count under a
+  // branch on the parity: the wait for either is a wait for EVERYTHING the wave has requested -- its quarter of the last
+  // chunks included, and once per slot.  Read off the ISA.)
+  const double *ybs[LOOKAHEAD_MAX_AGENTS];
+  int yns[LOOKAHEAD_MAX_AGENTS];
+#pragma unroll
+  for (int k = 0; k < LOOKAHEAD_MAX_AGENTS; ++k) { ybs[k] = fb.ybase[k]; yns[k] = fb.npose[k]; }
+  static_assert(LOOKAHEAD_MAX_AGENTS == 8, "one operand below per agent");
+  // (all sixteen in ONE statement: one wait for the scalar loads, not one per value)
+  asm volatile("" : "+s"(ybs[0]), "+s"(ybs[1]), "+s"(ybs[2]), "+s"(ybs[3]), "+s"(ybs[4]), "+s"(ybs[5]), "+s"(ybs[6]), "+s"(ybs[7]),
+               "+s"(yns[0]), "+s"(yns[1]), "+s"(yns[2]), "+s"(yns[3]), "+s"(yns[4]), "+s"(yns[5]), "+s"(yns[6]), "+s"(yns[7]));
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     {  // (every slot, edges or not: loads under a wave-uniform `if` leave the compiler without a count of what is in flight
        // behind the join, and the wait in front of the LDS writes becomes a wait for EVERYTHING the wave has requested)
-      unsigned wsel = 0;
+      // word ln >> 1 of the slot's 32: a binary tree of selects on the bits of the index -- five lane masks in scalar
+      // registers where a chain of 32 compares held 32 pairs, more than the wave has beside the descriptor's words
+      unsigned wt[32];
 #pragma unroll
-      for (int k = 0; k < 32; ++k) {
-        const unsigned wk = ag.fe_code[(32 * q + k < FE_MAX_EDGES / 2) ? 32 * q + k : FE_MAX_EDGES / 2 - 1];
-        wsel = ((ln >> 1) == k) ? wk : wsel;
+      for (int k = 0; k < 32; ++k) wt[k] = ag.fe_code[(32 * q + k < FE_MAX_EDGES / 2) ? 32 * q + k : FE_MAX_EDGES / 2 - 1];
+#pragma unroll
+      for (int bit = 0; bit < 5; ++bit) {
+        const bool up = ((ln >> 1) >> bit) & 1;
+#pragma unroll
+        for (int k = 0; k < (16 >> bit); ++k) wt[k] = up ? wt[2 * k + 1] : wt[2 * k];
       }
+      const unsigned wsel = wt[0];
       // (lanes beyond the last edge read the pose of an edge that exists: words beyond the last edge hold zeros = agent 0, frame 0)
       const unsigned code = (ln & 1) ? (wsel >> 16) : (wsel & 0xffffu);
       const int sa = (int)(code >> 12), sf = (int)(code & 0xfffu);
-      const double *yb = fb.ybase[0];
-      int yn = fb.npose[0];
+      const double *yb = ybs[0];
+      int yn = yns[0];
 #pragma unroll
-      for (int k = 1; k < LOOKAHEAD_MAX_AGENTS; ++k) { yb = (sa == k) ? fb.ybase[k] : yb; yn = (sa == k) ? fb.npose[k] : yn; }
+      for (int k = 1; k < LOOKAHEAD_MAX_AGENTS; ++k) { yb = (sa == k) ? ybs[k] : yb; yn = (sa == k) ? yns[k] : yn; }
       const double *xp = yb + (parity ? (size_t)B_ALT * 4 * R * yn : (size_t)0) + (size_t)sf * 4 * R;
 #pragma unroll
       for (int k = 0; k < 2 * R; ++k) xr.v[q][k] = ld2(xp + 2 * k);
@@ -160,9 +189,9 @@ __device__ __forceinline__ void fd_xn_request(const AgentDev &ag, const FeBases 
 }
 
 template <int R>
-__device__ __forceinline__ void fd_xn_to_lds(const AgentDev &ag, int ln, const FdXn<R> &xr, double *Es) {
+__device__ __forceinline__ void fd_xn_to_lds(int nshared, int ln, const FdXn<R> &xr, double *Es) {
   constexpr int EPE = 4 * R + 16;
-  int nsh = ag.nshared;
+  int nsh = nshared;
   asm volatile("" : "+v"(nsh));  // (see fd_cf_to_lds)
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
@@ -179,19 +208,19 @@ struct FdCf {
   double2 v[TRIPS];
 };
 
-__device__ __forceinline__ void fd_cf_request(const AgentDev &ag, int ln, FdCf &cr) {
-  const int nit = ag.nshared * 8;
+__device__ __forceinline__ void fd_cf_request(const double *fe_coef, int nshared, int ln, FdCf &cr) {
+  const int nit = nshared * 8;
 #pragma unroll
-  for (int j = 0; j < FdCf::TRIPS; ++j) cr.v[j] = ld2(ag.fe_coef + 2 * min(64 * j + ln, nit - 1));  // (every trip: see fd_xn_request)
+  for (int j = 0; j < FdCf::TRIPS; ++j) cr.v[j] = ld2(fe_coef + 2 * min(64 * j + ln, nit - 1));  // (every trip: see fd_xn_request)
 }
 
 template <int R>
-__device__ __forceinline__ void fd_cf_to_lds(const AgentDev &ag, int ln, const FdCf &cr, double *Es) {
+__device__ __forceinline__ void fd_cf_to_lds(int nshared, int ln, const FdCf &cr, double *Es) {
   constexpr int EPE = 4 * R + 16;
   // (held in a register: left as an expression of the descriptor the count was RE-READ from the kernel arguments in front of
   // every one of the 20 stores below, each time behind a wait for the scalar load and the LDS store before it -- 0.9 us
   // between this wave's last request and the hand-off the chain waits for; read off the ISA, round 6)
-  int nit = ag.nshared * 8;
+  int nit = nshared * 8;
   asm volatile("" : "+v"(nit));
 #pragma unroll
   for (int j = 0; j < FdCf::TRIPS; ++j) {
@@ -210,12 +239,14 @@ struct FdCur {
 };
 
 template <int R, int M0, int NC>
-__device__ __forceinline__ void fd_cur_request(const AgentDev &ag, const double *pacc_in, int bx, int nblk, int l, FdCur<R, NC> &cu) {
+__device__ __forceinline__ void fd_cur_request(const FdHead &hd, int N4, int bx, int nblk, int l, FdCur<R, NC> &cu) {
+  static_assert(NC <= FD_HEAD_ORD_MAX && M0 + NC == 32, "the head holds the ids of the last chunks");
   const int cg = (l >> 5) & 7, kl = l & 31;
-  const int N4 = ag.N4, col = 8 * bx + cg;
-  const double *Mc = ag.M + (size_t)((col < N4) ? col : 0) * N4;
+  const int col = 8 * bx + cg;
+  const double *pacc_in = hd.pacc_in;
+  const double *Mc = hd.M + (size_t)((col < N4) ? col : 0) * N4;
 #pragma unroll
-  for (int i = 0; i < NC; ++i) cu.mc[i] = ld2_nt(Mc + min(2 * kl + 64 * (int)ag.fe_ord[M0 + i], N4 - 2));
+  for (int i = 0; i < NC; ++i) cu.mc[i] = ld2_nt(Mc + min(2 * kl + 64 * fd_head_ord(hd.ord_lo, hd.ord_hi, i), N4 - 2));
 #pragma unroll
   for (int a = 0; a < R; ++a) cu.pa[a] = gp(pacc_in)[((size_t)min(bx, nblk - 1) * R + a) * 256 + l];
 }
@@ -242,6 +273,7 @@ __device__ __forceinline__ void fd_cur_product(const FdCur<R, NC> &cu, const dou
   for (int a = 0; a < R; ++a) red[kl * (8 * R + 1) + cg * R + a] = acc[a];
 }
 
+#define FD_TRACE_PART (fd_args_behind_requests<false>().ag.part)
 #ifdef DPGO_FE_TRACE
 #ifndef DPGO_FE_TRACE_BLOCK
 #define DPGO_FE_TRACE_BLOCK 100
@@ -252,51 +284,82 @@ __device__ __forceinline__ void fd_cur_product(const FdCur<R, NC> &cu, const dou
 #endif
 #define FD_STAMP(k) do { if (((DPGO_FD_STAMP_MASK >> (k)) & 1) && (threadIdx.x & 63) == 0) fd_stamps[(threadIdx.x >> 6) * 16 + (k)] = wall_clock64(); } while (0)
 #define FD_FLUSH() do { if ((threadIdx.x & 63) == 0) { const int w_ = threadIdx.x >> 6; \
-    if (blockIdx.x == DPGO_FE_TRACE_BLOCK) for (int k_ = 0; k_ < 16; ++k_) ag.part[PART_E + 4000 * PART_STRIDE + w_ * 16 + k_] = (double)fd_stamps[w_ * 16 + k_]; \
-    if (w_ == 4) { ag.part[PART_E + (4100 + 2 * (int)blockIdx.x) * PART_STRIDE] = (double)fd_stamps[4 * 16]; ag.part[PART_E + (4100 + 2 * (int)blockIdx.x) * PART_STRIDE + 1] = (double)fd_stamps[4 * 16 + 15]; } \
-    if (w_ == 0) { ag.part[PART_E + (4100 + 2 * (int)blockIdx.x) * PART_STRIDE + 2] = (double)fd_stamps[15]; } } } while (0)
+    if (blockIdx.x == DPGO_FE_TRACE_BLOCK) for (int k_ = 0; k_ < 16; ++k_) FD_TRACE_PART[PART_E + 4000 * PART_STRIDE + w_ * 16 + k_] = (double)fd_stamps[w_ * 16 + k_]; \
+    if (w_ == 4) { FD_TRACE_PART[PART_E + (4100 + 2 * (int)blockIdx.x) * PART_STRIDE] = (double)fd_stamps[4 * 16]; FD_TRACE_PART[PART_E + (4100 + 2 * (int)blockIdx.x) * PART_STRIDE + 1] = (double)fd_stamps[4 * 16 + 15]; } \
+    if (w_ == 0) { FD_TRACE_PART[PART_E + (4100 + 2 * (int)blockIdx.x) * PART_STRIDE + 2] = (double)fd_stamps[15]; } } } while (0)
 #elif defined(DPGO_FD_ENDS)
 // -DDPGO_FD_ENDS: nothing but the time every wave of workgroup 100 leaves, straight to memory (one store per wave: the
 // build runs within 0.1 us of the product build) -- PART_E words [4000 + 16 w + 15]; wave 4 also leaves its start [64]
 #define FD_TRACE_DECL
-#define FD_STAMP(k) do { if ((k) == 0 && blockIdx.x == 100 && threadIdx.x == 256) ag.part[PART_E + 4000 * PART_STRIDE + 64] = (double)wall_clock64(); } while (0)
-#define FD_FLUSH() do { if (blockIdx.x == 100 && (threadIdx.x & 63) == 0) ag.part[PART_E + 4000 * PART_STRIDE + (threadIdx.x >> 6) * 16 + 15] = (double)wall_clock64(); } while (0)
+#define FD_STAMP(k) do { if ((k) == 0 && blockIdx.x == 100 && threadIdx.x == 256) FD_TRACE_PART[PART_E + 4000 * PART_STRIDE + 64] = (double)wall_clock64(); } while (0)
+#define FD_FLUSH() do { if (blockIdx.x == 100 && (threadIdx.x & 63) == 0) FD_TRACE_PART[PART_E + 4000 * PART_STRIDE + (threadIdx.x >> 6) * 16 + 15] = (double)wall_clock64(); } while (0)
 #else
 #define FD_TRACE_DECL
 #define FD_STAMP(k) do { } while (0)
 #define FD_FLUSH() do { } while (0)
 #endif
 
-template <int R, int M0>
-__global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int next_sel, double step, int num_robots, int restart_interval,
-                                                 const NestState *nest_src, NestState *nest_dst, int parity, const AgentDev agv,
-                                                 int next3_sel, int flags, const FdNext nx, const FeBases fb,
-                                                 const double *__restrict__ pacc_in, double *__restrict__ pacc_out, int nblk_all,
-                                                 int num_agents) {
-  const AgentDev &ag = agv;
+// everything a launch is told beyond its head (step_head.h), by value in ONE struct behind it
+struct FdArgs {
+  AgentDev ag;
+  FdNext nx;
+  FeBases fb;
+  TeamDev *team;
+  const NestState *nest_src;
+  NestState *nest_dst;
+  double *pacc_out;
+  double step;
+  int sel, next_sel, next3_sel, num_robots, restart_interval, num_agents;
+};
+
+// The head arrives in registers; FdArgs (1.6 KB) sits in memory nobody has touched.  A role forms its first requests from
+// the head alone and calls this BEHIND them: the struct as it may be read from here on -- the compiler can move no load of
+// it above this point, where a wait for it would stand in front of those requests --, one word of each of its 64-byte lines
+// touched first, all in flight at once (fetched where they are first used, every scalar load misses in turn; traced in round
+// 6: the wave that needs the edges' codes issued its first request 2.7 us into the launch).  TOUCH = false: the streamers,
+// which read it only behind the request hand-off.
+// (The struct is addressed through the argument segment, where the launch ABI puts it: the arguments in order, each at its
+// natural alignment.  Through the kernel's parameter the compiler would first copy all of it to scratch.)
+constexpr size_t FD_ARGS_OFFSET = (4 * FD_HEAD_DWORDS + alignof(FdArgs) - 1) / alignof(FdArgs) * alignof(FdArgs);
+template <bool TOUCH>
+__device__ __forceinline__ const FdArgs &fd_args_behind_requests() {
+  typedef const __attribute__((address_space(4))) char *SegPtr;
+  __builtin_amdgcn_sched_barrier(0);
+  SegPtr p = (SegPtr)__builtin_amdgcn_kernarg_segment_ptr() + FD_ARGS_OFFSET;
+  asm volatile("" : "+s"(p)::"memory");
 #if DPGO_FD_KA_PREFETCH
-  {
-    // The launch's arguments (1.5 KB: the agent's descriptor by value, what it needs of the next two) sit in memory nobody
-    // has touched: fetched where they are first used, every scalar load misses in turn (traced: the wave that needs the
-    // edges' codes issued its first request 2.7 us into the launch).  One word of every 64-byte line now, all in flight at
-    // once: what follows hits the scalar cache.
-    const unsigned *ka = (const unsigned *)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr int KA_LINES = (int)((sizeof(AgentDev) + sizeof(FdNext) + sizeof(FeBases) + 160 + 63) / 64);
-    unsigned touch = 0;
-#pragma unroll
-    for (int i = 0; i < KA_LINES; ++i) touch |= ka[16 * i];
-    asm volatile("" ::"s"(touch));
+  if constexpr (TOUCH) {
+    // (every 64th byte and the last word -- the struct does not start on a line --, consumed TOGETHER: folded into one word
+    // the compiler fetched them in groups of eight, a wait and a cold trip for each group)
+    const __attribute__((address_space(4))) unsigned *ka = (const __attribute__((address_space(4))) unsigned *)p;
+    static_assert(sizeof(FdArgs) > 19 * 64 && sizeof(FdArgs) <= 20 * 64, "one operand below for every line of FdArgs");
+    constexpr int LAST = (int)(sizeof(FdArgs) / 4) - 1;
+    asm volatile("" ::"s"(ka[0]), "s"(ka[16]), "s"(ka[32]), "s"(ka[48]), "s"(ka[64]), "s"(ka[80]), "s"(ka[96]), "s"(ka[112]),
+                 "s"(ka[128]), "s"(ka[144]), "s"(ka[160]), "s"(ka[176]), "s"(ka[192]), "s"(ka[208]), "s"(ka[224]), "s"(ka[240]),
+                 "s"(ka[256]), "s"(ka[272]), "s"(ka[288]), "s"(ka[304]), "s"(ka[LAST]));
   }
 #endif
+  return *(const FdArgs *)p;
+}
+
+template <int R, int M0>
+__global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *hd_M, const double *__restrict__ hd_pacc_in,
+                                                 const double *hd_fe_coef, unsigned hd_np, unsigned hd_sf, unsigned hd_ord_lo,
+                                                 unsigned hd_ord_hi, int nblk_all, const FdArgs fa) {
+  // ---- the head (step_head.h): nothing down to the roles' calls of fd_args_behind_requests reads anything else
+  const FdHead hd = {hd_buf0, hd_M, hd_pacc_in, hd_fe_coef, hd_np, hd_sf, hd_ord_lo, hd_ord_hi, nblk_all};
+  const int n = fd_head_n(hd.np), N4 = 4 * n, hd_npub = fd_head_npub(hd.np), hd_nshared = fd_head_nshared(hd.sf);
+  const int parity = fd_head_parity(hd.sf), flags = fd_head_flags(hd.sf);
   // the poses live twice (step_fused.hip): this launch reads the copy of its parity and writes the other one
-  const double *__restrict__ Xr = ag.buf[parity ? B_XALT : B_X];
-  const double *__restrict__ Yr = ag.buf[parity ? B_YALT : B_Y];
-  double *__restrict__ Xw = ag.buf[parity ? B_X : B_XALT];
-  double *__restrict__ Yw = ag.buf[parity ? B_Y : B_YALT];
+  const double *__restrict__ Xr = fd_head_buf(hd.buf0, R, n, parity ? B_XALT : B_X);
+  const double *__restrict__ Yr = fd_head_buf(hd.buf0, R, n, parity ? B_YALT : B_Y);
+  double *__restrict__ Xw = fd_head_buf(hd.buf0, R, n, parity ? B_X : B_XALT);
+  double *__restrict__ Yw = fd_head_buf(hd.buf0, R, n, parity ? B_Y : B_YALT);
   const int hb = (int)blockIdx.x;
-  const int bx = (hb % 8) * ((int)gridDim.x / 8) + hb / 8;  // XCD-aware block order, as in k_precond
+  // XCD-aware block order, as in k_precond.  (The grid is nblk_all rounded up to a multiple of 8, launch_step_fd: gridDim
+  // itself is a word of the hidden arguments, behind FdArgs)
+  const int bx = (hb % 8) * ((nblk_all + 7) / 8) + hb / 8;
   const int tid = threadIdx.x;
-  const int N4 = ag.N4, n = ag.n;
   const int nblk = (N4 + 7) / 8;
   if (bx >= nblk_all) return;
   // (the grid covers the largest agent of the team: a workgroup beyond this agent's columns still takes its share of the
@@ -330,24 +393,25 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     // the rows of this agent's carried gradient that the last NC chunks meet: positions [M0 * 64 R, N4 R)
     constexpr int NGC = ((KC - 64 * M0) * R / 2 + 255) / 256;
     double2 gc[NGC];
+    const double *Gc = fd_head_buf(hd.buf0, R, n, B_CARRY_G);
 #if !DPGO_FD_GC_LATE
     {
-      const double *Gc = ag.buf[B_CARRY_G];
 #pragma unroll
       for (int u = 0; u < NGC; ++u) gc[u] = ld2(Gc + min(M0 * 64 * R + 2 * (tid + 256 * u), N4 * R - 2));
     }
 #endif
+    // (FdArgs behind the carried rows' requests.  The streamers touch none of its lines up front -- waves 4-7 do --: the
+    // chain needs these rows only behind its gradient phase, and the stream waits for the request hand-off anyway)
+    const FdArgs &as = fd_args_behind_requests<false>();
+    const FdNext &nx = as.nx;
     const int cold = 8 * bx + cg;
     const int N4d = nx.N4d;
     const double *Md = nx.Md + (size_t)((cold < N4d) ? cold : 0) * N4d;
     double2 mn[M0];
-#pragma unroll
-    for (int i = 0; i < FD_HEAD; ++i) mn[i] = ld2_nt(Md + min(2 * kl + 64 * (int)nx.ord_d[i], N4d - 2));
     FD_STAMP(10);
     __builtin_amdgcn_sched_barrier(0);
 #if DPGO_FD_GC_LATE
     {
-      const double *Gc = ag.buf[B_CARRY_G];
 #pragma unroll
       for (int u = 0; u < NGC; ++u) gc[u] = ld2(Gc + min(M0 * 64 * R + 2 * (tid + 256 * u), N4 * R - 2));
     }
@@ -371,7 +435,7 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
 #pragma unroll
     for (int u = 0; u < NGN; ++u) gn[u] = ld2(nx.Gd + min(2 * (tid + 256 * u), M0 * 64 * R - 2));
 #pragma unroll
-    for (int i = FD_HEAD; i < M0; ++i) mn[i] = ld2_nt(Md + min(2 * kl + 64 * (int)nx.ord_d[i], N4d - 2));
+    for (int i = 0; i < M0; ++i) mn[i] = ld2_nt(Md + min(2 * kl + 64 * (int)nx.ord_d[i], N4d - 2));
     FD_STAMP(12);
 #pragma unroll
     for (int u = 0; u < NGN; ++u) {
@@ -387,6 +451,13 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     for (int a = 0; a < R; ++a) acc[a] = 0;
 #pragma unroll
     for (int i = 0; i < M0; ++i) {
+      if (i % 8 == 0 && i > 0) {
+        // (the rows of no more than eight chunks read ahead of their multiply-adds: beside the slab's 96 registers the 36
+        // reads the scheduler otherwise hoists above the first multiply-add fit only by luck, and a spill is scratch
+        // traffic in the queue the chain waits on)
+#pragma unroll
+        for (int a = 0; a < R; ++a) asm volatile("" : "+v"(acc[a])::"memory");
+      }
       const int k = 2 * kl + 64 * i;
       double wv[2 * R];
 #pragma unroll
@@ -400,9 +471,9 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     if ((flags & FD_P) && bx < nx.nblk_d) {
 #pragma unroll
 #if DPGO_FD_PACC_WT
-      for (int a = 0; a < R; ++a) st_c(pacc_out + ((size_t)bx * R + a) * 256 + tid, acc[a]);  // (write-through: not left dirty in L2 for the kernel boundary)
+      for (int a = 0; a < R; ++a) st_c(as.pacc_out + ((size_t)bx * R + a) * 256 + tid, acc[a]);  // (write-through: not left dirty in L2 for the kernel boundary)
 #else
-      for (int a = 0; a < R; ++a) gp(pacc_out)[((size_t)bx * R + a) * 256 + tid] = acc[a];
+      for (int a = 0; a < R; ++a) gp(as.pacc_out)[((size_t)bx * R + a) * 256 + tid] = acc[a];
 #endif
     }
     FD_STAMP(15);
@@ -414,15 +485,14 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     // ================================================================ the chain: gradient of the public poses, product over the
     // last chunks, step of the workgroup's poses
     const int g = cwv - 4;
-    const int npub = ag.npub;
+    // ---- from the head: W / X of the public poses, this wave's quarter of the last chunks, the operands of the tail
+    const int npub = hd_npub;
     const int pq = 64 * g + ln;
     const bool pact = pq < npub;
     const int pqc = pact ? pq : 0;
-    const int pj = ag.pub_pose[pqc];
-    const int pe0 = ag.pub_ptr[pqc], pe1 = ag.pub_ptr[pqc + (pact ? 1 : 0)];
     double w[4 * R], x[4 * R];
     {
-      const double *Wc = ag.buf[B_CARRY_W], *Xc = ag.buf[B_CARRY_X];
+      const double *Wc = fd_head_buf(hd.buf0, R, n, B_CARRY_W), *Xc = fd_head_buf(hd.buf0, R, n, B_CARRY_X);
 #pragma unroll
       for (int i = 0; i < 2 * R; ++i) {
         // ([entry pair][public pose][2]: one 16-byte load per pair, a wave's 64 lanes one contiguous KB -- half the requests)
@@ -432,7 +502,23 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     }
     FD_STAMP(14);
     FdCur<R, NC> cu;
-    fd_cur_request<R, M0, NC>(ag, pacc_in, bx, nblk, tid - 256, cu);
+    fd_cur_request<R, M0, NC>(hd, N4, bx, nblk, tid - 256, cu);
+    // operands of the tail (the lanes of wave 4 that will hold them; wave 5's copies are never used)
+    const int tl = tid - 256 - 64 * g;
+    const size_t own_off = (size_t)((tl >= 4 * R) ? max(pj1, 0) : pj0) * 4 * R + (size_t)(tl % (4 * R));
+    double pre_x = 0, pre_v = 0, pre_y = 0, pre_p = 0;
+    if (tl < npose * 4 * R) {
+      pre_x = gp(Xr)[own_off];
+      pre_v = gp(fd_head_buf(hd.buf0, R, n, B_V))[own_off];
+      pre_y = gp(Yr)[own_off];
+      pre_p = gp(fd_head_buf(hd.buf0, R, n, B_XPREV))[own_off];
+    }
+    // ---- behind them, from FdArgs: which pose and which edges, the rows of W, the Nesterov state
+    const FdArgs &as = fd_args_behind_requests<true>();
+    const AgentDev &ag = as.ag;
+    const FdNext &nx = as.nx;
+    const int pj = ag.pub_pose[pqc];
+    const int pe0 = ag.pub_ptr[pqc], pe1 = ag.pub_ptr[pqc + (pact ? 1 : 0)];
     // W (wave 5, behind its quarter of the product): the indices of the rows now (wave 4's copies are never used)
     const int npw = (nx.n_e + nblk_all - 1) / nblk_all;  // (<= 2)
     const int wls = ln / (4 * R), we = ln - wls * (4 * R);
@@ -444,17 +530,8 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
 #pragma unroll
     for (int u = 0; u < 8; ++u) ii[u] = gp(nx.soa_col_e)[((size_t)wtile * wdn + min(u, wdn - 1)) * 64 + wpl];
     const int qi = gp(nx.pub_index_e)[pwc];
-    // operands of the tail (the lanes of wave 4 that will hold them; wave 5's copies are never used)
-    const int tl = tid - 256 - 64 * g;
-    const size_t own_off = (size_t)((tl >= 4 * R) ? max(pj1, 0) : pj0) * 4 * R + (size_t)(tl % (4 * R));
-    double pre_x = 0, pre_v = 0, pre_y = 0, pre_p = 0;
-    if (tl < npose * 4 * R) {
-      pre_x = gp(Xr)[own_off];
-      pre_v = gp(ag.buf[B_V])[own_off];
-      pre_y = gp(Yr)[own_off];
-      pre_p = gp(ag.buf[B_XPREV])[own_off];
-    }
-    const NestState ns = nest_src[sel];
+    const int sel = as.sel, next_sel = as.next_sel, num_robots = as.num_robots, restart_interval = as.restart_interval;
+    const NestState ns = as.nest_src[sel];
     __builtin_amdgcn_s_setprio(3);  // (the chain's instructions go first: the streamers' product shares the LDS with it)
     FD_STAMP(10);
     fd_signal_requested(&sy[FD_SY_RQ]);
@@ -559,7 +636,7 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
     if (ln < 2) tl_rel[ln] = 0.0;
     // ---- the step of the workgroup's two poses, one pose on 16 lanes
     const TwoPoseLds tl2 = {zs, Ysh, Esh[0], Esh[1], Psh, tl_x, tl_v, tl_y, tl_s, tl_rel};
-    step_two_poses<R>(ag, Xw, Yw, tl2, ln, npose, pj0, pj1, step, nn, ahead_opt, in, stats, lastat, [&](int k) { FD_STAMP(k); });
+    step_two_poses<R>(ag, Xw, Yw, tl2, ln, npose, pj0, pj1, as.step, nn, ahead_opt, in, stats, lastat, [&](int k) { FD_STAMP(k); });
     if (stats) {
       // (k_precond: the two poses' sums through wave_sum, lane 0 stores)
       WSYNC();
@@ -576,23 +653,25 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
   // then the row products of the agent two iterations ahead (6) / the look-ahead of the other agents' poses (7)
   const int h = cwv - 6;
   if (h == 0) {
-    FdXn<R> er;
-    fd_xn_request<R>(ag, fb, parity, ln, er);
-    FD_STAMP(9);
+    // (its quarter of the last chunks from the head first: the neighbour poses need the edges' codes, 320 B of FdArgs)
     FdCur<R, NC> cu;
-    fd_cur_request<R, M0, NC>(ag, pacc_in, bx, nblk, tid - 256, cu);
+    fd_cur_request<R, M0, NC>(hd, N4, bx, nblk, tid - 256, cu);
+    const FdArgs &as = fd_args_behind_requests<true>();
+    FdXn<R> er;
+    fd_xn_request<R>(as.ag, as.fb, parity, ln, er);
+    FD_STAMP(9);
     FD_STAMP(10);
     fd_signal_requested(&sy[FD_SY_RQ]);
     FD_STAMP(11);
     __builtin_amdgcn_s_setprio(3);
-    fd_xn_to_lds<R>(ag, ln, er, Es);
+    fd_xn_to_lds<R>(hd_nshared, ln, er, Es);
     fd_signal(&sy[FD_SY_E]);
     FD_STAMP(8);
     fd_wait(&sy[FD_SY_D], 2);  // this wave's quarter of the product over the last chunks
     fd_cur_product<R, M0, NC>(cu, vs, red, tid - 256);
     fd_signal(&sy[FD_SY_F]);
     if (bx == 0 && ln < LOOKAHEAD_MAX_AGENTS && in)  // the books, one lane per agent
-      step_books(team, nest_src, nest_dst, ln, num_agents, sel, next_sel, num_robots, restart_interval);
+      step_books(as.team, as.nest_src, as.nest_dst, ln, as.num_agents, as.sel, as.next_sel, as.num_robots, as.restart_interval);
     FD_STAMP(14);
     FD_FLUSH();
     return;
@@ -602,15 +681,19 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
   // per pose, k_step_fe's second wave), every address from the launch's arguments
   {
     FdCf er;
-    fd_cf_request(ag, ln, er);
+    fd_cf_request(hd.fe_coef, hd_nshared, ln, er);
     FD_STAMP(9);
     FdCur<R, NC> cu;
-    fd_cur_request<R, M0, NC>(ag, pacc_in, bx, nblk, tid - 256, cu);
+    fd_cur_request<R, M0, NC>(hd, N4, bx, nblk, tid - 256, cu);
+    const FdArgs &as = fd_args_behind_requests<true>();
+    const FeBases &fb = as.fb;
+    const int sel = as.sel, next_sel = as.next_sel, next3_sel = as.next3_sel, num_agents = as.num_agents;
+    const int num_robots = as.num_robots, restart_interval = as.restart_interval;
     // (the coefficients go to LDS as soon as they are here -- the chain waits for them --, the look-ahead operands are
     // requested behind that)
 #if DPGO_FD_E_EARLY
     __builtin_amdgcn_sched_barrier(0);
-    fd_cf_to_lds<R>(ag, ln, er, Es);
+    fd_cf_to_lds<R>(hd_nshared, ln, er, Es);
     fd_signal(&sy[FD_SY_E]);
     FD_STAMP(8);
     __builtin_amdgcn_sched_barrier(0);
@@ -648,13 +731,13 @@ __global__ __launch_bounds__(512) void k_step_fd(TeamDev *team, int sel, int nex
       const double2 tx = ld2(xr + o + 2 * i), tv = ld2(va + o + 2 * i);
       la_x[2 * i] = tx.x; la_x[2 * i + 1] = tx.y; la_v[2 * i] = tv.x; la_v[2 * i + 1] = tv.y;
     }
-    const NestState ns = nest_src[sel];
+    const NestState ns = as.nest_src[sel];
     FD_STAMP(10);
     fd_signal_requested(&sy[FD_SY_RQ]);
     FD_STAMP(11);
     __builtin_amdgcn_s_setprio(3);
 #if !DPGO_FD_E_EARLY
-    fd_cf_to_lds<R>(ag, ln, er, Es);
+    fd_cf_to_lds<R>(hd_nshared, ln, er, Es);
     fd_signal(&sy[FD_SY_E]);
     FD_STAMP(8);
 #endif
@@ -897,6 +980,14 @@ void launch_fd_open(const LaunchCtx &c, int m0, int s0, int s1, double *pacc_out
   }
 }
 
+// the head of a launch (step_head.h) can stand for this agent's descriptor at rank r: its fields fit their widths, its work
+// vectors are one allocation (every flag and parity the launches use fits by construction)
+bool step_fd_head_ok(const AgentDev &d, int r, int m0) {
+  FdHead hd;
+  return fd_head_build(hd, d.buf, NBUF, r, d.n, d.N4, d.npub, d.nshared, d.M, d.fe_coef, d.fe_ord, m0, 1, FD_HEAD_FLAGS_MAX, nullptr,
+                       (d.N4 + 7) / 8);
+}
+
 // sel .. : agents c, d, e, f of the head of the file (d, e, f: any valid agent where the flag is off)
 void launch_step_fd(const LaunchCtx &c, int m0, int sel, int next_sel, int next2_sel, int next3_sel, double step, int num_robots,
                     int restart_interval, const NestState *nest_src, NestState *nest_dst, int parity, int flags,
@@ -905,17 +996,25 @@ void launch_step_fd(const LaunchCtx &c, int m0, int sel, int next_sel, int next2
   int nblk_all = 0;
   for (int k = 0; k < c.num_agents; ++k) nblk_all = std::max(nblk_all, (c.host_agents[k].N4 + 7) / 8);
   const int grid = (nblk_all + 7) / 8 * 8;
-  FeBases fb = {};
+  FdArgs fa = {};
+  FeBases &fb = fa.fb;
+  FdNext &nx = fa.nx;
   for (int k = 0; k < c.num_agents && k < LOOKAHEAD_MAX_AGENTS; ++k) { fb.ybase[k] = c.host_agents[k].buf[B_Y]; fb.npose[k] = c.host_agents[k].n; fb.part[k] = c.host_agents[k].part; }
-  FdNext nx = {};
   nx.Md = dd.M; nx.N4d = dd.N4; nx.nblk_d = (dd.N4 + 7) / 8; nx.Gd = dd.buf[B_CARRY_G];
   for (int i = 0; i < 32; ++i) { nx.ord_d[i] = dd.fe_ord[i]; nx.ord_e[i] = de.fe_ord[i]; }
   nx.n_e = de.n; nx.soa_w_e = de.soa_w; nx.npub_e = de.npub; nx.soa_col_e = de.soa_col; nx.soa_val_e = de.soa_val;
   nx.pub_index_e = de.pub_index; nx.Ye = de.buf[B_CARRY_Y]; nx.We = de.buf[B_CARRY_W]; nx.Xe = de.buf[B_CARRY_X]; nx.Ge = de.buf[B_CARRY_G];
-#define FD_LAUNCH(RR, MM)                                                                                                   \
-  hipLaunchKernelGGL((k_step_fd<RR, MM>), dim3(grid), dim3(512), 0, c.stream, c.team, sel, next_sel, step, num_robots,        \
-                     restart_interval, nest_src, nest_dst, parity, d, next3_sel, flags, nx, fb, pacc_in, pacc_out, nblk_all, \
-                     c.num_agents)
+  fa.ag = d;
+  fa.team = c.team; fa.nest_src = nest_src; fa.nest_dst = nest_dst; fa.pacc_out = pacc_out; fa.step = step;
+  fa.sel = sel; fa.next_sel = next_sel; fa.next3_sel = next3_sel; fa.num_robots = num_robots;
+  fa.restart_interval = restart_interval; fa.num_agents = c.num_agents;
+  // (a team takes this form only where every agent's head stands for its descriptor: step_fd_head_ok, fe_deep_m0)
+  FdHead hd;
+  if (!fd_head_build(hd, d.buf, NBUF, c.r, d.n, d.N4, d.npub, d.nshared, d.M, d.fe_coef, d.fe_ord, m0, parity, flags, pacc_in, nblk_all))
+    return;
+#define FD_LAUNCH(RR, MM)                                                                                                    \
+  hipLaunchKernelGGL((k_step_fd<RR, MM>), dim3(grid), dim3(512), 0, c.stream, hd.buf0, hd.M, hd.pacc_in, hd.fe_coef, hd.np, \
+                     hd.sf, hd.ord_lo, hd.ord_hi, hd.nblk_all, fa)
 #define FD_LAUNCH_M(RR)                                   \
   switch (m0) {                                           \
     case 24: FD_LAUNCH(RR, 24); break;                    \

@@ -114,7 +114,8 @@ bool fused_eval_eligible(dpgo_team *t) {
 // The deep-carried form (step_deep.hip) may serve this team: the private part of every agent's product is formed one launch
 // early, its row products two, its evaluation point three -- so every FOUR consecutive agents of the schedule differ; the
 // first 24 chunks of every agent's order are private (24 is returned; 0: not this team); an agent's
-// public poses fit two waves, its shared edges three edge slots of 64, and the partial sums have their buffers.
+// public poses fit two waves, its shared edges three edge slots of 64, the head of a launch can stand for its descriptor
+// (step_head.h: fields within their widths, work vectors one allocation), and the partial sums have their buffers.
 // (The same run as ONE persistent launch was built, measured slower and removed: profiles/r06_deep_carry.md.)
 int fe_deep_m0(dpgo_team *t) {
   if (!t->use_fe_deep || !t->use_fe_carry || !fused_eval_eligible(t)) return 0;
@@ -135,6 +136,8 @@ int fe_deep_m0(dpgo_team *t) {
   int m0 = step_fd_pick_m0(min_priv);
   if (const char *e = std::getenv("DPGO_FD_M0")) { const int f = std::atoi(e); if (f > 0 && f <= min_priv && step_fd_pick_m0(f) == f) m0 = f; }  // (experiments)
   if (m0 == 0) return 0;
+  for (auto &a : t->ag)
+    if (!step_fd_head_ok(a->dev, t->prm.r, m0)) return 0;
   const size_t want = (size_t)2 * nblk_all * t->prm.r * 256;
   if (t->d_fd_pacc.n < want && t->d_fd_pacc.alloc(want)) return 0;
   return m0;

@@ -7,9 +7,12 @@ name=$1; flags=$2
 out=profiles/experiments/build/$name
 mkdir -p $out
 src=dpgo_ros_amd/csrc
+# (step_deep.o as csrc/Makefile builds it: the head of k_step_fd's arguments preloaded, so a trace build matches the product)
+step_deep_flags="-mllvm -amdgpu-kernarg-preload-count=14"
 objs=""
 for f in spmm precond step_fused step_deep rtr_fused linesearch pose_ops dense_inverse twolevel assembly solve team_run capi chordal; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on $flags -c $src/$f.hip -o $out/$f.o &
+  extra=""; [ $f = step_deep ] && extra=$step_deep_flags
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on $extra $flags -c $src/$f.hip -o $out/$f.o &
   objs="$objs $out/$f.o"
 done
 for f in loader frame_align twolevel_plan rank_exchange; do
