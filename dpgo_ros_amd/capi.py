@@ -131,7 +131,8 @@ dpgo_translations_given_rotations dpgo_team_certificate_apply_across dpgo_team_c
 dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
-dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal""".split()
+dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal
+dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across""".split()
 
 
 class DpgoError(RuntimeError):
@@ -347,6 +348,57 @@ class LocalGroup:
 
 def _owner_array(owner_of_robot):
     return np.ascontiguousarray(owner_of_robot, dtype=np.int32)
+
+
+_REC_INTS = ("r1", "p1", "r2", "p2", "fixed_weight", "is_known_inlier")
+_REC_DOUBLES = 4 + 9 + 3 + 3 + 2  # a MEAS_DTYPE record as plain doubles, the integers exact
+
+
+def records_to_doubles(recs):
+    """MEAS_DTYPE records as [K, 21] doubles (r1, p1, r2, p2, R, t, kappa, tau, weight, fixed_weight, is_known_inlier): what a
+    transport's allgather carries"""
+    recs = np.ascontiguousarray(recs, dtype=MEAS_DTYPE).reshape(-1)
+    out = np.zeros((len(recs), _REC_DOUBLES))
+    for c, f in enumerate(("r1", "p1", "r2", "p2")):
+        out[:, c] = recs[f]
+    out[:, 4:13], out[:, 13:16] = recs["R"], recs["t"]
+    out[:, 16], out[:, 17], out[:, 18] = recs["kappa"], recs["tau"], recs["weight"]
+    out[:, 19], out[:, 20] = recs["fixed_weight"], recs["is_known_inlier"]
+    return out
+
+
+def records_from_doubles(x):
+    """the inverse of records_to_doubles"""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, _REC_DOUBLES)
+    recs = np.zeros(len(x), dtype=MEAS_DTYPE)
+    for c, f in enumerate(("r1", "p1", "r2", "p2")):
+        recs[f] = x[:, c].astype(np.int32)
+    recs["R"], recs["t"] = x[:, 4:13], x[:, 13:16]
+    recs["kappa"], recs["tau"], recs["weight"] = x[:, 16], x[:, 17], x[:, 18]
+    recs["fixed_weight"], recs["is_known_inlier"] = x[:, 19].astype(np.int32), x[:, 20].astype(np.int32)
+    return recs
+
+
+def join_records_by_robot(lists_per_rank, owner_of_robot):
+    """One list of MEAS_DTYPE records for the whole problem from the lists of the participants (lists_per_rank[q]: what
+    rank q holds, in its own order; owner_of_robot[i]: the rank that holds robot i).  A record belongs to the lower robot of a
+    shared edge and to r1 otherwise; the joined list takes, robot after robot in id order, that robot's records from the rank
+    that holds it, in the order they have there -- so the weights are the owner's, a copy that the higher robot's rank also
+    lists is dropped, and a shared edge that its rank lists twice (both copies) appears once, as the first.  This is
+    Team.measurements_once() of a single team that holds every robot."""
+    own = np.asarray(owner_of_robot, dtype=np.int64).reshape(-1)
+    out = []
+    for i in range(len(own)):
+        recs = np.ascontiguousarray(lists_per_rank[int(own[i])], dtype=MEAS_DTYPE).reshape(-1)
+        key = np.where(recs["r1"] == recs["r2"], recs["r1"], np.minimum(recs["r1"], recs["r2"]))
+        seen = set()
+        for e in recs[key == i]:
+            edge = (int(e["r1"]), int(e["p1"]), int(e["r2"]), int(e["p2"]))
+            if e["r1"] != e["r2"] and edge in seen:
+                continue
+            seen.add(edge)
+            out.append(e)
+    return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
 
 
 def _chk(rc, what):
@@ -1079,11 +1131,30 @@ class Team:
              "marginal_covariances_nested")
         return res, diag, cross
 
-    def _gate_call(self, what, cand, T, method, max_block, want_innovation, want_sigma):
+    @staticmethod
+    def _across_check(what, method, max_block):
+        """the arguments a per-record call cannot take with a transport: ValueError before any transport call"""
+        if method not in (None, "schur"):
+            raise ValueError("%s: a team split across participants has the Schur path alone (method=%r with a transport)"
+                             % (what, method))
+        if max_block is not None:
+            raise ValueError("%s: max_block belongs to method=\"nested\", which has no call across teams (it was given a "
+                             "transport)" % what)
+
+    def _across_args(self, what, T, method, max_block, transport, owner_of_robot):
+        """those checks, and the call's T (None: the rounding across)"""
+        self._across_check(what, method, max_block)
+        if T is None:
+            T = self.round(transport=transport, owner_of_robot=owner_of_robot)[1]
+        return T
+
+    def _gate_call(self, what, cand, T, method, max_block, want_innovation, want_sigma, transport=None, owner_of_robot=None):
         if method not in (None, "dense", "schur", "nested"):
             raise ValueError("%s: method must be \"dense\", \"schur\" or \"nested\", not %r" % (what, method))
         N = int(sum(self.agents[i].n for i in self.ids))
-        if T is None:
+        if transport is not None:
+            T = self._across_args(what, T, method, max_block, transport, owner_of_robot)
+        elif T is None:
             T = self.round()[1]
         T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
         if T.size != 12 * N:
@@ -1093,13 +1164,20 @@ class Team:
         res = Covariance()
         xi, d2 = (np.zeros((K, 6)), np.zeros(K)) if want_innovation else (None, None)
         sg = np.zeros((K, 6, 6)) if want_sigma else None
+        outs = (_d(xi) if want_innovation and K else None, _d(d2) if want_innovation and K else None,
+                _d(sg) if want_sigma and K else None)
+        if transport is not None:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_gate_candidates_across(self.h, C.byref(transport.struct), _d(own), _d(T), K, _d(cand), *outs,
+                                                        C.byref(res)), "gate_candidates_across")
+            return res, xi, d2, sg
         code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
-        _chk(lib().dpgo_team_gate_candidates(self.h, _d(T), code, int(max_block or 0), K, _d(cand),
-                                             _d(xi) if want_innovation and K else None, _d(d2) if want_innovation and K else None,
-                                             _d(sg) if want_sigma and K else None, C.byref(res)), "gate_candidates")
+        _chk(lib().dpgo_team_gate_candidates(self.h, _d(T), code, int(max_block or 0), K, _d(cand), *outs, C.byref(res)),
+             "gate_candidates")
         return res, xi, d2, sg
 
-    def gate(self, candidates, T=None, method=None, max_block=None, quantile=0.99, sigma_rel=False):
+    def gate(self, candidates, T=None, method=None, max_block=None, quantile=0.99, sigma_rel=False, transport=None,
+             owner_of_robot=None):
         """Candidate measurements tested against the estimate's own uncertainty.  candidates: MEAS_DTYPE
         records (r1, p1) -> (r2, p2) with R (row-major), t, kappa, tau, T_j ~ T_i (R, t); weight and the flags are ignored: a
         candidate is a fresh measurement that is not in the graph.  T and method as in covariances (T None: the rounding of
@@ -1110,15 +1188,23 @@ class Team:
         with Sigma_meas = diag(I / (2 kappa), I / tau), the cost's own noise model; accept = sqrt(d2) <=
         error_threshold_at_quantile(quantile, 6).  The covariance blocks never leave the device: one kernel behind the
         covariance path forms the outputs.  Raises DpgoError as covariances does, and for a candidate that names a robot or pose
-        outside the team, joins a pose to itself, has kappa <= 0 or tau <= 0, or an R outside SO(3).  Changes no solver state."""
-        res, xi, d2, sg = self._gate_call("gate", candidates, T, method, max_block, True, bool(sigma_rel))
+        outside the team, joins a pose to itself, has kappa <= 0 or tau <= 0, or an R outside SO(3).  Changes no solver state.
+        With a transport (a team split across participants, owner_of_robot as for covariances): the candidates, the same list
+        on every participant, may name any robot of the problem -- a closure between a robot held here and one held elsewhere
+        is the normal case; T is this team's poses (None: the rounding across); method None or "schur" (anything else and a
+        max_block raise ValueError).  The results are complete and identical on every participant, bit for bit those of the
+        single team's method="schur"."""
+        res, xi, d2, sg = self._gate_call("gate", candidates, T, method, max_block, True, bool(sigma_rel), transport, owner_of_robot)
         accept = np.sqrt(d2) <= error_threshold_at_quantile(quantile, 6)
         return (res, xi, d2, accept, sg) if sigma_rel else (res, xi, d2, accept)
 
-    def relative_covariances(self, pairs, T=None, method=None, max_block=None):
+    def relative_covariances(self, pairs, T=None, method=None, max_block=None, transport=None, owner_of_robot=None):
         """sigma_rel[K, 6, 6] of gate for the pose pairs[k] = (i, j), team-order pose indices with i != j: the covariance of
-        the relative pose T_i^-1 T_j.  No measurement is involved; the same bits as gate(..., sigma_rel=True) gives."""
+        the relative pose T_i^-1 T_j.  No measurement is involved; the same bits as gate(..., sigma_rel=True) gives.  With a
+        transport (as in gate): pairs are global pose ids (robots by id, then poses), the same list on every participant."""
         pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        if transport is not None:
+            return self._relative_across(pr, T, method, max_block, transport, owner_of_robot)
         offs = np.cumsum([0] + [self.agents[i].n for i in self.ids])
         N = int(offs[-1])
         if len(pr) and (pr.min() < 0 or pr.max() >= N):
@@ -1130,9 +1216,42 @@ class Team:
             cand[r], cand[p] = ids[k], pr[:, e] - offs[k]
         return self._gate_call("relative_covariances", cand, T, method, max_block, False, True)[3]
 
-    def zero_weight_measurements(self):
+    def _relative_across(self, pr, T, method, max_block, transport, owner_of_robot):
+        self._across_check("relative_covariances", method, max_block)
+        # the robots' sizes from every participant (one allgather of num_robots doubles), then (robot, pose) of every global id
+        own = _owner_array(owner_of_robot)
+        mine = np.zeros(len(own))
+        for i in self.ids:
+            mine[i] = self.agents[i].n
+        sizes = np.asarray(transport.allgather(mine)).reshape(transport.world, len(own))
+        n_of = np.array([int(sizes[int(own[i]), i]) for i in range(len(own))], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(n_of)])
+        if len(pr) and (pr.min() < 0 or pr.max() >= offs[-1]):
+            raise ValueError("relative_covariances: a pair names a pose outside [0, %d)" % offs[-1])
+        cand = np.zeros(len(pr), dtype=MEAS_DTYPE)
+        for e, (r, p) in enumerate((("r1", "p1"), ("r2", "p2"))):
+            k = np.searchsorted(offs, pr[:, e], side="right") - 1
+            cand[r], cand[p] = k, pr[:, e] - offs[k]
+        return self._gate_call("relative_covariances", cand, T, method, max_block, False, True, transport, owner_of_robot)[3]
+
+    def _joined_records(self, recs, transport, owner_of_robot):
+        """the participants' record lists allgathered (lengths first, then the lists padded to the longest) and joined by
+        join_records_by_robot: the same global list on every participant"""
+        x = records_to_doubles(recs)
+        lens = np.asarray(transport.allgather(np.array([float(len(x))]))).reshape(-1).astype(int)
+        L = int(lens.max()) if len(lens) else 0
+        mine = np.zeros(max(L, 1) * _REC_DOUBLES)
+        mine[:x.size] = x.reshape(-1)
+        allr = np.asarray(transport.allgather(mine)).reshape(transport.world, -1)
+        lists = [records_from_doubles(allr[q, :lens[q] * _REC_DOUBLES]) for q in range(transport.world)]
+        return join_records_by_robot(lists, owner_of_robot)
+
+    def zero_weight_measurements(self, transport=None, owner_of_robot=None):
         """the team's measurements whose current weight is 0 (what GNC-TLS has rejected, or set_measurement_weight), in the
-        form gate accepts; each shared edge once, as the lower robot's copy (the rule of round's translation refinement)"""
+        form gate accepts; each shared edge once, as the lower robot's copy (the rule of round's translation refinement).
+        With a transport: those of the whole problem, the same list on every participant (join_records_by_robot)"""
+        if transport is not None:
+            return self._joined_records(self.zero_weight_measurements(), transport, owner_of_robot)
         out = [e for i in self.ids for e in self.agents[i].measurements()
                if e["weight"] == 0.0 and (e["r1"] == e["r2"] or min(int(e["r1"]), int(e["r2"])) == i)]
         return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
@@ -1144,7 +1263,8 @@ class Team:
                if e["r1"] == e["r2"] or min(int(e["r1"]), int(e["r2"])) == i]
         return np.array(out, dtype=MEAS_DTYPE) if out else np.zeros(0, dtype=MEAS_DTYPE)
 
-    def audit(self, measurements=None, T=None, method=None, max_block=None, quantile=0.99, min_redundancy=1e-6, sigma_loo=False):
+    def audit(self, measurements=None, T=None, method=None, max_block=None, quantile=0.99, min_redundancy=1e-6, sigma_loo=False,
+              transport=None, owner_of_robot=None):
         """Measurements that are in the graph tested against the rest of it: leave-one-out gating.
         measurements: MEAS_DTYPE records as in gate, whose weight w >= 0 says at which weight each is in the graph (w = 0: not in
         the Hessian); the flags are ignored and the records are taken on trust.  None: measurements_once(), the team's own
@@ -1162,16 +1282,27 @@ class Team:
             sigma_loo[K, 6, 6]  with sigma_loo=True: the relative covariance of the graph without the edge (zero where the
                           record is not testable).
         At w = 0 this is gate; at w = 1 the normalised-residual test.  Raises DpgoError as gate does, and for a weight that is
-        negative or not finite or a min_redundancy outside (0, 1).  Changes no solver state."""
+        negative or not finite or a min_redundancy outside (0, 1).  Changes no solver state.
+        With a transport (as in gate): the records, the same list on every participant, may name any robot of the problem;
+        None: every participant's measurements_once() allgathered and joined in robot order (join_records_by_robot), which is
+        the single team's measurements_once().  The results are complete and identical on every participant, bit for bit
+        those of the single team's method="schur"."""
         if method not in (None, "dense", "schur", "nested"):
             raise ValueError("audit: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
         N = int(sum(self.agents[i].n for i in self.ids))
-        if T is None:
+        if transport is not None:
+            T = self._across_args("audit", T, method, max_block, transport, owner_of_robot)
+        elif T is None:
             T = self.round()[1]
         T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
         if T.size != 12 * N:
             raise ValueError("audit: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
-        meas = self.measurements_once() if measurements is None else measurements
+        if measurements is not None:
+            meas = measurements
+        elif transport is not None:
+            meas = self._joined_records(self.measurements_once(), transport, owner_of_robot)
+        else:
+            meas = self.measurements_once()
         meas = np.ascontiguousarray(meas, dtype=MEAS_DTYPE).reshape(-1)
         K = len(meas)
         res = Covariance()
@@ -1179,9 +1310,15 @@ class Team:
         sg = np.zeros((K, 6, 6)) if sigma_loo else None
         code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         p = lambda a: _d(a) if K else None
-        _chk(lib().dpgo_team_audit_measurements(self.h, _d(T), code, int(max_block or 0), K, p(meas), C.c_double(min_redundancy),
-                                                p(xi), p(xl), p(d2), p(rho), p(pm), p(sg) if sigma_loo else None, C.byref(res)),
-             "audit_measurements")
+        if transport is not None:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_audit_measurements_across(self.h, C.byref(transport.struct), _d(own), _d(T), K, p(meas),
+                                                           C.c_double(min_redundancy), p(xi), p(xl), p(d2), p(rho), p(pm),
+                                                           p(sg) if sigma_loo else None, C.byref(res)), "audit_measurements_across")
+        else:
+            _chk(lib().dpgo_team_audit_measurements(self.h, _d(T), code, int(max_block or 0), K, p(meas), C.c_double(min_redundancy),
+                                                    p(xi), p(xl), p(d2), p(rho), p(pm), p(sg) if sigma_loo else None, C.byref(res)),
+                 "audit_measurements")
         testable = pm > min_redundancy
         out = dict(measurements=meas, xi=xi, xi_loo=xl, d2=d2, redundancy=rho, pivot_min=pm, testable=testable,
                    accept=testable & (np.sqrt(d2) <= error_threshold_at_quantile(quantile, 6)), covariance=res)

@@ -10,7 +10,8 @@
 //   xi_loo = (A^-1 z) / s,  Sigma_loo = diag(1 / s) sym(A^-1 C) diag(1 / s) = (Sigma_rel^-1 - w W0)^-1
 //   an untestable record, or a non-positive pivot of B, gives d2 = +inf and xi_loo = 0; untestable also Sigma_loo = 0
 // The arithmetic is in audit_block.h.  The blocks are those a covariance path has staged on the device (certify_internal.h,
-// CovStage): k_audit is the step behind them, and only the per-record outputs go to the host.
+// CovStage): k_audit is the step behind them, and only the per-record outputs go to the host.  Across teams
+// (dpgo_team_audit_measurements_across) the same kernel runs on every participant on the compact tables of AcrossStage.
 #include "closure_frame.h"
 #include "audit_block.h"
 
@@ -64,46 +65,75 @@ namespace {
 
 const ClosureCall AUDIT = {"audit_measurements", "record"};
 
-// the step behind a covariance path's staged blocks: upload the records, run k_audit, queue the copies into staging vectors
-struct AuditEpilogue : ClosureEpilogue {
-  std::vector<AuditRec> rec;
+// the device side of the audit behind either kind of staged tables: the records uploaded, k_audit, the copy into a staging vector
+struct AuditWork {
   double min_redundancy = 0.0;
   bool want_sigma = false;
   DevBuf<AuditRec> d_rec;
   DevBuf<double> d_out;  // xi[6 K], xi_loo[6 K], d2[K], rho[K], pmin[K], sigma_loo[36 K] when it is formed
   std::vector<double> h_out;
-  AuditEpilogue() : ClosureEpilogue(2) {}
-  size_t doubles() const { return (size_t)(want_sigma ? 51 : 15) * rec.size(); }
-  int alloc() {
-    const size_t K = rec.size();
-    if (d_rec.alloc(K) || d_out.alloc(doubles())) {
-      set_err("audit_measurements: device allocation failed (" + std::to_string(K * sizeof(AuditRec) + 8 * doubles()) + " bytes for " +
+  size_t doubles(size_t K) const { return (size_t)(want_sigma ? 51 : 15) * K; }
+  int alloc(size_t K, const char *name) {
+    if (d_rec.alloc(K) || d_out.alloc(doubles(K))) {
+      set_err(std::string(name) + ": device allocation failed (" + std::to_string(K * sizeof(AuditRec) + 8 * doubles(K)) + " bytes for " +
               std::to_string(K) + " records)");
       return DPGO_ERR;
     }
-    return ev.create();
+    return DPGO_OK;
   }
-  int run(const CovStage &st) override {
+  // rec: i, j index T and diag, blk indexes pairs (the caller has checked them against the tables)
+  int queue(hipStream_t s, const double *Td, const double *diag, const double *pairs, const std::vector<AuditRec> &rec, const Events &ev) {
     const size_t K = rec.size();
-    for (const AuditRec &c : rec)
-      if (c.i < 0 || c.i >= st.N || c.j < 0 || c.j >= st.N || c.blk < 0 || c.blk >= st.num_pairs) {
-        set_err("audit_measurements: a record lies outside the staged blocks");
-        return DPGO_ERR;
-      }
-    hipStream_t s = st.stream;
     HIPC(hipMemcpyAsync(d_rec.p, rec.data(), sizeof(AuditRec) * K, hipMemcpyHostToDevice, s));
     double *xi = d_out.p, *xl = xi + 6 * K, *d2 = xl + 6 * K, *rho = d2 + K, *pm = rho + K, *sg = want_sigma ? pm + K : nullptr;
     // at most one workgroup per CU of an MI355X: the lanes beyond stride over the rest
     const unsigned grid = (unsigned)std::min<size_t>((K + 255) / 256, 256);
     HIPC(hipEventRecord(ev[0], s));
-    if (want_sigma) k_audit<true><<<grid, 256, 0, s>>>(st.Td, st.diag, st.pairs, d_rec.p, (int)K, min_redundancy, xi, xl, d2, rho, pm, sg);
-    else k_audit<false><<<grid, 256, 0, s>>>(st.Td, st.diag, st.pairs, d_rec.p, (int)K, min_redundancy, xi, xl, d2, rho, pm, sg);
+    if (want_sigma) k_audit<true><<<grid, 256, 0, s>>>(Td, diag, pairs, d_rec.p, (int)K, min_redundancy, xi, xl, d2, rho, pm, sg);
+    else k_audit<false><<<grid, 256, 0, s>>>(Td, diag, pairs, d_rec.p, (int)K, min_redundancy, xi, xl, d2, rho, pm, sg);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[1], s));
-    h_out.resize(doubles());
-    HIPC(hipMemcpyAsync(h_out.data(), d_out.p, sizeof(double) * doubles(), hipMemcpyDeviceToHost, s));
+    h_out.resize(doubles(K));
+    HIPC(hipMemcpyAsync(h_out.data(), d_out.p, sizeof(double) * doubles(K), hipMemcpyDeviceToHost, s));
+    return DPGO_OK;
+  }
+  void copy_out(size_t K, double *xi, double *xi_loo, double *d2, double *rho, double *pmin, double *sigma_loo) const {
+    const double *h = h_out.data();
+    std::memcpy(xi, h, sizeof(double) * 6 * K);
+    std::memcpy(xi_loo, h + 6 * K, sizeof(double) * 6 * K);
+    std::memcpy(d2, h + 12 * K, sizeof(double) * K);
+    std::memcpy(rho, h + 13 * K, sizeof(double) * K);
+    std::memcpy(pmin, h + 14 * K, sizeof(double) * K);
+    if (sigma_loo) std::memcpy(sigma_loo, h + 15 * K, sizeof(double) * 36 * K);
+  }
+};
+
+// the step behind a covariance path's staged blocks
+struct AuditEpilogue : ClosureEpilogue, AuditWork {
+  std::vector<AuditRec> rec;
+  AuditEpilogue() : ClosureEpilogue(2) {}
+  int alloc() { return AuditWork::alloc(rec.size(), "audit_measurements") ? DPGO_ERR : ev.create(); }
+  int run(const CovStage &st) override {
+    for (const AuditRec &c : rec)
+      if (c.i < 0 || c.i >= st.N || c.j < 0 || c.j >= st.N || c.blk < 0 || c.blk >= st.num_pairs) {
+        set_err("audit_measurements: a record lies outside the staged blocks");
+        return DPGO_ERR;
+      }
+    if (queue(st.stream, st.Td, st.diag, st.pairs, rec, ev)) return DPGO_ERR;
     ran = true;
     return DPGO_OK;
+  }
+};
+
+const ClosureCall AUDIT_ACROSS = {"audit_measurements_across", "record"};
+
+// the same step behind the compact tables of the path across teams: every participant runs all K records
+struct AuditAcross : RecordsAcross<AuditRec>, AuditWork {
+  AuditAcross() : RecordsAcross<AuditRec>(&AUDIT_ACROSS, &AuditRec::blk) {}
+  int run(const AcrossStage &st) override {
+    if (!inside(st)) { set_err("a record lies outside the staged blocks"); return DPGO_ERR; }
+    if (AuditWork::alloc(rec.size(), "audit_measurements_across") || ev.create()) return DPGO_ERR;
+    return queue(st.stream, st.Td, st.diag, st.pairs, rec, ev);
   }
 };
 
@@ -151,13 +181,65 @@ extern "C" int dpgo_team_audit_measurements(dpgo_team_t *t, const double *T, int
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr, "audit_measurements: %d records on %d pair blocks, audit kernel %.3f ms\n", num, np, epi.ev.ms());
-  const size_t K = (size_t)num;
-  const double *h = epi.h_out.data();
-  std::memcpy(xi, h, sizeof(double) * 6 * K);
-  std::memcpy(xi_loo, h + 6 * K, sizeof(double) * 6 * K);
-  std::memcpy(d2, h + 12 * K, sizeof(double) * K);
-  std::memcpy(rho, h + 13 * K, sizeof(double) * K);
-  std::memcpy(pmin, h + 14 * K, sizeof(double) * K);
-  if (sigma_loo) std::memcpy(sigma_loo, h + 15 * K, sizeof(double) * 36 * K);
+  epi.copy_out((size_t)num, xi, xi_loo, d2, rho, pmin, sigma_loo);
+  return DPGO_OK;
+}
+
+extern "C" int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
+                                                   const double *T, int num, const dpgo_measurement_t *meas, double min_redundancy,
+                                                   double *xi, double *xi_loo, double *d2, double *rho, double *pmin, double *sigma_loo,
+                                                   dpgo_covariance_t *res) {
+  const ClosureCall &A = AUDIT_ACROSS;
+  if (res) std::memset(res, 0, sizeof *res);
+  AuditAcross epi;
+  epi.op = 5;
+  epi.min_redundancy = min_redundancy;
+  epi.want_sigma = sigma_loo != nullptr;
+  // ---- the refusals of the audit itself, in the single team's order and words: decided here, told to everyone by the
+  // agreement record (a participant that returned now would leave the others waiting)
+  auto refusal = [&]() -> int {
+    if (!T || !res || !xi || !xi_loo || !d2 || !rho || !pmin) return A.refuse("null argument");
+    if (num <= 0) return A.refuse("num must be positive, not " + std::to_string(num));
+    if (!meas) return A.refuse("null argument");
+    if (!(min_redundancy > 0.0 && min_redundancy < 1.0)) {
+      char buf[120];
+      std::snprintf(buf, sizeof buf, "min_redundancy must lie in (0, 1), not %.6g", min_redundancy);
+      return A.refuse(buf);
+    }
+    for (int k = 0; k < num; ++k) {
+      const dpgo_measurement_t &m = meas[k];
+      if (m.r1 == m.r2 && m.p1 == m.p2) return A.refuse(A.item(k) + " joins a pose to itself");
+      if (A.check(k, m, true)) return DPGO_ERR;
+    }
+    return DPGO_OK;
+  };
+  if (refusal()) epi.argerr = A.refused();
+  else {
+    epi.meas = meas;
+    epi.rec.resize(num);
+    RecordHash h;
+    h.add(epi.want_sigma ? 1 : 0);
+    h.add(min_redundancy);
+    for (int k = 0; k < num; ++k) {
+      const dpgo_measurement_t &m = meas[k];
+      AuditRec &c = epi.rec[k];
+      std::memset(&c, 0, sizeof c);
+      pack_measurement(m, c.m);
+      c.m[14] = m.weight;
+      h.add(m.r1); h.add(m.p1); h.add(m.r2); h.add(m.p2);
+      h.add(c.m, sizeof(double) * 15);
+    }
+    epi.num = num;
+    epi.hash = h.value();
+  }
+  if (const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, T, DPGO_COV_SCHUR, 0, nullptr, nullptr, nullptr, res, &epi)) {
+    if (res) std::memset(res, 0, sizeof *res);
+    return rc;
+  }
+  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+  if (timing)
+    std::fprintf(stderr, "audit_measurements_across: %d records on %zu pair blocks and %zu endpoints, audit kernel %.3f ms\n", num,
+                 epi.pairs.size() / 2, epi.endpoints.size(), epi.ev.ms());
+  epi.copy_out((size_t)num, xi, xi_loo, d2, rho, pmin, sigma_loo);
   return DPGO_OK;
 }

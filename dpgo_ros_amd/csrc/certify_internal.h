@@ -203,8 +203,36 @@ int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out);
 // fail[1] the team pose of the pivot, fail[2] its row in that factor
 int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
                             dpgo_covariance_t *res, int *fail, CovEpilogue *epi = nullptr);
-// the same over a split team (dpgo_team_marginal_covariances_across; covariance_schur.hip)
+// What the path across teams has on the device of EVERY participant once allgather D has run ("across teams"):
+// compact tables over the E sorted distinct endpoint poses of the records and the P listed pairs -- T (12 per endpoint, the
+// iterate layout), the E diagonal blocks and the P pair blocks (36 doubles each, row-major), all ordered on `stream`.  An index
+// into them takes the place of the team pose of CovStage: the kernels behind a single team's blocks run on them unchanged.
+struct AcrossStage {
+  const double *Td, *diag, *pairs;
+  int E, P;
+  hipStream_t stream;
+};
+// The step behind the blocks of covariance_schur_across (gate.hip, audit.hip), in the spirit of CovEpilogue.  The call fills
+// name, op, num, hash and argerr before the path starts: the path hands them to Across::begin (op 4, 5; the two real fields
+// carry num and hash), so that a record list that differs on one participant is refused everywhere.  resolve() runs behind
+// begin, when the global numbering is known: it fills `pairs` (global pose ids, two per pair) and `endpoints` (sorted,
+// distinct), or refuses in words that are the same on every participant.  run() queues its uploads, its kernel and the copies
+// of its per-record outputs on stage.stream and does not synchronise; the path drains the stream and closes the protocol.
+struct AcrossEpilogue {
+  const char *name = "";
+  int op = 0;
+  double num = 0.0, hash = 0.0;
+  std::string argerr;  // this participant's own refusal (the others learn of it from the agreement record)
+  std::vector<int> pairs, endpoints;
+  virtual int resolve(const Across &x, std::string &msg) = 0;
+  virtual int run(const AcrossStage &stage) = 0;
+  virtual ~AcrossEpilogue() = default;
+};
+
+// the same over a split team (dpgo_team_marginal_covariances_across; covariance_schur.hip).  epi: the step behind the blocks
+// (num_pairs and pairs are then epi's; cov_diag and cov_pairs are not touched and may be null, only res is filled)
 int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
-                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res);
+                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res,
+                            AcrossEpilogue *epi = nullptr);
 
 }  // namespace dpgo_cert

@@ -83,6 +83,21 @@ struct ClosureCall {
     return DPGO_OK;
   }
 
+  // across teams: the GLOBAL pose (robots by id, then poses) of (robot r, pose p) of record k, or DPGO_ERR with the refusal in
+  // msg -- the same words on every participant, which all hold the same records and the same numbering
+  int global_endpoint(const Across &x, int k, int r, int p, int *g, std::string &msg) const {
+    if (r < 0 || r >= x.num_robots) {
+      msg = item(k) + " names robot " + std::to_string(r) + ", outside the problem's [0, " + std::to_string(x.num_robots) + ")";
+      return DPGO_ERR;
+    }
+    if (p < 0 || p >= x.robot_n[r]) {
+      msg = item(k) + " names pose " + std::to_string(p) + " of robot " + std::to_string(r) + ", outside [0, " + std::to_string(x.robot_n[r]) + ")";
+      return DPGO_ERR;
+    }
+    *g = (int)(x.robot_goff[r] + p);
+    return DPGO_OK;
+  }
+
   // the fields of record k: kappa and tau positive, with_weight: the weight finite and not negative, and (R~, t~) in SE(3) by
   // the rule of T (covariance_host_checks; R~ is row-major here, which changes neither figure)
   int check(int k, const dpgo_measurement_t &m, bool with_weight = false) const {
@@ -111,6 +126,12 @@ struct ClosureCall {
       return refuse(buf);
     }
     return DPGO_OK;
+  }
+
+  // the words of the refusal just made (refuse, check) without the call's name: what travels as argerr across teams
+  std::string refused() const {
+    const std::string p = std::string(name) + ": ", e = g_err;
+    return e.rfind(p, 0) == 0 ? e.substr(p.size()) : e;
   }
 
   // free bytes of the team's device for the call's budget (cov_device_avail), or a refusal
@@ -173,5 +194,59 @@ inline std::vector<int> rank_endpoints(std::vector<GateRec> &recs) {
   }
   return poses;
 }
+
+// ---- across teams (the gate and the audit)
+
+// FNV-1a over the bytes of what every participant must pass alike, as a double that an allgather carries exactly
+struct RecordHash {
+  unsigned long long h = 1469598103934665603ull;
+  void add(const void *p, size_t bytes) {
+    const unsigned char *b = (const unsigned char *)p;
+    for (size_t k = 0; k < bytes; ++k) { h ^= b[k]; h *= 1099511628211ull; }
+  }
+  void add(int v) { add(&v, sizeof v); }
+  void add(double v) { add(&v, sizeof v); }
+  double value() const { return (double)(h & ((1ull << 52) - 1)); }
+};
+
+// The frame of a per-record call over a split team: the records as the caller passed them, their device form (Rec: GateRec
+// or AuditRec, whose words i, j and *blk the kernel reads as indices into the staged tables), and the hook's resolve().  The
+// records' endpoints become global poses, the pair list is FirstUsePairs over them (the single team's rule), and i, j are
+// rewritten to the ranks of the two poses among the sorted distinct endpoints: the compact tables of AcrossStage.
+template <class Rec>
+struct RecordsAcross : AcrossEpilogue {
+  const ClosureCall *call;
+  int Rec::*blk;
+  const dpgo_measurement_t *meas = nullptr;
+  std::vector<Rec> rec;
+  Events ev;
+  RecordsAcross(const ClosureCall *c, int Rec::*b) : call(c), blk(b), ev(2) { name = c->name; }
+
+  int resolve(const Across &x, std::string &msg) override {
+    FirstUsePairs fp;
+    for (size_t k = 0; k < rec.size(); ++k) {
+      const dpgo_measurement_t &m = meas[k];
+      int g[2];
+      if (call->global_endpoint(x, (int)k, m.r1, m.p1, &g[0], msg) || call->global_endpoint(x, (int)k, m.r2, m.p2, &g[1], msg)) return DPGO_ERR;
+      rec[k].i = g[0]; rec[k].j = g[1];
+      rec[k].*blk = fp.block(g[0], g[1]);
+      endpoints.push_back(g[0]); endpoints.push_back(g[1]);
+    }
+    pairs = fp.pairs;
+    std::sort(endpoints.begin(), endpoints.end());
+    endpoints.erase(std::unique(endpoints.begin(), endpoints.end()), endpoints.end());
+    for (Rec &c : rec) {
+      c.i = (int)(std::lower_bound(endpoints.begin(), endpoints.end(), c.i) - endpoints.begin());
+      c.j = (int)(std::lower_bound(endpoints.begin(), endpoints.end(), c.j) - endpoints.begin());
+    }
+    return DPGO_OK;
+  }
+  // every index of every record inside the stage's tables (checked before the launch: the kernel does not)
+  bool inside(const AcrossStage &st) const {
+    for (const Rec &c : rec)
+      if (c.i < 0 || c.i >= st.E || c.j < 0 || c.j >= st.E || c.*blk < 0 || c.*blk >= st.P) return false;
+    return true;
+  }
+};
 
 }  // namespace dpgo_cert

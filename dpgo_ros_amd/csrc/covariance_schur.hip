@@ -426,6 +426,9 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
 //   C  the pair blocks a participant owns (two interior poses of one of its robots; an interior pose of one of its robots
 //      with a public pose) and, for every pair of interior poses of two robots, the two rows W_a[i,:], W_b[j,:] from their
 //      holders;
+// with an AcrossEpilogue (the gate and the audit across teams) also
+//   D  per endpoint of the epilogue's records, sorted by global pose: T and the diagonal block from the pose's holder, zeros
+//      from everyone else -- every participant then runs the epilogue's kernel on compact tables of endpoints and pairs;
 // and the closing status word.  Every participant builds the same S_c from B, inverts it itself (deterministic: no
 // broadcast) and forms the pairs of two robots itself from the rows of C.  No sum crosses a robot boundary except the
 // host's log det in robot order, so every block, log det and pivot is bitwise the single team's.
@@ -446,11 +449,12 @@ enum { XF_OK = 0, XF_PIVOT = 1, XF_MEMORY = 2, XF_LOCAL = 3 };
 }  // namespace
 
 int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
-                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res) {
-  const char *what = "marginal_covariances_across";
+                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, AcrossEpilogue *epi) {
+  const char *what = epi ? epi->name : "marginal_covariances_across";
   if (res) std::memset(res, 0, sizeof *res);
   std::string argerr;
-  if (!T || !cov_diag || !res || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))) argerr = "null argument";
+  if (epi && !epi->argerr.empty()) argerr = epi->argerr;
+  else if (!T || !res || (!epi && (!cov_diag || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))))) argerr = "null argument";
   else if (flags != DPGO_COV_SCHUR) argerr = "flags must be DPGO_COV_SCHUR";
   else if (t) {
     int n = 0;
@@ -464,12 +468,22 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     }
   }
   Across x;
-  if (x.begin(t, tr, owner, what, 3, 3, flags, (double)num_pairs, argerr.empty() ? pair_hash(pairs, num_pairs) : 0.0, 0,
-              argerr.empty() ? nullptr : argerr.c_str()))
+  const double agree_num = epi ? epi->num : (double)num_pairs;
+  const double agree_hash = !argerr.empty() ? 0.0 : epi ? epi->hash : pair_hash(pairs, num_pairs);
+  if (x.begin(t, tr, owner, what, epi ? epi->op : 3, 3, flags, agree_num, agree_hash, 0, argerr.empty() ? nullptr : argerr.c_str())) {
+    // (a participant whose own records were refused says why in the words of the single team's call)
+    if (epi && !epi->argerr.empty()) set_err(std::string(what) + ": " + epi->argerr);
     return DPGO_ERR;
+  }
   // (from here on the participants agree on the owner table, the robots' sizes and the pair list)
   const int nr = x.num_robots, na = (int)t->ag.size(), world = x.world;
   const long long NG = x.nglob;
+  if (epi) {  // the records' endpoints in the global numbering: a refusal is the same on every participant
+    std::string msg;
+    if (epi->resolve(x, msg)) { set_err(std::string(what) + ": " + msg); return DPGO_ERR; }
+    pairs = epi->pairs.data();
+    num_pairs = (int)(epi->pairs.size() / 2);
+  }
   for (int k = 0; k < 2 * num_pairs; ++k)
     if (pairs[k] < 0 || pairs[k] >= NG) {  // (the same on every participant: nobody goes on)
       set_err(std::string(what) + ": pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " +
@@ -486,7 +500,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     schur_partition(t, z, P);
   }
   const int N = P.N;
-  if (NG < 2) {
+  if (NG < 2 && !epi) {  // (with an epilogue never: a record joins two different poses of the problem)
     std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
     if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
     return x.finish() ? DPGO_ERR : DPGO_OK;
@@ -906,6 +920,40 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     return DPGO_OK;
   };
   if (!x.bad && phase3()) x.fail_local(g_err);
+  // ---- the step behind the blocks (the gate, the audit).  Allgather D: per endpoint of the records, sorted by global pose,
+  // 12 doubles of T and the 36 of its diagonal block from the participant that holds it, zeros from everyone else (pose 0's
+  // block is zero with its holder too).  Then every participant holds the compact tables and runs all records itself.
+  DevBuf<double> d_tab;
+  auto phase4 = [&](const std::vector<double> &tab, int E) -> int {
+    if (d_tab.alloc(tab.size())) { set_err("device allocation failed"); return DPGO_ERR; }
+    HIPC(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
+    const AcrossStage st{d_tab.p, d_tab.p + (size_t)12 * E, d_tab.p + (size_t)48 * E, E, num_pairs, s};
+    if (epi->run(st)) return DPGO_ERR;
+    HIPC(hipStreamSynchronize(s));
+    return DPGO_OK;
+  };
+  if (epi) {
+    const int E = (int)epi->endpoints.size();
+    std::vector<double> gd(1 + 48 * (size_t)E, 0.0);
+    if (!x.bad)
+      for (int e = 0; e < E; ++e) {
+        const int g = epi->endpoints[e];
+        if (!here(g)) continue;
+        const int lp = local_pose(g);
+        std::memcpy(gd.data() + 1 + 48 * (size_t)e, T + (size_t)12 * lp, sizeof(double) * 12);
+        std::memcpy(gd.data() + 1 + 48 * (size_t)e + 12, hout.data() + (size_t)36 * lp, sizeof(double) * 36);
+      }
+    if (x.gather(gd, gall)) return x.fail();
+    // T of the E endpoints, their diagonal blocks, the pair blocks
+    std::vector<double> tab((size_t)48 * E + (size_t)36 * num_pairs);
+    for (int e = 0; e < E; ++e) {
+      const double *q = gall.data() + (size_t)x.robot_holder[grobot[epi->endpoints[e]]] * gd.size() + 1 + 48 * (size_t)e;
+      std::memcpy(tab.data() + (size_t)12 * e, q, sizeof(double) * 12);
+      std::memcpy(tab.data() + (size_t)12 * E + (size_t)36 * e, q + 12, sizeof(double) * 36);
+    }
+    std::memcpy(tab.data() + (size_t)48 * E, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
+    if (phase4(tab, E)) x.fail_local(g_err);
+  }
   if (x.finish()) return DPGO_ERR;
   // ---- the results: log det and pivots in robot order, the separator last
   std::vector<char> counted(nr + 1, 0);
@@ -919,9 +967,10 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr,
-                 "marginal_covariances_across: rank %d of %d, n %lld, separator %d, largest interior here %d, assemble %.3f ms, factorisations "
+                 "%s: rank %d of %d, n %lld, separator %d, largest interior here %d, assemble %.3f ms, factorisations "
                  "%.3f ms, products %.3f ms, separator inverse %.3f ms, extract %.3f ms, %lld allgathers, %lld exchanges\n",
-                 x.rank, world, 6 * (NG - 1), nS, 6 * P.max_int, ms[0], ms[1], ms[2], ms[3], ms[4], x.n_allgather, x.n_exchange);
+                 what, x.rank, world, 6 * (NG - 1), nS, 6 * P.max_int, ms[0], ms[1], ms[2], ms[3], ms[4], x.n_allgather, x.n_exchange);
+  if (epi) return DPGO_OK;  // (the blocks stay here: the epilogue's outputs are the call's)
   std::memcpy(cov_diag, hout.data(), sizeof(double) * 36 * (size_t)N);
   if (num_pairs > 0) std::memcpy(cov_pairs, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
   return DPGO_OK;

@@ -9,7 +9,9 @@
 //   noise           Sigma_meas = diag(I / (2 kappa), I / tau): the inverse Hessian of the candidate's own term of the cost
 //   distance        d^2 = xi^T (Sigma_rel + Sigma_meas)^-1 xi by a 6 x 6 Cholesky; a non-positive pivot gives +inf
 // The blocks S_ii, S_jj, S_ij are those a covariance path has staged on the device (certify_internal.h, CovStage): k_gate is
-// the step behind them, and only xi, d^2 and the requested Sigma_rel go to the host.
+// the step behind them, and only xi, d^2 and the requested Sigma_rel go to the host.  Across teams (dpgo_team_gate_candidates_across)
+// the same kernel runs on every participant behind covariance_schur_across, on compact tables of the records' endpoints
+// (AcrossStage): i, j and the block word index those instead of the team's arrays.
 #include "closure_frame.h"
 
 namespace dpgo {
@@ -56,39 +58,31 @@ namespace {
 
 const ClosureCall GATE = {"gate_candidates", "candidate"};
 
-// the step behind a covariance path's staged blocks: upload the records, run k_gate, queue the copies of what was asked for
-struct GateEpilogue : ClosureEpilogue {
-  std::vector<GateRec> cand;  // w0: the staged pair block that holds S_ij
+// the device side of the gate behind either kind of staged tables: the records uploaded, k_gate, the copies of what was asked for
+struct GateWork {
   bool innov = false, want_sigma = false;
   DevBuf<GateRec> d_cand;
   DevBuf<double> d_out;  // xi[6 K], d2[K], sigma_rel[36 K], whichever are formed
   std::vector<double> h_xi, h_d2, h_sigma;
-  GateEpilogue() : ClosureEpilogue(2) {}
-  int alloc() {
-    const size_t K = cand.size();
+  int alloc(size_t K, const char *name) {
     if (d_cand.alloc(K) || d_out.alloc((innov ? 7 * K : 0) + (want_sigma ? 36 * K : 0))) {
-      set_err("gate_candidates: device allocation failed (" + std::to_string(K * (128 + (innov ? 56 : 0) + (want_sigma ? 288 : 0))) +
+      set_err(std::string(name) + ": device allocation failed (" + std::to_string(K * (128 + (innov ? 56 : 0) + (want_sigma ? 288 : 0))) +
               " bytes for " + std::to_string(K) + " candidates)");
       return DPGO_ERR;
     }
-    return ev.create();
+    return DPGO_OK;
   }
-  int run(const CovStage &st) override {
+  // cand: i, j index T and diag, w0 indexes pairs (the caller has checked them against the tables)
+  int queue(hipStream_t s, const double *Td, const double *diag, const double *pairs, const std::vector<GateRec> &cand, const Events &ev) {
     const size_t K = cand.size();
-    for (const GateRec &c : cand)
-      if (c.i < 0 || c.i >= st.N || c.j < 0 || c.j >= st.N || c.w0 < 0 || c.w0 >= st.num_pairs) {
-        set_err("gate_candidates: a candidate lies outside the staged blocks");
-        return DPGO_ERR;
-      }
-    hipStream_t s = st.stream;
     HIPC(hipMemcpyAsync(d_cand.p, cand.data(), sizeof(GateRec) * K, hipMemcpyHostToDevice, s));
     double *xi = innov ? d_out.p : nullptr, *d2 = innov ? d_out.p + 6 * K : nullptr;
     double *sg = want_sigma ? d_out.p + (innov ? 7 * K : 0) : nullptr;
     // at most one workgroup per CU of an MI355X: the lanes beyond stride over the rest
     const unsigned grid = (unsigned)std::min<size_t>((K + 255) / 256, 256);
     HIPC(hipEventRecord(ev[0], s));
-    if (innov) k_gate<true><<<grid, 256, 0, s>>>(st.Td, st.diag, st.pairs, d_cand.p, (int)K, xi, d2, sg);
-    else k_gate<false><<<grid, 256, 0, s>>>(st.Td, st.diag, st.pairs, d_cand.p, (int)K, xi, d2, sg);
+    if (innov) k_gate<true><<<grid, 256, 0, s>>>(Td, diag, pairs, d_cand.p, (int)K, xi, d2, sg);
+    else k_gate<false><<<grid, 256, 0, s>>>(Td, diag, pairs, d_cand.p, (int)K, xi, d2, sg);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[1], s));
     if (innov) {
@@ -100,8 +94,41 @@ struct GateEpilogue : ClosureEpilogue {
       h_sigma.resize(36 * K);
       HIPC(hipMemcpyAsync(h_sigma.data(), sg, sizeof(double) * 36 * K, hipMemcpyDeviceToHost, s));
     }
+    return DPGO_OK;
+  }
+  void copy_out(size_t K, double *xi, double *d2, double *sigma_rel) const {
+    if (xi) std::memcpy(xi, h_xi.data(), sizeof(double) * 6 * K);
+    if (d2) std::memcpy(d2, h_d2.data(), sizeof(double) * K);
+    if (sigma_rel) std::memcpy(sigma_rel, h_sigma.data(), sizeof(double) * 36 * K);
+  }
+};
+
+// the step behind a covariance path's staged blocks
+struct GateEpilogue : ClosureEpilogue, GateWork {
+  std::vector<GateRec> cand;  // w0: the staged pair block that holds S_ij
+  GateEpilogue() : ClosureEpilogue(2) {}
+  int alloc() { return GateWork::alloc(cand.size(), "gate_candidates") ? DPGO_ERR : ev.create(); }
+  int run(const CovStage &st) override {
+    for (const GateRec &c : cand)
+      if (c.i < 0 || c.i >= st.N || c.j < 0 || c.j >= st.N || c.w0 < 0 || c.w0 >= st.num_pairs) {
+        set_err("gate_candidates: a candidate lies outside the staged blocks");
+        return DPGO_ERR;
+      }
+    if (queue(st.stream, st.Td, st.diag, st.pairs, cand, ev)) return DPGO_ERR;
     ran = true;
     return DPGO_OK;
+  }
+};
+
+const ClosureCall GATE_ACROSS = {"gate_candidates_across", "candidate"};
+
+// the same step behind the compact tables of the path across teams: every participant runs all K records
+struct GateAcross : RecordsAcross<GateRec>, GateWork {
+  GateAcross() : RecordsAcross<GateRec>(&GATE_ACROSS, &GateRec::w0) {}
+  int run(const AcrossStage &st) override {
+    if (!inside(st)) { set_err("a candidate lies outside the staged blocks"); return DPGO_ERR; }
+    if (GateWork::alloc(rec.size(), "gate_candidates_across") || ev.create()) return DPGO_ERR;
+    return queue(st.stream, st.Td, st.diag, st.pairs, rec, ev);
   }
 };
 
@@ -147,9 +174,60 @@ extern "C" int dpgo_team_gate_candidates(dpgo_team_t *t, const double *T, int me
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr, "gate_candidates: %d candidates on %d pair blocks, gate kernel %.3f ms\n", num, np, epi.ev.ms());
-  const size_t K = (size_t)num;
-  if (xi) std::memcpy(xi, epi.h_xi.data(), sizeof(double) * 6 * K);
-  if (d2) std::memcpy(d2, epi.h_d2.data(), sizeof(double) * K);
-  if (sigma_rel) std::memcpy(sigma_rel, epi.h_sigma.data(), sizeof(double) * 36 * K);
+  epi.copy_out((size_t)num, xi, d2, sigma_rel);
+  return DPGO_OK;
+}
+
+extern "C" int dpgo_team_gate_candidates_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, const double *T,
+                                                int num, const dpgo_measurement_t *cand, double *xi, double *d2, double *sigma_rel,
+                                                dpgo_covariance_t *res) {
+  const ClosureCall &G = GATE_ACROSS;
+  if (res) std::memset(res, 0, sizeof *res);
+  GateAcross epi;
+  epi.op = 4;
+  epi.innov = xi != nullptr;
+  epi.want_sigma = sigma_rel != nullptr;
+  // ---- the refusals of the gate itself, in the single team's order and words: decided here, told to everyone by the
+  // agreement record (a participant that returned now would leave the others waiting)
+  auto refusal = [&]() -> int {
+    if (!T || !res) return G.refuse("null argument");
+    if (num <= 0) return G.refuse("num must be positive, not " + std::to_string(num));
+    if (!cand) return G.refuse("null argument");
+    if (!xi && !d2 && !sigma_rel) return G.refuse("no output requested (xi, d2 and sigma_rel are all null)");
+    if ((xi == nullptr) != (d2 == nullptr)) return G.refuse("xi and d2 come together: exactly one of them is null");
+    for (int k = 0; k < num; ++k) {
+      const dpgo_measurement_t &m = cand[k];
+      if (m.r1 == m.r2 && m.p1 == m.p2) return G.refuse(G.item(k) + " joins a pose to itself");
+      if (epi.innov && G.check(k, m)) return DPGO_ERR;
+    }
+    return DPGO_OK;
+  };
+  if (refusal()) epi.argerr = G.refused();
+  else {
+    epi.meas = cand;
+    epi.rec.resize(num);
+    RecordHash h;
+    h.add((epi.innov ? 1 : 0) | (epi.want_sigma ? 2 : 0));
+    for (int k = 0; k < num; ++k) {
+      const dpgo_measurement_t &m = cand[k];
+      GateRec &c = epi.rec[k];
+      std::memset(&c, 0, sizeof c);
+      h.add(m.r1); h.add(m.p1); h.add(m.r2); h.add(m.p2);
+      if (!epi.innov) continue;  // (the relative covariance alone: the measurement fields are not read)
+      pack_measurement(m, c.m);
+      h.add(c.m, sizeof c.m);
+    }
+    epi.num = num;
+    epi.hash = h.value();
+  }
+  if (const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, T, DPGO_COV_SCHUR, 0, nullptr, nullptr, nullptr, res, &epi)) {
+    if (res) std::memset(res, 0, sizeof *res);
+    return rc;
+  }
+  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+  if (timing)
+    std::fprintf(stderr, "gate_candidates_across: %d candidates on %zu pair blocks and %zu endpoints, gate kernel %.3f ms\n", num,
+                 epi.pairs.size() / 2, epi.endpoints.size(), epi.ev.ms());
+  epi.copy_out((size_t)num, xi, d2, sigma_rel);
   return DPGO_OK;
 }

@@ -660,3 +660,38 @@ def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8,
         dg = np.concatenate([dblocks[i] for i in sorted(dblocks)]).reshape(-1, 6, 6)
         out["covariances"] = (cres, dg) if pairs is None else (cres, dg, cross)
     return out
+
+
+def _participants(backend_or_team, dist, owner_of_robot):
+    """the conventions of certify_and_round: (team, transport over the ranks that own a robot, owner table in the transport's
+    ranks), or None on a rank that owns none (the sub-group's creation is collective: every rank of the world calls)"""
+    owners = sorted(set(int(o) for o in owner_of_robot))
+    group = None
+    if dist.get_world_size() != len(owners):
+        group = dist.new_group(owners)
+    if dist.get_rank() not in owners:
+        return None
+    own = np.array([owners.index(int(o)) for o in owner_of_robot], dtype=np.int32)
+    return getattr(backend_or_team, "team", backend_or_team), TorchTransport(dist, group), own
+
+
+def gate_candidates(backend_or_team, dist, owner_of_robot, candidates, **kw):
+    """Team.gate of an estimate split across ranks (one team per rank): the candidates, the same list on every rank, may join
+    robots held by different ranks.  kw: T (this rank's poses; None: the rounding across), quantile, sigma_rel.  The result of
+    Team.gate, complete and identical on every rank that owns a robot; None on a rank that owns none."""
+    p = _participants(backend_or_team, dist, owner_of_robot)
+    if p is None:
+        return None
+    team, tr, own = p
+    return team.gate(candidates, transport=tr, owner_of_robot=own, **kw)
+
+
+def audit(backend_or_team, dist, owner_of_robot, measurements=None, **kw):
+    """Team.audit of an estimate split across ranks: measurements None audits every measurement of the problem once (the
+    ranks' own lists allgathered and joined in robot order).  kw: T, quantile, min_redundancy, sigma_loo.  The dict of
+    Team.audit, complete and identical on every rank that owns a robot; None on a rank that owns none."""
+    p = _participants(backend_or_team, dist, owner_of_robot)
+    if p is None:
+        return None
+    team, tr, own = p
+    return team.audit(measurements, transport=tr, owner_of_robot=own, **kw)

@@ -423,7 +423,7 @@ int dpgo_team_marginal_covariances_nested(dpgo_team_t *t, const double *T, int m
  * robot or pose of the team; i == j; and, when xi / d2 are requested, kappa <= 0 or tau <= 0, or R~ outside SO(3) by the
  * 1e-8 rule of T.  Every refusal of the chosen covariance path carries over with its own message (T outside SE(3), a
  * disconnected weighted graph, too little device memory, a non-positive pivot); the outputs are then untouched and *res all
- * zero.  *res: the path's own record.  Changes no solver state.  There is no call across teams. */
+ * zero.  *res: the path's own record.  Changes no solver state.  Across teams: dpgo_team_gate_candidates_across below. */
 enum { DPGO_GATE_DENSE = 0, DPGO_GATE_SCHUR = 1, DPGO_GATE_NESTED = 2 };
 int dpgo_team_gate_candidates(dpgo_team_t *t, const double *T, int method, int max_block /* NESTED only */,
                               int num, const dpgo_measurement_t *cand,
@@ -461,7 +461,7 @@ int dpgo_team_gate_candidates(dpgo_team_t *t, const double *T, int method, int m
  * (0, 1); an endpoint that is not a robot or pose of the team; i == j; kappa <= 0 or tau <= 0; a non-finite value; a weight that
  * is negative or not finite; R~ outside SO(3) by the 1e-8 rule of T.  Every refusal of the chosen covariance path carries over
  * with its own message; the outputs are then untouched and *res all zero.  *res: the path's own record.  Changes no solver
- * state.  There is no call across teams. */
+ * state.  Across teams: dpgo_team_audit_measurements_across below. */
 int dpgo_team_audit_measurements(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */,
                                  int num, const dpgo_measurement_t *meas, double min_redundancy,
                                  double *xi /* 6 num */, double *xi_loo /* 6 num */, double *d2 /* num */,
@@ -709,6 +709,33 @@ int dpgo_team_round_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int
 int dpgo_team_marginal_covariances_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
                                           const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
                                           double *cov_pairs, dpgo_covariance_t *res);
+/* dpgo_team_gate_candidates and dpgo_team_audit_measurements over a split team (csrc/gate.hip, csrc/audit.hip; DESIGN.md 5f,
+ * 5h, "across teams"): the step behind dpgo_team_marginal_covariances_across, whose Schur path is the only method.  T: this
+ * team's poses in team order.  The records are the same on every participant and their (r1, p1) -> (r2, p2) may name any
+ * robot of the problem: a closure between a robot held here and one held elsewhere is the normal case.  All num outputs are
+ * complete and identical on every participant, and every bit equals the single team's DPGO_GATE_SCHUR call on the same T and
+ * records, whatever the split.  The agreement record carries num and a hash of the records' endpoint ids and their 14 (the
+ * audit: 15, with the weight) doubles, of the outputs requested and of min_redundancy: a list that differs on one
+ * participant is refused everywhere ("the number of records", "the record list").  The path is asked for the records' pairs
+ * of GLOBAL poses, each ordered pair once in order of first use.  Behind its three allgathers comes a fourth, D: per endpoint
+ * of the records, sorted by global pose, the 12 doubles of T and the 36 of Sigma_ii from the participant that holds it, zeros
+ * from everyone else.  Every participant then holds compact tables (endpoint poses, their diagonal blocks, the pair blocks),
+ * runs the single team's kernel on all num records itself, and copies back the per-record outputs: nothing is broadcast.
+ * Exactly one allgather more than dpgo_team_marginal_covariances_across with the same pairs.
+ * The refusals of the single-team call keep their words (NULL arguments, num <= 0, xi and d2 not together, i == j, kappa <= 0
+ * or tau <= 0, a weight that is negative or not finite, R~ outside SO(3), min_redundancy outside (0, 1)); they are decided on
+ * the host before any device work, and because the others must not be left waiting they travel in the agreement record: the
+ * participant whose argument it was reports the words above, the others "rank q: invalid arguments".  An endpoint outside
+ * the problem is refused behind the agreement, in the same words everywhere.  Every refusal of
+ * dpgo_team_marginal_covariances_across passes through with its own message.  A refused call leaves every output untouched on
+ * every participant and *res all zero.  Changes no solver state. */
+int dpgo_team_gate_candidates_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, const double *T,
+                                     int num, const dpgo_measurement_t *cand, double *xi /* 6 num or NULL */,
+                                     double *d2 /* num or NULL */, double *sigma_rel /* 36 num or NULL */, dpgo_covariance_t *res);
+int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, const double *T,
+                                        int num, const dpgo_measurement_t *meas, double min_redundancy, double *xi /* 6 num */,
+                                        double *xi_loo /* 6 num */, double *d2 /* num */, double *rho /* num */, double *pmin /* num */,
+                                        double *sigma_loo /* 36 num or NULL */, dpgo_covariance_t *res);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
