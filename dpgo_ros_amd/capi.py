@@ -132,7 +132,8 @@ dpgo_team_marginal_covariances dpgo_team_marginal_covariances_across
 dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_covariances_nested
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
 dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal
-dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across""".split()
+dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across
+dpgo_team_covariance_apply dpgo_team_linear_update_solved""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1131,6 +1132,37 @@ class Team:
              "marginal_covariances_nested")
         return res, diag, cross
 
+    def covariance_apply(self, V, T=None, method=None, max_block=None):
+        """X = Sigma V, the estimate's covariance applied to vectors: the solve H_red X_red = V_red on the factors
+        of a covariance path, without a block of Sigma.  V: [6 N, m] (or [6 N]: one column); rows 6 p .. 6 p + 5 belong to team
+        pose p in the perturbation of covariances (rotation first, body frame; translation, world frame; pose 0 fixed).  Sigma
+        is the full covariance whose rows and columns of pose 0 are zero: pose 0's rows of V are not read, those of X are zero.
+        T as in covariances (None: the rounding of the current iterate).  method: "dense" (the default) multiplies by the
+        explicit inverse; "nested" eliminates on covariance_plan(max_block)'s sets, split or not; "schur" raises DpgoError
+        ("nested" with no robot split has its sets).  Returns (Covariance, X[6 N, m]).  Two calls give the same bytes.  Raises
+        DpgoError as covariances does, for a V that is not finite, and for V and X that do not fit the device.  One team only.
+        Changes no solver state."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("covariance_apply: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("covariance_apply: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)
+        if V.ndim != 2 or V.shape[0] != 6 * N or V.shape[1] < 1:
+            raise ValueError("covariance_apply: V has shape %r, the team's %d poses need [%d, m] with m >= 1" % (V.shape, N, 6 * N))
+        Vf = np.asfortranarray(V)
+        X = np.zeros(Vf.shape, order="F")
+        res = Covariance()
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        _chk(lib().dpgo_team_covariance_apply(self.h, _d(T), code, int(max_block or 0), Vf.shape[1], _d(Vf), _d(X), C.byref(res)),
+             "covariance_apply")
+        return res, X
+
     @staticmethod
     def _across_check(what, method, max_block):
         """the arguments a per-record call cannot take with a transport: ValueError before any transport call"""
@@ -1446,7 +1478,7 @@ class Team:
         return dict(candidates=cand, gain=gain, gain_cond=gc, rank=rank, selected=selected, num_selected=n,
                     gain_total=float(gt.value), logdet_joint=float(lj.value), covariance=res)
 
-    def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None):
+    def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None, columns="blocks"):
         """The estimate and its covariances updated to first order for a set of new closures, without a re-solve (DESIGN.md
         5j): the information-filter update of the whole trajectory.  closures, T, method and max_block as in gate_jointly, whose
         A, R and M = A Sigma A^T + R these are: with B = Sigma A^T, dx = -B M^-1 xi, Sigma' = Sigma - B M^-1 B^T and
@@ -1464,7 +1496,15 @@ class Team:
             covariance       the Covariance record of the path (of Sigma, not Sigma').
         The covariance blocks, B, M and their products stay on the device.  Raises DpgoError as gate_jointly does, for a pair that
         names a pose outside the team, and for a batch whose blocks and matrices do not fit the device.  One team only.
-        Changes no solver state."""
+        Changes no solver state.
+        columns: how B = Sigma A^T is formed.  "blocks" (the default) asks the covariance path for the N m blocks
+        Sigma_{p, e_a} of the m distinct endpoint poses and multiplies afterwards.  "solve" has the path apply Sigma to A^T on
+        its own factors (covariance_apply) and asks it for `pairs` alone: the time no longer grows with the
+        blocks extracted.  Under "solve" method is "dense" or "nested" ("schur" raises DpgoError: "nested" with no robot split
+        has its sets), and the outputs are NOT bitwise those of "blocks", because the sums of B come in another order; they
+        agree to round-off, and two calls of either route give the same bytes."""
+        if columns not in ("blocks", "solve"):
+            raise ValueError("linear_update: columns must be \"blocks\" or \"solve\", not %r" % (columns,))
         if method not in (None, "dense", "schur", "nested"):
             raise ValueError("linear_update: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
         N = int(sum(self.agents[i].n for i in self.ids))
@@ -1481,9 +1521,10 @@ class Team:
         xi, xp, sc = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(3)
         code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         p = lambda a: _d(a) if K else None
-        _chk(lib().dpgo_team_linear_update(self.h, _d(T), code, int(max_block or 0), K, p(cand), len(pr), _d(pr) if len(pr) else None,
-                                           _d(Tn), _d(dx), _d(diag), _d(cross) if len(pr) else None, _d(xi), _d(xp), _d(sc),
-                                           C.byref(res)), "linear_update")
+        call = lib().dpgo_team_linear_update_solved if columns == "solve" else lib().dpgo_team_linear_update
+        _chk(call(self.h, _d(T), code, int(max_block or 0), K, p(cand), len(pr), _d(pr) if len(pr) else None,
+                  _d(Tn), _d(dx), _d(diag), _d(cross) if len(pr) else None, _d(xi), _d(xp), _d(sc),
+                  C.byref(res)), "linear_update")
         return dict(T=Tn, delta=dx, cov_diag=diag, cov_pairs=cross, xi=xi, xi_post=xp, d2_joint=float(sc[0]), logdet_M=float(sc[1]),
                     logdet_R=float(sc[2]), information_gain=0.5 * float(sc[1] - sc[2]), covariance=res)
 

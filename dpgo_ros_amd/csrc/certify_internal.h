@@ -180,18 +180,31 @@ struct CovEpilogue {
   virtual int run(const CovStage &stage) = 0;
   virtual ~CovEpilogue() = default;
 };
+// Sigma applied to vectors inside a covariance path (covariance_apply.h).  A path that is given one allocates V
+// and X (6 N x num_cols, column-major, leading dimension 6 N; rows 6 p .. 6 p + 5 belong to team pose p), calls rhs() once
+// CovFrame::begin has T on the device -- rhs() queues on `stream` whatever writes every element of V outside pose 0's rows,
+// which are not read -- forms X = Sigma V from its own factors without a block of Sigma, and sets X before it runs the
+// epilogue: the pointer stays valid as long as the staged blocks do.  Pose 0's rows of X are zero bits.
+struct CovApply {
+  int num_cols = 0;
+  double *X = nullptr;
+  double ms_products = 0.0, flops = 0.0;  // the apply's own products, for the caller's DPGO_TIMING line
+  virtual int rhs(const double *Td, int N, double *V, hipStream_t stream) = 0;
+  virtual ~CovApply() = default;
+};
 
 // the device part of dpgo_team_marginal_covariances by the dense inverse (covariance.hip, behind the host-side refusals of
 // marginal_covariances_call): DPGO_OK, DPGO_ERR with a message, or k + 1 > 0 when the pivot of row k of the reduced Hessian
 // was not positive
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
-                      dpgo_covariance_t *res, CovEpilogue *epi = nullptr);
+                      dpgo_covariance_t *res, CovEpilogue *epi = nullptr, CovApply *app = nullptr);
 // dpgo_team_marginal_covariances / _nested with an epilogue in the place of the copy of the blocks (covariance.hip,
 // covariance_nested.hip): the public calls are these with epi = nullptr; with one, cov_diag and cov_pairs may be null
 int marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
-                              double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi);
+                              double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi, CovApply *app = nullptr);
+// (with app the nested call runs its own device part on nest_plan_team's plan whether or not a robot is split)
 int marginal_covariances_nested_call(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs, double *cov_diag,
-                                     double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi);
+                                     double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi, CovApply *app = nullptr);
 // the refusals of the marginal covariances that are decided on the host, shared by its methods (covariance.hip): DPGO_OK, 1 (the
 // anchor alone: outputs written), or DPGO_ERR
 int covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_error, int num_pairs, const int *pairs, double *cov_diag,

@@ -140,11 +140,12 @@ struct ClosureCall {
   // The covariance path by `method`, with its own refusals and messages, for the listed pairs; its blocks stay on the device
   // for the epilogue.  The path's code, or a refusal with res cleared when the path returned without staging anything (a team
   // of the anchor alone has no two poses to join: the endpoint checks refuse that before)
+  // app: Sigma applied to vectors beside the blocks (covariance_apply.h), for a call that takes its columns from the solve
   int path(dpgo_team_t *t, const double *T, int method, int max_block, int np, const int *pairs, dpgo_covariance_t *res,
-           ClosureEpilogue &epi) const {
+           ClosureEpilogue &epi, CovApply *app = nullptr) const {
     const int rc = method == DPGO_GATE_NESTED
-                       ? marginal_covariances_nested_call(t, T, max_block, np, pairs, nullptr, nullptr, res, &epi)
-                       : marginal_covariances_call(t, T, method == DPGO_GATE_SCHUR ? DPGO_COV_SCHUR : 0, np, pairs, nullptr, nullptr, res, &epi);
+                       ? marginal_covariances_nested_call(t, T, max_block, np, pairs, nullptr, nullptr, res, &epi, app)
+                       : marginal_covariances_call(t, T, method == DPGO_GATE_SCHUR ? DPGO_COV_SCHUR : 0, np, pairs, nullptr, nullptr, res, &epi, app);
     if (rc != DPGO_OK) return rc;
     if (!epi.ran) {
       std::memset(res, 0, sizeof *res);

@@ -21,6 +21,7 @@
 // This file also holds what the three methods share on the host (covariance_frame.h): the frame of a call (CovFrame), the
 // refusals decided before any device work, and the public entry points of the dense and the Schur method
 // (covariance_schur.hip, covariance_nested.hip have the other two device parts).
+#include "covariance_apply.h"
 #include "covariance_block.h"
 #include "covariance_frame.h"
 
@@ -196,7 +197,7 @@ std::string pivot_message(const std::string &what, long long row, const std::str
 // written only when the factorisation succeeded.  Returns DPGO_OK, DPGO_ERR (message set), or k + 1 > 0: the pivot of row k of
 // H_red was not positive.
 int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
-                      dpgo_covariance_t *res, CovEpilogue *epi) {
+                      dpgo_covariance_t *res, CovEpilogue *epi, CovApply *app) {
   if (check_team(t, "marginal_covariances")) return DPGO_ERR;
   CovFrame F(t);
   const int N = F.N, n = 6 * (N - 1);
@@ -220,22 +221,31 @@ int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int 
     srcs.push_back({q.agent, q.idx});
   }
   const size_t nn = (size_t)n * n;
-  DevBuf<double> d_A, d_W, d_M;
+  DevBuf<double> d_A, d_W, d_M, d_V, d_X;
   DevBuf<int> d_pairs;
   DevBuf<CovItem> d_items;
   DevBuf<CovSrc> d_src;
+  DevBuf<ApplyItem> d_app;
   hipStream_t s = t->stream;
+  // Sigma applied to vectors (covariance_apply.h): V and X of 6 N x num_cols beside the three matrices
+  const size_t vx = app ? (size_t)6 * N * app->num_cols : 0;
   auto nomem = [&]() {
-    set_err("marginal_covariances: device allocation failed (" + std::to_string(3 * nn * 8) + " bytes for three matrices of order " +
-            std::to_string(n) + ")");
+    set_err("marginal_covariances: device allocation failed (" + std::to_string((3 * nn + 2 * vx) * 8) + " bytes for three matrices of order " +
+            std::to_string(n) + (app ? ", V and X" : "") + ")");
     return DPGO_ERR;
   };
   if (d_A.alloc(nn) || d_W.alloc(nn) || d_M.alloc(nn) || d_pairs.alloc(2 * (size_t)num_pairs) || d_items.upload(items, s) || d_src.upload(srcs, s))
     return nomem();
+  if (app && (d_V.alloc(vx) || d_X.alloc(vx) || d_app.alloc(1))) return nomem();
   // (queued before the frame's first mark: outside the time of the assembly)
   if (num_pairs > 0) HIPC(hipMemcpyAsync(d_pairs.p, pairs, sizeof(int) * 2 * (size_t)num_pairs, hipMemcpyHostToDevice, s));
   if (const int rc = F.begin(T, 1, num_pairs, false)) return rc > 0 ? nomem() : DPGO_ERR;
   SchurMarks &marks = F.marks;
+  if (app) {
+    HIPC(hipMemsetAsync(d_X.p, 0, sizeof(double) * vx, s));
+    if (app->rhs(F.Td, N, d_V.p, s)) return DPGO_ERR;
+    MARK(-1);
+  }
   HIPC(hipMemsetAsync(d_A.p, 0, sizeof(double) * nn, s));
   if (!items.empty())
     k_cov_assemble<<<(unsigned)((items.size() + 255) / 256), 256, 0, s>>>(t->d_agents.p, d_items.p, d_src.p, (int)items.size(), F.Td,
@@ -253,7 +263,23 @@ int covariance_device(dpgo_team_t *t, const double *T, int num_pairs, const int 
   k_cov_extract<<<(unsigned)((F.nout + 255) / 256), 256, 0, s>>>(d_M.p, n, N, d_pairs.p, num_pairs, F.outd);
   HIPC(hipGetLastError());
   MARK(4);
+  size_t app_mark = 0;
+  if (app) {
+    // X_red = G V_red: one product with the explicit inverse, past pose 0's rows of V and of X
+    const ApplyItem it{d_M.p, d_V.p + 6, d_X.p + 6, nullptr, nullptr, n, 6 * N, 6 * N, n, app->num_cols, n};
+    HIPC(hipMemcpyAsync(d_app.p, &it, sizeof it, hipMemcpyHostToDevice, s));
+    launch_apply_gemm(s, false, d_app.p, &it, 1, false);
+    HIPC(hipGetLastError());
+    MARK(-1);
+    app_mark = marks.ev.size() - 1;
+    app->flops = apply_flops(&it, 1);
+    app->X = d_X.p;
+  }
   if (F.finish(epi, res, cov_diag, cov_pairs, {1})) return DPGO_ERR;
+  if (app) {
+    float v = 0.f;
+    if (hipEventElapsedTime(&v, marks.ev[app_mark - 1], marks.ev[app_mark]) == hipSuccess) app->ms_products = v;
+  }
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr, "marginal_covariances: n %d, %zu blocks, assemble %.3f ms, invert %.3f ms, extract %.3f ms\n", n, items.size(),
@@ -310,7 +336,7 @@ int covariance_host_checks(dpgo_team_t *t, const double *T, const char *flags_er
 }
 
 int marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
-                              double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi) {
+                              double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi, CovApply *app) {
   const char *what = "marginal_covariances";
   int N = 0;
   const int pre = covariance_host_checks(t, T, flags != 0 && flags != DPGO_COV_SCHUR ? "flags must be 0 or DPGO_COV_SCHUR" : nullptr, num_pairs,
@@ -330,9 +356,18 @@ int marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int nu
   }
   {
     // three dense matrices of order 6 (N - 1)
-    const double n = 6.0 * (N - 1), need = 3.0 * n * n * 8.0;
+    const double n = 6.0 * (N - 1), vx = app ? 2.0 * 8.0 * 6.0 * N * (double)app->num_cols : 0.0, need = 3.0 * n * n * 8.0 + vx;
     double avail = 0.0;
     if (!cov_device_avail(t, &avail)) { set_err(std::string(what) + ": hipMemGetInfo failed"); return DPGO_ERR; }
+    if (need > avail && app) {
+      char buf[400];
+      std::snprintf(buf, sizeof buf,
+                    "%s: the dense Hessian of order %.0f, its inverse and V and X of %d columns need %.0f bytes (3 x 8 n^2 + 2 x 8 x 6 N x "
+                    "num_cols), %.0f are available on the device",
+                    what, n, app->num_cols, need, avail);
+      set_err(buf);
+      return DPGO_ERR;
+    }
     if (need > avail) {
       char buf[400];
       std::snprintf(buf, sizeof buf,
@@ -343,7 +378,7 @@ int marginal_covariances_call(dpgo_team_t *t, const double *T, int flags, int nu
       return DPGO_ERR;
     }
   }
-  const int rc = covariance_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, epi);
+  const int rc = covariance_device(t, T, num_pairs, pairs, cov_diag, cov_pairs, res, epi, app);
   if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
   if (rc > 0) {
     set_err(pivot_message(what, rc - 1, "the reduced Hessian", (rc - 1) / 6 + 1));

@@ -19,12 +19,16 @@
 // blockIdx.z), so neither do the bits of the result.  No atomics, fp64 throughout, outputs staged on the device.
 // The blocks are the sets of the extraction kernels of covariance_extract.h, which the Schur path launches too; the head and
 // the tail of the call are CovFrame's (covariance_frame.h).
+// With a CovApply (certify_internal.h, covariance_apply.h) the path also forms X = Sigma V from the same factors,
+// without a block of Sigma: u_b = C_b v_b and W_b^T v_b while C_b is live in its batch, r_S = v_S - sum_b scatter(W_b^T v_b) one
+// launch per block in block order, x_S = Sigma_SS r_S, x_b = u_b - W_b x_S[N_b].  Without one it queues what it queued before.
 // Loads of matrices, lists and index arrays go through gp(); the one exception is the record of a table (GemmItem,
 // NestTarget, CovBlock: one per workgroup or per thread, a few dozen bytes), copied as a struct -- where the index is
 // uniform (blockIdx) the compiler reads it through the scalar cache.
 #include <cmath>
 #include <cstdlib>
 
+#include "covariance_apply.h"
 #include "covariance_extract.h"
 
 namespace dpgo {
@@ -190,14 +194,15 @@ void nest_plan_team(dpgo_team_t *t, int max_block, NestPlan &P) {
 
 // ---- memory ("nested"; include/dpgo_hip.h has the formula).  Doubles of workspace block b needs while its
 // batch is eliminated: H_bb, the inverse's work matrix and C_b (3 n_b^2), B_b (n_b K_b), B_b^T W_b (K_b^2); n_b = 6 |I_b|,
-// K_b = 6 |N_b|.  (The extraction puts Z_b where B_b was and Sigma_SS[N_b, N_b] where B_b^T W_b was.)
-double nest_block_ws(const NestPlan::Block &b) {
+// K_b = 6 |N_b|.  (The extraction puts Z_b where B_b was and Sigma_SS[N_b, N_b] where B_b^T W_b was.)  With Sigma applied to
+// `cols` vectors (covariance_apply.h) the temporary W_b^T v_b (K_b cols) rides in the same workspace.
+double nest_block_ws(const NestPlan::Block &b, int cols = 0) {
   const double n = 6.0 * b.poses.size(), K = 6.0 * b.nb.size();
-  return 3.0 * n * n + n * K + K * K;
+  return 3.0 * n * n + n * K + K * K + K * cols;
 }
 
 struct NestBytes {
-  double large = 0, small = 0, ws_min = 0, w_all = 0, sep = 0;
+  double large = 0, small = 0, ws_min = 0, w_all = 0, sep = 0, apply = 0;
   int ws_block = -1;
 };
 
@@ -206,7 +211,10 @@ struct NestBytes {
 // (24 bytes per kept or requested block), the work list (40 bytes per stored block of Q), the tables of the blocks
 // (56 + 3 x 48 + 2 x 16 bytes each: a CovBlock, three GemmItem, two NestTarget), the index lists (4 bytes per interior pose
 // and per entry of an N_b), the Linv blocks of dense_spd_inverse (8 KiB per 32 rows of every factor)
-NestBytes nest_bytes(dpgo_team_t *t, const NestPlan &P, int num_pairs) {
+// With Sigma applied to `cols` vectors: apply = V and X (8 x 6 N cols each), r_S (8 x 6 |S| cols; x_S is written straight into
+// X), one ApplyItem per block for each of the three products and one for the separator's (64 bytes each), the team poses of
+// the separator and of every N_b (4 bytes each); the temporaries are in the batch workspace (nest_block_ws)
+NestBytes nest_bytes(dpgo_team_t *t, const NestPlan &P, int num_pairs, int cols = 0) {
   NestBytes r;
   int max_n = 0, kmax = 0;
   size_t stored = 0;
@@ -216,7 +224,7 @@ NestBytes nest_bytes(dpgo_team_t *t, const NestPlan &P, int num_pairs) {
   }
   double linv = std::ceil(6.0 * P.nS / 32.0);
   for (size_t b = 0; b < P.blocks.size(); ++b) {
-    const double ws = nest_block_ws(P.blocks[b]);
+    const double ws = nest_block_ws(P.blocks[b], cols);
     if (ws > r.ws_min) { r.ws_min = ws; r.ws_block = (int)b; }
     r.w_all += 36.0 * (double)P.blocks[b].poses.size() * (double)P.blocks[b].nb.size();
     kmax = std::max(kmax, 6 * (int)P.blocks[b].nb.size());
@@ -229,16 +237,18 @@ NestBytes nest_bytes(dpgo_team_t *t, const NestPlan &P, int num_pairs) {
             8.0 * 6.0 * std::max(kmax, 1) * (double)cov_cross_chunk((size_t)num_pairs, kmax) + 24.0 * (2.0 * N + 3.0 * np) +
             40.0 * (double)stored + (double)(sizeof(CovBlock) + 3 * sizeof(GemmItem) + 2 * sizeof(NestTarget)) * nb +
             4.0 * (N + (double)P.sum_nb() + A + 1.0) + 8.0 * 1024.0 * linv;
+  if (cols > 0)
+    r.apply = 8.0 * (double)cols * (12.0 * N + 6.0 * P.nS) + (double)sizeof(ApplyItem) * (3.0 * nb + 1.0) + 4.0 * ((double)P.sum_nb() + P.nS);
   return r;
 }
 
 // the batches: blocks [beg[q], beg[q + 1]) in block order, each batch's workspace within ws_cap doubles (a single block may
 // exceed it: it then rides alone)
-std::vector<int> nest_batches(const NestPlan &P, double ws_cap) {
+std::vector<int> nest_batches(const NestPlan &P, double ws_cap, int cols = 0) {
   std::vector<int> beg(1, 0);
   double used = 0.0;
   for (size_t b = 0; b < P.blocks.size(); ++b) {
-    const double ws = nest_block_ws(P.blocks[b]);
+    const double ws = nest_block_ws(P.blocks[b], cols);
     if (b > (size_t)beg.back() && (used + ws > ws_cap || b - beg.back() >= 65535)) { beg.push_back((int)b); used = 0.0; }
     used += ws;
   }
@@ -264,17 +274,30 @@ double gemm_flops(const GemmItem *it, int count) {
 // The device part of dpgo_team_marginal_covariances_nested for a plan in which some robot is split.  DPGO_OK, DPGO_ERR
 // (message set), or 1: a pivot was not positive -- fail[0] the block (-1: the separator), fail[1] the team pose, fail[2] the
 // row of that factor.  The outputs are written only when every factorisation succeeded.
+// app: Sigma applied to vectors beside the blocks (covariance_apply.h); with one, any plan is valid -- an unsplit one, whose
+// blocks are the robots' interiors, and one block with an empty separator included.  Without one the launches are the same.
 int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T, int num_pairs, const int *pairs, double *cov_diag,
-                             double *cov_pairs, dpgo_covariance_t *res, int *fail, CovEpilogue *epi) {
+                             double *cov_pairs, dpgo_covariance_t *res, int *fail, CovEpilogue *epi, CovApply *app) {
+  const int cols = app ? app->num_cols : 0;
   const char *what = "marginal_covariances_nested";
   const int N = P.N, nS = 6 * P.nS, nblk = (int)P.blocks.size();
   int kmax = 0;
   for (const NestPlan::Block &b : P.blocks) kmax = std::max(kmax, 6 * (int)b.nb.size());
   // ---- memory: refused before any device work
-  const NestBytes nbytes = nest_bytes(t, P, num_pairs);
+  const NestBytes nbytes = nest_bytes(t, P, num_pairs, cols);
   double avail = 0.0;
   {
     if (!cov_device_avail(t, &avail)) { set_err(std::string(what) + ": hipMemGetInfo failed"); return DPGO_ERR; }
+    if (app && nbytes.large + nbytes.small + nbytes.apply > avail) {
+      char buf[600];
+      std::snprintf(buf, sizeof buf,
+                    "%s: the nested path needs %.0f bytes for its large buffers (the temporaries of %d columns among them), %.0f for "
+                    "the small ones and %.0f for V, X and r_S (8 x (12 N + 6 |S|) x num_cols, N = %d, |S| = %d), %.0f are available on "
+                    "the device",
+                    what, nbytes.large, cols, nbytes.small, nbytes.apply, N, P.nS, avail);
+      set_err(buf);
+      return DPGO_ERR;
+    }
     if (nbytes.large + nbytes.small > avail) {
       const bool by_sep = nbytes.sep >= nbytes.ws_min;
       const NestPlan::Block &wb = P.blocks[nbytes.ws_block];
@@ -293,8 +316,8 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     }
   }
   // the workspace of a batch: what is left beside everything else, at most 2 GiB, at least the largest block
-  const double ws_cap = std::max(nbytes.ws_min, std::min((double)((size_t)1 << 28), 0.5 * (avail - nbytes.large - nbytes.small) / 8.0 + nbytes.ws_min));
-  const std::vector<int> bbeg = nest_batches(P, ws_cap);
+  const double ws_cap = std::max(nbytes.ws_min, std::min((double)((size_t)1 << 28), 0.5 * (avail - nbytes.large - nbytes.small - nbytes.apply) / 8.0 + nbytes.ws_min));
+  const std::vector<int> bbeg = nest_batches(P, ws_cap, cols);
   const int nbatch = (int)bbeg.size() - 1;
   // ---- the work lists.  Every stored block of the team-wide Q outside pose 0's row and column is one of: two poses of one
   // block (H_bb), a block's pose and a separator pose of its N_b (B_b, or its mirror, dropped), two separator poses.  Symmetric
@@ -336,7 +359,7 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   double ws_need = 0.0;
   for (int q = 0; q < nbatch; ++q) {
     double u = 0.0;
-    for (int b = bbeg[q]; b < bbeg[q + 1]; ++b) u += nest_block_ws(P.blocks[b]);
+    for (int b = bbeg[q]; b < bbeg[q + 1]; ++b) u += nest_block_ws(P.blocks[b], cols);
     ws_need = std::max(ws_need, u);
   }
   CovFrame F(t);
@@ -350,6 +373,9 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   DevBuf<CovBlock> d_tab;
   DevBuf<CovBlk> d_keep, d_same, d_pub, d_is;
   DevBuf<CovCross> d_cross;
+  DevBuf<double> d_V, d_X, d_rS;
+  DevBuf<int> d_aint;
+  DevBuf<ApplyItem> d_app;
   // d_int: the team pose of every interior index (block after block), the N_b
   std::vector<int> ints;
   std::vector<size_t> ipose_at(nblk), nb_at(nblk), w_at(nblk + 1, 0);
@@ -372,11 +398,26 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     return DPGO_ERR;
   };
   if (bad) return nomem();
-  // the tables of the blocks.  Workspace of block b inside its batch: A | Wk | M | B (later Z) | P (later G)
+  // Sigma applied to vectors.  d_aint: the team poses of the separator, then of every N_b (the row maps of the tile)
+  std::vector<int> aints;
+  std::vector<size_t> nbp_at(nblk, 0);
+  const size_t vx = (size_t)6 * N * cols;
+  if (app) {
+    aints = P.sep;
+    for (int b = 0; b < nblk; ++b) {
+      nbp_at[b] = aints.size();
+      for (int k : P.blocks[b].nb) aints.push_back(P.sep[k]);
+    }
+    if (d_V.alloc(vx) || d_X.alloc(vx) || d_rS.alloc((size_t)nS * cols) || d_aint.upload(aints, s) || d_app.alloc((size_t)3 * nblk + 1))
+      return nomem();
+  }
+  // the tables of the blocks.  Workspace of block b inside its batch: A | Wk | M | B (later Z) | P (later G) | W_b^T v_b (app)
   std::vector<NestTarget> tgt(2 * (size_t)nblk);
   std::vector<GemmItem> gemm(3 * (size_t)nblk);  // [0, nblk) W = C B, [nblk, 2 nblk) P = B^T W, [2 nblk, 3 nblk) Z = W G
   std::vector<CovBlock> tab(nblk);
-  std::vector<double *> pA(nblk), pWk(nblk), pM(nblk), pP(nblk);
+  std::vector<double *> pA(nblk), pWk(nblk), pM(nblk), pP(nblk), pEnd(nblk);
+  // [0, nblk) u_b = C_b v_b, [nblk, 2 nblk) t_b = W_b^T v_b, [2 nblk, 3 nblk) x_b -= W_b x_S[N_b], 3 nblk: x_S = Sigma_SS r_S
+  std::vector<ApplyItem> aitem(app ? 3 * (size_t)nblk + 1 : 0);
   std::vector<int> order(nblk);
   for (int q = 0; q < nbatch; ++q) {
     double *w = d_ws.p;
@@ -384,7 +425,9 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
       const int n = 6 * (int)P.blocks[b].poses.size(), K = 6 * (int)P.blocks[b].nb.size();
       const size_t nn = (size_t)n * n, nK = (size_t)n * K;
       double *A = w, *Wk = A + nn, *M = Wk + nn, *B = M + nn, *Pm = B + nK;
-      w = Pm + (size_t)K * K;
+      double *Tm = Pm + (size_t)K * K;
+      w = Tm + (size_t)K * cols;
+      pEnd[b] = w;
       double *W = d_W.p + w_at[b];
       pA[b] = A; pWk[b] = Wk; pM[b] = M; pP[b] = Pm; order[b] = n;
       tgt[2 * b] = {A, n, 0};
@@ -393,7 +436,17 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
       gemm[nblk + b] = {B, W, Pm, n, n, K, K, K, n};
       gemm[2 * nblk + b] = {W, Pm, B, n, K, n, n, K, K};
       tab[b] = {W, d_int.p + nb_at[b], d_int.p + ipose_at[b], M, Pm, B, n, K};
+      if (app) {
+        const int *poses = d_int.p + ipose_at[b], *nbp = d_aint.p + nbp_at[b];
+        aitem[b] = {M, d_V.p, d_X.p, poses, poses, n, 6 * N, 6 * N, n, cols, n};
+        aitem[nblk + b] = {W, d_V.p, Tm, poses, nullptr, n, 6 * N, K, K, cols, n};
+        aitem[2 * nblk + b] = {W, d_X.p, d_X.p, nbp, poses, n, 6 * N, 6 * N, n, cols, K};
+      }
     }
+  }
+  if (app) {
+    aitem[3 * nblk] = {d_M.p, d_rS.p, d_X.p, nullptr, d_aint.p, nS, nS, 6 * N, nS, cols, nS};
+    HIPC(hipMemcpyAsync(d_app.p, aitem.data(), sizeof(ApplyItem) * aitem.size(), hipMemcpyHostToDevice, s));
   }
   HIPC(hipMemcpyAsync(d_tgt.p, tgt.data(), sizeof(NestTarget) * tgt.size(), hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d_gemm.p, gemm.data(), sizeof(GemmItem) * gemm.size(), hipMemcpyHostToDevice, s));
@@ -401,6 +454,14 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   if (const int rc = F.begin(T, nblk + 1, num_pairs, true)) return rc > 0 ? nomem() : DPGO_ERR;
   double *Td = F.Td, *lam = F.lam, *stat = F.stat, *keepd = F.keepd, *outd = F.outd;
   SchurMarks &marks = F.marks;
+  std::vector<size_t> app_marks;  // the marks that END an interval of the apply's own launches
+  if (app) {
+    HIPC(hipMemsetAsync(d_X.p, 0, sizeof(double) * vx, s));
+    if (app->rhs(Td, N, d_V.p, s)) return DPGO_ERR;
+    launch_apply_gather(s, d_V.p, (size_t)6 * N, d_aint.p, P.nS, cols, d_rS.p);  // r_S = v_S
+    HIPC(hipGetLastError());
+    MARK(-1);
+  }
   if (nS > 0) {
     HIPC(hipMemsetAsync(d_S.p, 0, sizeof(double) * SS, s));
     launch_cov_assemble_map(s, t->d_agents.p, d_items.p + L.lbeg[nblk], d_src.p, d_dst.p + L.lbeg[nblk], L.count(nblk), Td, lam, d_S.p, nS);
@@ -411,7 +472,7 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   double flops_fact = 0.0, flops_prod = 0.0;
   for (int q = 0; q < nbatch; ++q) {
     const int b0 = bbeg[q], b1 = bbeg[q + 1], cnt = b1 - b0;
-    const size_t used = (size_t)((pP[b1 - 1] + (size_t)tab[b1 - 1].K * tab[b1 - 1].K) - d_ws.p);
+    const size_t used = (size_t)(pEnd[b1 - 1] - d_ws.p);
     HIPC(hipMemsetAsync(d_ws.p, 0, sizeof(double) * used, s));
     const int i0 = L.lbeg[b0], ni = L.lbeg[b1] - i0;
     if (ni > 0)
@@ -447,6 +508,16 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     HIPC(hipGetLastError());
     MARK(2);
     flops_prod += gemm_flops(gemm.data() + b0, cnt) + gemm_flops(gemm.data() + nblk + b0, cnt);
+    if (app) {
+      launch_apply_gemm(s, false, d_app.p + b0, aitem.data() + b0, cnt, false);               // u_b = C_b v_b, into X
+      launch_apply_gemm(s, true, d_app.p + nblk + b0, aitem.data() + nblk + b0, cnt, false);  // t_b = W_b^T v_b
+      for (int b = b0; b < b1; ++b)                                                           // r_S[N_b] -= t_b, in block order
+        launch_apply_scatter_sub(s, d_rS.p, (size_t)nS, aitem[nblk + b].C, tab[b].K, cols, tab[b].nb);
+      HIPC(hipGetLastError());
+      MARK(-1);
+      app_marks.push_back(marks.ev.size() - 1);
+      app->flops += apply_flops(aitem.data() + b0, cnt) + apply_flops(aitem.data() + nblk + b0, cnt);
+    }
     const int k0 = keep_beg[b0], nk = keep_beg[b1] - k0;  // (never empty: the diagonal blocks)
     launch_ext_keep(s, d_tab.p, d_keep.p + k0, nk, keepd);
     HIPC(hipGetLastError());
@@ -465,6 +536,15 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
     launch_ext_public(s, d_M.p, nS, d_pub.p, (int)O.pub.size(), outd);
     HIPC(hipGetLastError());
     MARK(4);
+    if (app) {
+      launch_apply_gemm(s, false, d_app.p + 3 * nblk, aitem.data() + 3 * nblk, 1, false);  // x_S = Sigma_SS r_S, into X
+      for (int q = 0; q < nbatch; ++q)                                                     // x_b = u_b - W_b x_S[N_b]
+        launch_apply_gemm(s, false, d_app.p + 2 * nblk + bbeg[q], aitem.data() + 2 * nblk + bbeg[q], bbeg[q + 1] - bbeg[q], true);
+      HIPC(hipGetLastError());
+      MARK(-1);
+      app_marks.push_back(marks.ev.size() - 1);
+      app->flops += apply_flops(aitem.data() + 2 * nblk, nblk + 1);
+    }
   }
   // ---- the interior blocks, by the same batches: Sigma_SS[N_b, N_b], Z_b = W_b Sigma_SS[N_b, N_b], the diagonal blocks and the
   // pairs inside a block
@@ -490,7 +570,12 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
   // log det and pivots: the blocks in order, the separator last
   std::vector<char> counted(nblk + 1, 1);
   counted[nblk] = nS > 0;
+  if (app) app->X = d_X.p;
   if (F.finish(epi, res, cov_diag, cov_pairs, counted)) return DPGO_ERR;
+  for (size_t k : app_marks) {
+    float v = 0.f;
+    if (hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) == hipSuccess) app->ms_products += v;
+  }
   const double *ms = F.ms;
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
@@ -499,7 +584,7 @@ int covariance_nested_device(dpgo_team_t *t, const NestPlan &P, const double *T,
                  "N_b %d, %.0f bytes; assemble %.3f ms, factorisations %.3f ms (%.2f TFLOP/s), products %.3f ms (%.2f TFLOP/s), separator "
                  "inverse %.3f ms, extract %.3f ms\n",
                  6 * (N - 1), nblk, 6 * P.largest_block(), nbatch, nS, P.promoted, 6 * P.largest_nb(),
-                 nbytes.large + nbytes.small + 8.0 * (ws_need - nbytes.ws_min), ms[0], ms[1], flops_fact / (1e9 * std::max(ms[1], 1e-9)), ms[2],
+                 nbytes.large + nbytes.small + nbytes.apply + 8.0 * (ws_need - nbytes.ws_min), ms[0], ms[1], flops_fact / (1e9 * std::max(ms[1], 1e-9)), ms[2],
                  flops_prod / (1e9 * std::max(ms[2], 1e-9)), ms[3], ms[4]);
   return DPGO_OK;
 }
@@ -563,7 +648,8 @@ extern "C" int dpgo_team_marginal_covariances_nested(dpgo_team_t *t, const doubl
 }
 
 int dpgo_cert::marginal_covariances_nested_call(dpgo_team_t *t, const double *T, int max_block, int num_pairs, const int *pairs,
-                                                double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi) {
+                                                double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, CovEpilogue *epi,
+                                                CovApply *app) {
   const char *what = "marginal_covariances_nested";
   int N = 0;
   const int pre = covariance_host_checks(t, T, nullptr, num_pairs, pairs, cov_diag, cov_pairs, res, what, &N, epi != nullptr);
@@ -572,9 +658,9 @@ int dpgo_cert::marginal_covariances_nested_call(dpgo_team_t *t, const double *T,
   NestPlan P;
   nest_plan_team(t, nest_max_block(max_block), P);
   // no robot is split: the sets are those of the robot-wise Schur path, and so is the call
-  if (!P.split) return marginal_covariances_call(t, T, DPGO_COV_SCHUR, num_pairs, pairs, cov_diag, cov_pairs, res, epi);
+  if (!P.split && !app) return marginal_covariances_call(t, T, DPGO_COV_SCHUR, num_pairs, pairs, cov_diag, cov_pairs, res, epi);
   int fail[3] = {0, 0, 0};
-  const int rc = covariance_nested_device(t, P, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail, epi);
+  const int rc = covariance_nested_device(t, P, T, num_pairs, pairs, cov_diag, cov_pairs, res, fail, epi, app);
   if (rc != DPGO_OK) std::memset(res, 0, sizeof *res);
   if (rc > 0) {
     set_err(pivot_message(what, fail[2], fail[0] < 0 ? "the Schur complement on the separator"

@@ -23,12 +23,18 @@
 // U = B G on the fp64 matrix cores through dgemm_tile, k_upd_z forms z and xi_post, k_upd_scalars the three figures, and
 // k_upd_finish, one wave per pose or requested pair, reduces the 6 K columns and writes T', dx and the blocks of Sigma'.
 // B, U, M and G stay on the device; only the outputs go to the host.
+//
+// On the solve (dpgo_team_linear_update_solved) the path is asked for the caller's own pairs alone and is handed
+// a CovApply: k_apply_rhs_closures writes V = A^T (apply_block.h) once T is on the device, the path forms X = Sigma V on its
+// factors, and that X is B.  k_upd_b is skipped; k_upd_m onward runs unchanged on that B.  The sums of B come in another order
+// than on the rectangular set, so the outputs of the two routes agree to round-off, not bitwise.
 #include <algorithm>
 #include <chrono>
 
 #include "closure_frame.h"
 #include "covariance_schur.h"
 #include "linear_update_block.h"
+#include "apply_block.h"
 
 namespace dpgo {
 
@@ -51,6 +57,19 @@ __global__ __launch_bounds__(256) void k_upd_b(const double *__restrict__ T, con
     for (int c = 0; c < 6; ++c)
 #pragma unroll
       for (int a = 0; a < 6; ++a) gp(o)[c * ld + a] = Bk[a][c];
+  }
+}
+
+// V = A^T into a zeroed V (6 N x 6 K, column-major, leading dimension 6 N): one lane per closure, grid-stride; J_i^T and J_j^T
+// of closure k go into column block k at the rows of its endpoints (apply_rhs_closure), pose 0's rows stay zero
+__global__ __launch_bounds__(256) void k_apply_rhs_closures(const double *__restrict__ T, const GateRec *__restrict__ cand, int N, int K,
+                                                            double *__restrict__ V) {
+  for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) {
+    JointEnds e;
+    double Rij[3][3], tij[3];
+    joint_ends(T, cand + k, e, Rij, tij);
+    if (e.i < 0 || e.i >= N || e.j < 0 || e.j >= N) continue;  // (the call has checked the endpoints on the host)
+    apply_rhs_closure(e.Ji, e.Jj, e.i, e.j, k, (size_t)6 * N, V);
   }
 }
 
@@ -176,6 +195,7 @@ struct UpdateEpilogue : ClosureEpilogue {
   std::vector<GateRec> cand;  // w0, w1: the ranks of i and j among the endpoints
   std::vector<int> user_pairs;  // the caller's pairs, behind the N m blocks of the call
   int m = 0, N = 0;
+  const CovApply *solve = nullptr;  // on the solve: the path's X is B, and the records are already on the device
   DevBuf<GateRec> d_cand;
   DevBuf<double> d_B, d_U, d_M, d_W, d_G, d_work, d_out;
   DevBuf<int> d_pairs;
@@ -189,7 +209,7 @@ struct UpdateEpilogue : ClosureEpilogue {
   }
   int alloc() {
     const size_t k = K();
-    if (d_cand.alloc(k) || d_B.alloc((size_t)36 * N * k) || d_U.alloc((size_t)36 * N * k) || d_M.alloc(36 * k * k) || d_W.alloc(36 * k * k) ||
+    if (d_cand.alloc(k) || (!solve && d_B.alloc((size_t)36 * N * k)) || d_U.alloc((size_t)36 * N * k) || d_M.alloc(36 * k * k) || d_W.alloc(36 * k * k) ||
         d_G.alloc(36 * k * k) || d_work.alloc(6 * k + 4) || d_out.alloc(out_doubles()) || d_pairs.alloc(2 * P())) {
       char buf[200];
       std::snprintf(buf, sizeof buf, "linear_update: device allocation failed (%.0f bytes for %zu closures on %d poses)",
@@ -201,7 +221,10 @@ struct UpdateEpilogue : ClosureEpilogue {
   }
   int run(const CovStage &st) override {
     const size_t k = K(), np = P();
-    if (st.N != N || (size_t)st.num_pairs != (size_t)N * m + np) {
+    const size_t nrect = solve ? 0 : (size_t)N * m;
+    if (solve && !solve->X) { set_err("linear_update: the covariance path formed no X"); return DPGO_ERR; }
+    const double *B = solve ? solve->X : d_B.p;
+    if (st.N != N || (size_t)st.num_pairs != nrect + np) {
       set_err("linear_update: the staged blocks are not the rectangular set of the endpoints");
       return DPGO_ERR;
     }
@@ -217,17 +240,17 @@ struct UpdateEpilogue : ClosureEpilogue {
       }
     hipStream_t s = st.stream;
     const int n = (int)(6 * k);
-    HIPC(hipMemcpyAsync(d_cand.p, cand.data(), sizeof(GateRec) * k, hipMemcpyHostToDevice, s));
+    if (!solve) HIPC(hipMemcpyAsync(d_cand.p, cand.data(), sizeof(GateRec) * k, hipMemcpyHostToDevice, s));
     if (np) HIPC(hipMemcpyAsync(d_pairs.p, user_pairs.data(), sizeof(int) * 2 * np, hipMemcpyHostToDevice, s));
     double *oT = d_out.p, *odx = oT + (size_t)12 * N, *odiag = odx + (size_t)6 * N, *opairs = odiag + (size_t)36 * N;
     double *oxi = opairs + 36 * np, *opost = oxi + 6 * k, *oscal = opost + 6 * k;
     double *z = d_work.p, *ldet = z + 6 * k;
     HIPC(hipEventRecord(ev[0], s));
     // at most eight workgroups per CU of an MI355X: the lanes beyond stride over the rest
-    k_upd_b<<<(unsigned)std::min<size_t>(((size_t)N * k + 255) / 256, 2048), 256, 0, s>>>(st.Td, st.pairs, d_cand.p, N, (int)k, d_B.p);
+    if (!solve) k_upd_b<<<(unsigned)std::min<size_t>(((size_t)N * k + 255) / 256, 2048), 256, 0, s>>>(st.Td, st.pairs, d_cand.p, N, (int)k, d_B.p);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[1], s));
-    k_upd_m<<<(unsigned)std::min<size_t>((k * k + 255) / 256, 2048), 256, 0, s>>>(st.Td, d_cand.p, (int)k, N, d_B.p, d_M.p, oxi);
+    k_upd_m<<<(unsigned)std::min<size_t>((k * k + 255) / 256, 2048), 256, 0, s>>>(st.Td, d_cand.p, (int)k, N, B, d_M.p, oxi);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[2], s));
     const int fail = dense_spd_inverse(s, d_M.p, d_W.p, d_G.p, n);  // (synchronises the stream; the factor stays in d_M)
@@ -240,15 +263,15 @@ struct UpdateEpilogue : ClosureEpilogue {
     }
     HIPC(hipEventRecord(ev[3], s));
     if (launch_cov_logdet(s, d_M.p, n, ldet)) return DPGO_ERR;
-    k_upd_u<<<dim3((unsigned)((6 * (size_t)N + 63) / 64), (unsigned)((n + 63) / 64), 1), 256, 0, s>>>(d_B.p, d_G.p, d_U.p, 6 * N, n);
+    k_upd_u<<<dim3((unsigned)((6 * (size_t)N + 63) / 64), (unsigned)((n + 63) / 64), 1), 256, 0, s>>>(B, d_G.p, d_U.p, 6 * N, n);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[4], s));
     k_upd_z<<<(unsigned)std::min<size_t>((n + 255) / 256, 2048), 256, 0, s>>>(d_G.p, oxi, d_cand.p, n, z, opost);
     k_upd_scalars<<<1, 64, 0, s>>>(oxi, z, d_cand.p, (int)k, ldet, oscal);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[5], s));
-    k_upd_finish<<<(unsigned)(((size_t)N + np + 3) / 4), 256, 0, s>>>(st.Td, st.diag, st.pairs + (size_t)36 * N * m, d_pairs.p, N, (int)k, (int)np,
-                                                                     d_B.p, d_U.p, z, oT, odx, odiag, opairs);
+    k_upd_finish<<<(unsigned)(((size_t)N + np + 3) / 4), 256, 0, s>>>(st.Td, st.diag, st.pairs + 36 * nrect, d_pairs.p, N, (int)k, (int)np,
+                                                                     B, d_U.p, z, oT, odx, odiag, opairs);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ev[6], s));
     h_out.resize(out_doubles());
@@ -258,16 +281,23 @@ struct UpdateEpilogue : ClosureEpilogue {
   }
 };
 
-}  // namespace
+// the hook of the solve: the records to the device, V cleared, V = A^T
+struct UpdateRhs : CovApply {
+  UpdateEpilogue *e = nullptr;
+  int rhs(const double *Td, int N, double *V, hipStream_t s) override {
+    const size_t k = e->K();
+    if (N != e->N) { set_err("linear_update: the covariance path's poses are not the call's"); return DPGO_ERR; }
+    HIPC(hipMemcpyAsync(e->d_cand.p, e->cand.data(), sizeof(GateRec) * k, hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(V, 0, sizeof(double) * 36 * (size_t)N * k, s));
+    k_apply_rhs_closures<<<(unsigned)std::min<size_t>((k + 255) / 256, 2048), 256, 0, s>>>(Td, e->d_cand.p, N, (int)k, V);
+    HIPC(hipGetLastError());
+    return DPGO_OK;
+  }
+};
 
-}  // namespace dpgo_cert
-
-using namespace dpgo_cert;
-
-extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method, int max_block, int num,
-                                       const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new, double *delta,
-                                       double *cov_diag, double *cov_pairs, double *xi, double *xi_post, double *scalars,
-                                       dpgo_covariance_t *res) {
+int linear_update_call(dpgo_team_t *t, const double *T, int method, int max_block, int num, const dpgo_measurement_t *closures,
+                       int num_pairs, const int *pairs, double *T_new, double *delta, double *cov_diag, double *cov_pairs, double *xi,
+                       double *xi_post, double *scalars, dpgo_covariance_t *res, bool solved) {
   const auto t_begin = std::chrono::steady_clock::now();
   // ---- the refusals of the call itself: on the host, before any device work, no output touched
   if (!t || !T || !res || !T_new || !delta || !cov_diag || !xi || !xi_post || !scalars) return UPDATE.refuse("null argument");
@@ -276,6 +306,9 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
   if (num_pairs < 0) return UPDATE.refuse("num_pairs must not be negative, not " + std::to_string(num_pairs));
   if (num_pairs > 0 && (!pairs || !cov_pairs)) return UPDATE.refuse("null argument");
   if (UPDATE.check_method(method)) return DPGO_ERR;
+  if (solved && method == DPGO_GATE_SCHUR)
+    return UPDATE.refuse("there is no solve on the robot-wise Schur path: DPGO_GATE_NESTED (method=\"nested\") with no robot split has "
+                         "the Schur path's sets");
   if (check_team_local(t, UPDATE.name)) return DPGO_ERR;
   const std::vector<int> offs = pose_offsets(t);
   const int N = offs.back();
@@ -295,7 +328,11 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
       return UPDATE.refuse("pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " + std::to_string(N) + ")");
   const std::vector<int> poses = rank_endpoints(epi.cand);
   const int m = epi.m = (int)poses.size();
-  const size_t K = (size_t)num, nb = (size_t)N * m, np = nb + (size_t)num_pairs;
+  const size_t K = (size_t)num, nb = solved ? 0 : (size_t)N * m, np = nb + (size_t)num_pairs;
+  UpdateRhs hook;
+  hook.e = &epi;
+  hook.num_cols = 6 * num;
+  if (solved) epi.solve = &hook;
   HIPC(hipSetDevice(t->device));
   {
     // the pair blocks the path stages for this call, B and U, M, the scratch of its inverse and G: the rest is the path's own
@@ -304,6 +341,14 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
     const double need = blocks + UpdateEpilogue::bytes(N, (double)K, num_pairs);
     double avail = 0.0;
     if (UPDATE.device_avail(t, &avail)) return DPGO_ERR;
+    if (solved && (need - bu > avail || 36 * K * K > (size_t)1 << 40 || 6 * K > (size_t)INT32_MAX / 2)) {
+      char buf[480];
+      std::snprintf(buf, sizeof buf,
+                    "%d closures on %d of %d poses: the %zu pair blocks, U (6 N x 6 K; V and B are the covariance path's) and the three "
+                    "matrices of order %zu need %.0f bytes (%.0f + %.0f + 3 x %.0f and the working arrays), %.0f are available on the device",
+                    num, m, N, np, 6 * K, need - bu, blocks, bu, mat, avail);
+      return UPDATE.refuse(buf);
+    }
     if (need > avail || np > (size_t)INT32_MAX || 36 * K * K > (size_t)1 << 40 || 6 * K > (size_t)INT32_MAX / 2) {
       char buf[480];
       std::snprintf(buf, sizeof buf,
@@ -318,12 +363,12 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
   // first as the pair (i, i), which agrees with the diagonal block, the second as zeros); the caller's pairs behind them
   std::vector<int> all;
   all.reserve(2 * np);
-  for (int a = 0; a < m; ++a)
+  for (int a = 0; a < m && !solved; ++a)
     for (int p = 0; p < N; ++p) { all.push_back(p); all.push_back(poses[a]); }
   all.insert(all.end(), pairs, pairs + 2 * (size_t)num_pairs);
   epi.user_pairs.assign(pairs, pairs + 2 * (size_t)num_pairs);
   if (epi.alloc()) return DPGO_ERR;
-  if (const int rc = UPDATE.path(t, T, method, max_block, (int)np, all.data(), res, epi)) return rc;
+  if (const int rc = UPDATE.path(t, T, method, max_block, (int)np, all.data(), res, epi, solved ? &hook : nullptr)) return rc;
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing) {
     float ms[6];
@@ -332,6 +377,9 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
     std::fprintf(stderr, "linear_update: %d closures on %d of %d poses (%zu pair blocks), k_upd_b %.3f ms, k_upd_m %.3f ms, inverse %.3f ms, "
                          "k_upd_u %.3f ms, k_upd_z and figures %.3f ms, k_upd_finish %.3f ms, the whole call %.3f ms\n",
                  num, m, N, np, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], whole);
+    if (solved)
+      std::fprintf(stderr, "linear_update (solve): B = Sigma A^T of %d columns inside the path, the apply's products %.3f ms (%.2f TFLOP/s)\n",
+                   6 * num, hook.ms_products, hook.flops / (1e9 * std::max(hook.ms_products, 1e-9)));
   }
   const double *h = epi.h_out.data();
   std::memcpy(T_new, h, sizeof(double) * 12 * (size_t)N);
@@ -344,4 +392,26 @@ extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int meth
   std::memcpy(xi_post, hp + 6 * K, sizeof(double) * 6 * K);
   std::memcpy(scalars, hp + 12 * K, sizeof(double) * 3);
   return DPGO_OK;
+}
+
+}  // namespace
+
+}  // namespace dpgo_cert
+
+using namespace dpgo_cert;
+
+extern "C" int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method, int max_block, int num,
+                                       const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new, double *delta,
+                                       double *cov_diag, double *cov_pairs, double *xi, double *xi_post, double *scalars,
+                                       dpgo_covariance_t *res) {
+  return linear_update_call(t, T, method, max_block, num, closures, num_pairs, pairs, T_new, delta, cov_diag, cov_pairs, xi, xi_post, scalars,
+                            res, false);
+}
+
+extern "C" int dpgo_team_linear_update_solved(dpgo_team_t *t, const double *T, int method, int max_block, int num,
+                                              const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
+                                              double *delta, double *cov_diag, double *cov_pairs, double *xi, double *xi_post,
+                                              double *scalars, dpgo_covariance_t *res) {
+  return linear_update_call(t, T, method, max_block, num, closures, num_pairs, pairs, T_new, delta, cov_diag, cov_pairs, xi, xi_post, scalars,
+                            res, true);
 }

@@ -550,6 +550,48 @@ int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method /* DPGO_
                             const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
                             double *delta /* 6 N */, double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_post,
                             double *scalars /* d2_joint, logdet_M, logdet_R */, dpgo_covariance_t *res);
+/* ---- the estimate's covariance applied to vectors (csrc/covariance_apply.hip, covariance_apply.h) ----
+ * X = Sigma V, which is the solve H_red X_red = V_red on the factors a covariance path holds, without a block of Sigma: the
+ * covariance of any linear function of the trajectory, B = Sigma A^T for any set of measurements, a Newton step -Sigma g.
+ *   V, X           6 N x num_cols, column-major with leading dimension 6 N.  Rows 6 p .. 6 p + 5 belong to team pose p in the
+ *                  perturbation of dpgo_team_marginal_covariances: rotation first and in the body frame, translation in the
+ *                  world frame, pose 0 fixed.  Sigma is the full 6 N x 6 N covariance whose rows and columns of pose 0 are
+ *                  zero: the six rows of pose 0 of V are not read, those of X are zero bits.
+ *   DPGO_GATE_NESTED  on the plan of dpgo_team_covariance_nested_plan at max_block, whether or not a robot is split (this call
+ *                  does not delegate to the Schur path: an unsplit plan's blocks are the robots' interiors, and one robot
+ *                  below max_block is one block with an empty separator).  With v_b the rows of block b, v_S the separator's:
+ *                    u_b = C_b v_b (while C_b is live in its batch),  r_S = v_S - sum_b scatter_{N_b}(W_b^T v_b) (block order),
+ *                    x_S = Sigma_SS r_S,  x_b = u_b - W_b x_S[N_b].
+ *   DPGO_GATE_DENSE   X_red = G V_red, one product with the explicit inverse.
+ *   DPGO_GATE_SCHUR   refused: DPGO_GATE_NESTED with no robot split has the Schur path's sets.
+ * The products are 64 x 64 fp64 matrix-core tiles with row maps on the B operand and on C (a row r of a mapped operand is row
+ * 6 pose[r / 6] + r mod 6 of V or X), so v_b is read straight out of V and x_b written straight into X.  Every element's sum
+ * runs over k in index order; W_b^T v_b goes through a temporary that is subtracted from r_S one launch per block, in block
+ * order; no floating-point atomics: two calls give the same bytes.
+ * Bytes on the device beside what the path needs for zero pairs:
+ *   dense    2 x 8 x 6 N x num_cols (V and X)
+ *   nested   8 num_cols (12 N + 6 |S|) (V, X and r_S; x_S is written straight into X) + 8 num_cols K_b per block in the batch
+ *            workspace (the temporaries; they are cut into batches with the rest of it) + 64 (3 blocks + 1) of product records
+ *            + 4 (sum_b |N_b| + |S|) of row maps.
+ * Refused with DPGO_ERR and a message that begins "covariance_apply:", before any device work: a NULL among t, T, V, X, res;
+ * num_cols <= 0; an unknown method; DPGO_GATE_SCHUR; V and X that do not fit the free device memory (decided before V is
+ * read), with the bytes named; an entry of V outside pose 0's rows that is not finite.  The refusals of the chosen
+ * covariance path (T outside SE(3), a weighted graph not joined to pose 0, its bytes with the apply's beside them, a
+ * non-positive pivot) carry over in their own words.  A refused call leaves X untouched and *res all zero.  *res: the path's
+ * record.  Changes no solver state.  One team only: all robots local and INITIALIZED. */
+int dpgo_team_covariance_apply(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */,
+                               int num_cols, const double *V, double *X, dpgo_covariance_t *res);
+/* dpgo_team_linear_update on that solve: the same arguments, outputs and refusals, but the covariance path is asked for the
+ * caller's own pairs alone (the diagonal blocks are staged anyway) and forms B = Sigma A^T itself, from V = A^T written on the
+ * device (J_i^T and J_j^T of closure k in column block k at the rows of its endpoints, pose 0's rows zero).  B is not formed
+ * from N m extracted blocks; M onward is computed as in dpgo_team_linear_update on that B.  The sums of B come in another
+ * order, so the outputs agree with dpgo_team_linear_update's to round-off, not bitwise; two calls give the same bytes.
+ * DPGO_GATE_SCHUR is refused (DPGO_GATE_NESTED with no robot split has the Schur path's sets).  Bytes: the caller's pair
+ * blocks, U (288 N K), the three matrices of order 6 K, and dpgo_team_covariance_apply's for num_cols = 6 K. */
+int dpgo_team_linear_update_solved(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block, int num,
+                                   const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
+                                   double *delta /* 6 N */, double *cov_diag /* 36 N */, double *cov_pairs, double *xi,
+                                   double *xi_post, double *scalars /* d2_joint, logdet_M, logdet_R */, dpgo_covariance_t *res);
 /* ---- measurements removed or down-weighted in the estimate and its covariances, no re-solve (csrc/linear_removal.hip;
  * DESIGN.md 5l) ----
  * The counterpart of dpgo_team_linear_update for weight taken OUT of the graph.  num = K records of one team are in the
