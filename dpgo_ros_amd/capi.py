@@ -92,6 +92,12 @@ class Covariance(C.Structure):
                 % (self.n, self.logdet, self.min_pivot, self.max_pivot, self.seconds_assemble, self.seconds_invert))
 
 
+class Refine(C.Structure):
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("f0", C.c_double), ("f", C.c_double), ("grad_inf0", C.c_double),
+                ("grad_inf", C.c_double)]
+
+
+REFINE_STATUS = ("converged", "max_iters", "indefinite", "no_descent")  # DPGO_REFINE_*
 METHOD_RTR, METHOD_RGD = 0, 1
 COST_L2, COST_L1, COST_HUBER, COST_TLS, COST_GM, COST_GNC_TLS = 0, 1, 2, 3, 4, 5
 WEIGHT_LIBRARY, WEIGHT_WRAPPER = 0, 1
@@ -133,7 +139,7 @@ dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
 dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal
 dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across
-dpgo_team_covariance_apply dpgo_team_linear_update_solved""".split()
+dpgo_team_covariance_apply dpgo_team_linear_update_solved dpgo_team_refine""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1163,6 +1169,41 @@ class Team:
              "covariance_apply")
         return res, X
 
+    def refine(self, T=None, method=None, max_block=None, max_iters=10, grad_tol=1e-8, armijo=1e-4, ladder=8):
+        """T refined to a critical point of the SE(3) cost by Newton steps on Sigma: what covariances, the gates,
+        audit, select_closures, linear_update, linear_removal and covariance_apply assume of their T.  Every iteration forms the
+        gradient of g(xi) = f(T [+] xi) (the perturbation of covariances, pose 0 fixed), the cost and |g|_inf on the device,
+        stops at |g|_inf <= grad_tol, else takes X = Sigma g from one covariance path (method "dense", the default, or "nested"
+        with max_block; "schur" raises DpgoError as in covariance_apply) and the first step length 2^-l, l < ladder, with
+        f_l <= f - armijo 2^-l g^T X up to the rounding of the cost's sum.  T as in covariances (None: the rounding of the
+        current iterate).  A polisher, not a solver: a T at which the Hessian is not positive definite raises DpgoError with the
+        path's message ("not a minimum"); there is no Levenberg shift.  Returns dict(T, status: "converged" | "max_iters" |
+        "indefinite" (a later iterate lost positive definiteness: T is the last good one) | "no_descent" (no step length
+        passed), iterations, f0, f, grad_inf0, grad_inf, history=dict(f, grad_inf: iterations + 1 entries; alpha, decrement =
+        g^T Sigma g, pivot_min: one entry per path that ran, alpha NaN where no step was taken), covariance: the last path's
+        record).  A T that meets grad_tol comes back bit for bit with iterations 0.  Two calls give the same bytes.  One team
+        only.  Changes no solver state."""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("refine: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("refine: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        rows = max(int(max_iters), 0) + 1
+        T_out, hist, out, res = np.zeros(12 * N), np.zeros((rows, 5)), Refine(), Covariance()
+        _chk(lib().dpgo_team_refine(self.h, _d(T), code, int(max_block or 0), int(max_iters), C.c_double(grad_tol),
+                                    C.c_double(armijo), int(ladder), _d(T_out), _d(hist), C.byref(out), C.byref(res)), "refine")
+        k = out.iterations
+        ran = int(np.count_nonzero(~np.isnan(hist[:, 3])))
+        return dict(T=T_out, status=REFINE_STATUS[out.status], iterations=k, f0=out.f0, f=out.f, grad_inf0=out.grad_inf0,
+                    grad_inf=out.grad_inf,
+                    history=dict(f=hist[:k + 1, 0].copy(), grad_inf=hist[:k + 1, 1].copy(), alpha=hist[:ran, 2].copy(),
+                                 decrement=hist[:ran, 3].copy(), pivot_min=hist[:ran, 4].copy()),
+                    covariance=res)
+
     @staticmethod
     def _across_check(what, method, max_block):
         """the arguments a per-record call cannot take with a transport: ValueError before any transport call"""
@@ -1754,16 +1795,23 @@ def _staircase(meas, params, r0, r_max, eta, T, X0, iters, first_iters, alpha0, 
 
 def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iters=20, first_iters=None,
                     refine_translations=True, certify_kw=None, device=0, covariances=False, covariance_method="dense",
-                    covariance_max_block=None, audit=False):
+                    covariance_max_block=None, audit=False, refine=False):
     """End to end: the Riemannian staircase, then the SE-Sync rounding of its final point (Team.round on the final team).
     Returns dict(T=trajectory, 12 doubles per pose in team order anchored at the first pose, r=final rank, ranks,
     certificate, rounding=Rounding, f_relaxed, f_rounded, gap_rel, escape_costs).  gap_rel = (f_rounded - f_relaxed) /
     f_relaxed bounds the relative suboptimality of T (up to the certificate's eta) when the point is certified; it is None
     otherwise.  covariances=True adds covariances=(Covariance, diag[N, 6, 6]): Team.covariances of the final team at T by
     covariance_method ("dense", "schur", or "nested" with covariance_max_block).  audit=True adds audit=Team.audit() of the final
-    team at T, its own measurements at their final weights, by the same covariance_method / covariance_max_block."""
+    team at T, its own measurements at their final weights, by the same covariance_method / covariance_max_block.
+    refine=True refines the rounded T to a critical point on SE(3) (Team.refine at its defaults, on the dense path or, for
+    covariance_method "schur" / "nested", the nested one at covariance_max_block: the Schur path has no apply) and adds refine=its dict; T, the covariances and the audit are then
+    taken at the refined T, while rounding and f_rounded stay those of the rounded point."""
     def round_final(team, out):
         out["rounding"], out["T"] = team.round(refine_translations=refine_translations)
+        if refine:
+            out["refine"] = team.refine(out["T"], method="dense" if covariance_method == "dense" else "nested",
+                                        max_block=covariance_max_block)
+            out["T"] = out["refine"]["T"]
         if covariances:
             if covariance_method == "nested":
                 out["covariances"] = team.covariances_nested(out["T"], max_block=covariance_max_block)[:2]
@@ -1782,4 +1830,6 @@ def solve_certified(meas, params, r0=5, r_max=8, eta=1e-6, T=None, X0=None, iter
         res["covariances"] = out["covariances"]
     if audit:
         res["audit"] = out["audit"]
+    if refine:
+        res["refine"] = out["refine"]
     return res

@@ -629,6 +629,42 @@ int dpgo_team_linear_removal(dpgo_team_t *t, const double *T, int method /* DPGO
                              double min_redundancy, int num_pairs, const int *pairs, double *T_new, double *delta /* 6 N */,
                              double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_loo, double *pivot_min /* num */,
                              double *scalars /* d2_joint, logdet_N, logdet_R, pivot_min_joint */, dpgo_covariance_t *res);
+/* ---- a trajectory refined to a critical point of the SE(3) cost by Newton steps on Sigma (csrc/refine.hip) ----
+ * The covariance calls take Sigma = H_red^-1 for the Laplace approximation at a minimum; this call puts T on one.  With
+ * g(xi) = f(T [+] xi), the perturbation of dpgo_team_marginal_covariances and pose 0 held fixed, every iteration forms on the
+ * device the gradient g = J^T vec(T Q) (six numbers per pose), the cost f as the sum of the measurements' terms and |g|_inf,
+ * stops when |g|_inf <= grad_tol, else runs ONE covariance path (method, max_block as in dpgo_team_covariance_apply) whose
+ * right-hand side is g, so that X = Sigma g comes from the path's factors, writes the `ladder` trial trajectories
+ * T [+] (-2^-l X), l = 0 .. ladder - 1, evaluates their costs in one pass and takes the first l with
+ *   f_l <= f - armijo 2^-l g^T X + eps_f,   eps_f = (24 + ceil(measurements / 256)) 2^-53 f
+ * (the rounding of the cost's sum, whose terms are not negative).  A polisher, not a solver: H_red must be positive definite
+ * at every iterate, and there is no Levenberg shift.
+ * status: DPGO_REFINE_CONVERGED |g|_inf <= grad_tol;  DPGO_REFINE_MAX_ITERS;  DPGO_REFINE_INDEFINITE a pivot of the path was
+ * not positive at a later iterate: T_out is the last good iterate;  DPGO_REFINE_NO_DESCENT no entry of the ladder passed:
+ * T_out is the iterate it started from.
+ * T_out: 12 N doubles (may be T).  A T that already meets grad_tol comes back bit for bit with iterations = 0.
+ * history: 5 (max_iters + 1) doubles, row k = [f, |g|_inf at iterate k; alpha, decrement g^T Sigma g, the path's smallest pivot
+ * of the step taken from it]; what was not computed is NaN.  *res: the record of the last path that succeeded (zero: none ran).
+ * Refused with DPGO_ERR and a message that begins "refine:", before any device work, T_out, history untouched and *out, *res
+ * zero: a NULL argument; max_iters < 0; ladder outside [1, 32]; grad_tol not positive; armijo outside (0, 1); an unknown
+ * method; DPGO_GATE_SCHUR (in the words of dpgo_team_covariance_apply); a pose of T outside SE(3).  A pivot that is not positive
+ * at the input T is refused with the path's message behind "refine: "; the other refusals of the path (its bytes, a graph not
+ * joined to pose 0) carry over in their own words.  Bytes on the device beside the path's (one column of V and X): 8 x 12 N
+ * (ladder + 2) + 8 x 6 N + 128 per measurement.  Fixed-order sums, no floating-point atomics: two calls give the same bytes.
+ * Changes no solver state.  One team only: all robots local and INITIALIZED. */
+#define DPGO_REFINE_CONVERGED 0
+#define DPGO_REFINE_MAX_ITERS 1
+#define DPGO_REFINE_INDEFINITE 2
+#define DPGO_REFINE_NO_DESCENT 3
+typedef struct {
+  int status;     /* DPGO_REFINE_* */
+  int iterations; /* steps taken */
+  double f0, f;   /* the cost at the input and at T_out */
+  double grad_inf0, grad_inf;
+} dpgo_refine_t;
+int dpgo_team_refine(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */, int max_iters,
+                     double grad_tol, double armijo, int ladder, double *T_out /* 12 N */, double *history /* 5 (max_iters + 1) */,
+                     dpgo_refine_t *out, dpgo_covariance_t *res);
 /* ---- the most informative candidate closures under a budget (csrc/select.hip) ----
  * Asked before anything is measured: of num = P proposed pose pairs of one team, which `budget` would tighten the estimate
  * most.  T, Sigma, the perturbation, J_i, J_j and Sigma_meas are those of dpgo_team_gate_candidates, A, R and
