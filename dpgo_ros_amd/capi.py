@@ -139,7 +139,7 @@ dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
 dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal
 dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across
-dpgo_team_covariance_apply dpgo_team_linear_update_solved dpgo_team_refine""".split()
+dpgo_team_covariance_apply dpgo_team_linear_update_solved dpgo_team_refine dpgo_team_covariance_apply_across""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1138,7 +1138,7 @@ class Team:
              "marginal_covariances_nested")
         return res, diag, cross
 
-    def covariance_apply(self, V, T=None, method=None, max_block=None):
+    def covariance_apply(self, V, T=None, method=None, max_block=None, transport=None, owner_of_robot=None):
         """X = Sigma V, the estimate's covariance applied to vectors: the solve H_red X_red = V_red on the factors
         of a covariance path, without a block of Sigma.  V: [6 N, m] (or [6 N]: one column); rows 6 p .. 6 p + 5 belong to team
         pose p in the perturbation of covariances (rotation first, body frame; translation, world frame; pose 0 fixed).  Sigma
@@ -1146,12 +1146,22 @@ class Team:
         T as in covariances (None: the rounding of the current iterate).  method: "dense" (the default) multiplies by the
         explicit inverse; "nested" eliminates on covariance_plan(max_block)'s sets, split or not; "schur" raises DpgoError
         ("nested" with no robot split has its sets).  Returns (Covariance, X[6 N, m]).  Two calls give the same bytes.  Raises
-        DpgoError as covariances does, for a V that is not finite, and for V and X that do not fit the device.  One team only.
-        Changes no solver state."""
+        DpgoError as covariances does, for a V that is not finite, and for V and X that do not fit the device.  Changes no
+        solver state.
+        With a transport (a team split across participants, owner_of_robot as for covariances): the Schur path is the only
+        one (method None or "schur"; anything else, or a max_block, raises ValueError before any transport call).  T, V and
+        X are this team's poses in team order, V [6 N_loc, m] with the same m on every participant; the fixed pose is the
+        problem's pose 0, robot 0's first, whose rows are not read and come back zero on the participant that holds it.  T
+        None: the rounding across.  Returns (Covariance, X_local); every row is the same bits whatever the split, and the
+        scalars are identical on every participant.  A ValueError (V's shape, T's size) is raised on this participant alone
+        before the library is called, as in the other calls across teams: the others wait in the agreement record until their
+        transport times out, so check shapes before a collective call."""
         if method not in (None, "dense", "schur", "nested"):
             raise ValueError("covariance_apply: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
         N = int(sum(self.agents[i].n for i in self.ids))
-        if T is None:
+        if transport is not None:
+            T = self._across_args("covariance_apply", T, method, max_block, transport, owner_of_robot)
+        elif T is None:
             T = self.round()[1]
         T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
         if T.size != 12 * N:
@@ -1164,6 +1174,11 @@ class Team:
         Vf = np.asfortranarray(V)
         X = np.zeros(Vf.shape, order="F")
         res = Covariance()
+        if transport is not None:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_covariance_apply_across(self.h, C.byref(transport.struct), _d(own), _d(T), Vf.shape[1], _d(Vf),
+                                                         _d(X), C.byref(res)), "covariance_apply_across")
+            return res, X
         code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         _chk(lib().dpgo_team_covariance_apply(self.h, _d(T), code, int(max_block or 0), Vf.shape[1], _d(Vf), _d(X), C.byref(res)),
              "covariance_apply")

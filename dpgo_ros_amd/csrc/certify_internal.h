@@ -185,11 +185,17 @@ struct CovEpilogue {
 // CovFrame::begin has T on the device -- rhs() queues on `stream` whatever writes every element of V outside pose 0's rows,
 // which are not read -- forms X = Sigma V from its own factors without a block of Sigma, and sets X before it runs the
 // epilogue: the pointer stays valid as long as the staged blocks do.  Pose 0's rows of X are zero bits.
+// Across teams (covariance_schur_across, which has no CovEpilogue) N is this participant's N_loc and pose 0 the problem's, the
+// agreement record carries num_cols, and the path calls taken() once X is set, before its closing status word: taken() queues
+// on `stream` whatever reads X; the path drains the stream.  argerr: this participant's own refusal, which the others learn from
+// the agreement record; memerr: V and X alone exceed the device (V was then not read), told as the path's memory refusal.
 struct CovApply {
   int num_cols = 0;
   double *X = nullptr;
   double ms_products = 0.0, flops = 0.0;  // the apply's own products, for the caller's DPGO_TIMING line
+  std::string argerr, memerr;
   virtual int rhs(const double *Td, int N, double *V, hipStream_t stream) = 0;
+  virtual int taken(int /*N*/, hipStream_t /*stream*/) { return DPGO_OK; }
   virtual ~CovApply() = default;
 };
 
@@ -243,9 +249,10 @@ struct AcrossEpilogue {
 };
 
 // the same over a split team (dpgo_team_marginal_covariances_across; covariance_schur.hip).  epi: the step behind the blocks
-// (num_pairs and pairs are then epi's; cov_diag and cov_pairs are not touched and may be null, only res is filled)
+// (num_pairs and pairs are then epi's; cov_diag and cov_pairs are not touched and may be null, only res is filled).  app: Sigma
+// applied to vectors beside the blocks (dpgo_team_covariance_apply_across; no epi, no pairs, cov_diag may be null)
 int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
                             const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res,
-                            AcrossEpilogue *epi = nullptr);
+                            AcrossEpilogue *epi = nullptr, CovApply *app = nullptr);
 
 }  // namespace dpgo_cert

@@ -126,6 +126,11 @@ void launch_apply_gather(hipStream_t s, const double *V, size_t ldv, const int *
 // R[6 nb[i / 6] + i mod 6, c] -= P[i, c], P K x cols with leading dimension K, R with leading dimension ldr.  One launch per
 // block, in block order on one stream: two blocks that meet in a row of R subtract from it in that order
 void launch_apply_scatter_sub(hipStream_t s, double *R, size_t ldr, const double *P, int K, int cols, const int *nb);
+// D[drow(i), c] = S[srow(i), c] - P[i, c] over K rows and `cols` columns: S and D with leading dimensions lds and ldd and rows
+// through the pose lists smap and dmap (null: the identity), P K x cols with leading dimension K (null: nothing is subtracted).
+// Across teams: r_a = v_{S_a} - W_a^T v_a out of V into the robot's rows of r_S, and X[S_a] = x_S[S_a]
+void launch_apply_rows_sub(hipStream_t s, const double *S, size_t lds, const int *smap, const double *P, double *D, size_t ldd,
+                           const int *dmap, int K, int cols);
 // the flops of a list of items
 double apply_flops(const dpgo::ApplyItem *it, int count);
 

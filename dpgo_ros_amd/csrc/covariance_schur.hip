@@ -32,6 +32,7 @@
 #include <map>
 #include <tuple>
 
+#include "covariance_apply.h"
 #include "covariance_extract.h"
 
 namespace dpgo {
@@ -154,13 +155,34 @@ static double schur_bytes(dpgo_team_t *t, const SchurPartition &P, int nS, int k
   return 8.0 * (3.0 * M * M + ms * ms + w_all + w_max) + small;
 }
 
-static int schur_fits(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax, int num_pairs, const char *what, std::string &msg) {
+// the bytes Sigma applied to `cols` vectors adds on a participant ("across teams"): V and X (8 x 6 N_loc cols
+// each), r_S and x_S (8 x 6 |S| cols each, the separator of the whole problem), the temporary W_a^T v_a (8 x cols x max_a K_a
+// over the robots here), 64 bytes per product record (three per robot and one) and 4 per public pose here (the row maps)
+static double schur_apply_bytes(const SchurPartition &P, int nS, int cols) {
+  int kloc = 0;
+  for (int k = 0; k < P.na; ++k) kloc = std::max(kloc, 6 * (P.sep_off[k + 1] - P.sep_off[k]));
+  return 8.0 * (double)cols * (12.0 * P.N + 12.0 * nS + kloc) + (double)sizeof(ApplyItem) * (3.0 * P.na + 1.0) + 4.0 * P.nS;
+}
+
+// cols > 0: with Sigma applied to that many vectors
+static int schur_fits(dpgo_team_t *t, const SchurPartition &P, int nS, int kmax, int num_pairs, const char *what, std::string &msg,
+                      int cols = 0) {
   std::string who;
   const double need = schur_bytes(t, P, nS, kmax, num_pairs, who);
   double avail = 0.0;
   if (!cov_device_avail(t, &avail)) { msg = std::string(what) + ": hipMemGetInfo failed"; return -1; }
-  if (need <= avail) return 0;
   char buf[400];
+  if (cols > 0) {
+    const double extra = schur_apply_bytes(P, nS, cols);
+    if (need + extra <= avail) return 0;
+    std::snprintf(buf, sizeof buf,
+                  "%s: the Schur path needs %.0f bytes, set by %s, and V, X, r_S, x_S and the temporary of %d columns %.0f more (8 x "
+                  "num_cols x (12 N + 12 |S| + max K), N = %d, |S| = %d), %.0f are available on the device",
+                  what, need, who.c_str(), cols, extra, P.N, nS, avail);
+    msg = buf;
+    return -1;
+  }
+  if (need <= avail) return 0;
   std::snprintf(buf, sizeof buf,
                 "%s: the Schur path needs %.0f bytes, set by %s, %.0f are available on the device; a team of more robots has "
                 "smaller interiors and needs less",
@@ -189,12 +211,27 @@ struct SchurDev {
   }
 };
 
+// Sigma applied to vectors beside one robot's step ("across teams"): the records of u_a = C_a v_a (into X) and
+// t_a = W_a^T v_a (into tmp, K x cols) on the device and on the host, and where r_a = v_{S_a} - t_a goes: the robot's rows of
+// r_S (leading dimension ldr), read out of V through `pub`, the team poses of its public poses
+struct SchurApply {
+  const ApplyItem *u_d, *t_d, *u_h, *t_h;
+  const double *V;
+  size_t ldv, ldr;
+  const int *pub;
+  double *tmp, *r;
+  int cols;
+  CovApply *app;
+  std::vector<size_t> *ends;  // the marks that END an interval of the apply's own launches
+};
+
 // One robot: H_II and B assembled (lists `lii`, `lb`), C = H_II^-1 into D.M, W = C B, Sd -= B^T W (Sd: the
 // robot's diagonal block of the separator, leading dimension lds), the statistics of the factor into stat[0 .. 2], the blocks
 // of C named by `keep` (its entries name the robot's set of D.tab) into keepd.  DPGO_OK, DPGO_ERR (message set), or row + 1 of a non-positive pivot.  A single team and
-// every participant of a split team come through here with the same shapes: the same bits.
+// every participant of a split team come through here with the same shapes: the same bits.  ap: behind W = C B, while C is live
+// in D.M, also u_a, t_a and r_a of SchurApply; without one the launches are the ones above and no other.
 static int schur_robot_step(SchurDev &D, SchurMarks &marks, int robot_id, int lii, int lb, int ni, int K, double *W, double *Sd, int lds,
-                            const std::vector<CovBlk> &keep, double *keepd, double *stat) {
+                            const std::vector<CovBlk> &keep, double *keepd, double *stat, const SchurApply *ap = nullptr) {
   hipStream_t s = D.s;
   HIPC(hipMemsetAsync(D.A.p, 0, sizeof(double) * (size_t)ni * ni, s));
   D.assemble(lii, D.A.p, ni);
@@ -217,6 +254,15 @@ static int schur_robot_step(SchurDev &D, SchurMarks &marks, int robot_id, int li
   marks.note.back() = "robot " + std::to_string(robot_id) + ": W = C B (" + std::to_string(ni) + " x " + std::to_string(K) + " x " +
                       std::to_string(ni) + ") and B^T W (" + std::to_string(K) + " x " + std::to_string(K) + " x " + std::to_string(ni) + ")";
   marks.flops.back() = 2.0 * ni * (double)ni * K + 2.0 * K * (double)K * ni;
+  if (ap) {
+    launch_apply_gemm(s, false, ap->u_d, ap->u_h, 1, false);  // u_a = C_a v_a, into X
+    launch_apply_gemm(s, true, ap->t_d, ap->t_h, 1, false);   // t_a = W_a^T v_a
+    launch_apply_rows_sub(s, ap->V, ap->ldv, ap->pub, ap->tmp, ap->r, ap->ldr, nullptr, K, ap->cols);  // r_a = v_{S_a} - t_a
+    HIPC(hipGetLastError());
+    MARK(-1);
+    ap->ends->push_back(marks.ev.size() - 1);
+    ap->app->flops += apply_flops(ap->u_h, 1) + apply_flops(ap->t_h, 1);
+  }
   // (keep is never empty: the diagonal blocks)
   HIPC(hipMemcpyAsync(D.blk.p, keep.data(), sizeof(CovBlk) * keep.size(), hipMemcpyHostToDevice, s));
   launch_ext_keep(s, D.tab.p, D.blk.p, (int)keep.size(), keepd);
@@ -449,12 +495,15 @@ enum { XF_OK = 0, XF_PIVOT = 1, XF_MEMORY = 2, XF_LOCAL = 3 };
 }  // namespace
 
 int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
-                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, AcrossEpilogue *epi) {
-  const char *what = epi ? epi->name : "marginal_covariances_across";
+                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, AcrossEpilogue *epi,
+                            CovApply *app) {
+  const char *what = epi ? epi->name : app ? "covariance_apply_across" : "marginal_covariances_across";
   if (res) std::memset(res, 0, sizeof *res);
+  const int cols = app ? app->num_cols : 0;
   std::string argerr;
   if (epi && !epi->argerr.empty()) argerr = epi->argerr;
-  else if (!T || !res || (!epi && (!cov_diag || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))))) argerr = "null argument";
+  else if (app && !app->argerr.empty()) argerr = app->argerr;
+  else if (!T || !res || (!epi && ((!cov_diag && !app) || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))))) argerr = "null argument";
   else if (flags != DPGO_COV_SCHUR) argerr = "flags must be DPGO_COV_SCHUR";
   else if (t) {
     int n = 0;
@@ -468,11 +517,13 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     }
   }
   Across x;
-  const double agree_num = epi ? epi->num : (double)num_pairs;
+  // (op 6, Sigma applied to vectors: the first real field carries num_cols)
+  const double agree_num = epi ? epi->num : app ? (double)cols : (double)num_pairs;
   const double agree_hash = !argerr.empty() ? 0.0 : epi ? epi->hash : pair_hash(pairs, num_pairs);
-  if (x.begin(t, tr, owner, what, epi ? epi->op : 3, 3, flags, agree_num, agree_hash, 0, argerr.empty() ? nullptr : argerr.c_str())) {
+  if (x.begin(t, tr, owner, what, epi ? epi->op : app ? 6 : 3, 3, flags, agree_num, agree_hash, 0, argerr.empty() ? nullptr : argerr.c_str())) {
     // (a participant whose own records were refused says why in the words of the single team's call)
     if (epi && !epi->argerr.empty()) set_err(std::string(what) + ": " + epi->argerr);
+    else if (app && !app->argerr.empty()) set_err(std::string(what) + ": " + app->argerr);
     return DPGO_ERR;
   }
   // (from here on the participants agree on the owner table, the robots' sizes and the pair list)
@@ -501,6 +552,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   }
   const int N = P.N;
   if (NG < 2 && !epi) {  // (with an epilogue never: a record joins two different poses of the problem)
+    if (app) return x.finish() ? DPGO_ERR : DPGO_OK;  // (nothing is free: the caller's X is zero)
     std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
     if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
     return x.finish() ? DPGO_ERR : DPGO_OK;
@@ -628,9 +680,23 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   d_all = doff[na];
   int fcode = XF_OK, frobot = 0, fpose = 0, frow = 0;
   std::string fmsg;
-  if (!x.bad && schur_fits(t, P, nSp, kmax, num_pairs, what, fmsg)) { fcode = XF_MEMORY; }
+  // (V and X alone beyond the device: the caller has decided it without reading V, and says so in its own words)
+  if (!x.bad && app && !app->memerr.empty()) { fcode = XF_MEMORY; fmsg = std::string(what) + ": " + app->memerr; }
+  else if (!x.bad && schur_fits(t, P, nSp, kmax, num_pairs, what, fmsg, cols)) { fcode = XF_MEMORY; }
   SchurDev D;
   DevBuf<double> d_S, d_small, d_t, d_T, d_D, d_X, d_rows;
+  // Sigma applied to vectors ("across teams").  d_aV, d_aX: 6 N x cols; d_rS, d_xS: r_S and x_S of the whole
+  // problem, 6 |S| x cols; d_tmp: W_a^T v_a of the robot at hand; d_pub: the team poses of this participant's public poses
+  // (P.sep), a robot's row map a window of it.  Records: [0, na) u_a = C_a v_a, [na, 2 na) t_a = W_a^T v_a, [2 na, 3 na)
+  // x_a -= W_a x_S[S_a], 3 na: x_S = Sigma_SS r_S
+  DevBuf<double> d_aV, d_aX, d_rS, d_xS, d_tmp;
+  DevBuf<int> d_pub;
+  DevBuf<ApplyItem> d_app;
+  std::vector<ApplyItem> aitem(app ? 3 * (size_t)na + 1 : 0);
+  std::vector<size_t> app_marks, roff(na, 0);  // roff: a robot's r_a (K_a x cols) in this participant's part of allgather C, id order
+  size_t rlen = 0;
+  for (int k : byid) { roff[k] = rlen; rlen += (size_t)6 * gs[t->ag[k]->id] * cols; }
+  std::vector<double> h_ra;  // the r_a of the robots here, back from the device
   std::vector<DevBuf<double>> d_W(na);
   DevBuf<int> d_int;
   DevBuf<CovBlk> d_is;
@@ -660,6 +726,13 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
                D.blk.alloc(nblk) || d_is.alloc((size_t)num_pairs) || d_cross.alloc(ncrosspairs) || D.tab.alloc((size_t)na + 2 * ncrosspairs) ||
                d_t.alloc(cross_chunk * 6 * std::max(kmax, 1)) || d_T.alloc((size_t)12 * (N + halo_slots)) || d_D.alloc(d_all) ||
                d_X.alloc(36 * xb.size());
+    if (app && !bad) {
+      int kloc = 0;
+      for (int k = 0; k < na; ++k) kloc = std::max(kloc, 6 * (P.sep_off[k + 1] - P.sep_off[k]));
+      const size_t vx = (size_t)6 * N * cols, sx = (size_t)nS * cols;
+      bad = d_aV.alloc(vx) || d_aX.alloc(vx) || d_rS.alloc(sx) || d_xS.alloc(sx) || d_tmp.alloc((size_t)kloc * cols) || d_pub.upload(P.sep, s) ||
+            d_app.alloc(aitem.size());
+    }
     for (int k = 0; k < na && !bad; ++k) bad = d_W[k].alloc((size_t)36 * P.interior[k].size() * (size_t)(P.sep_off[k + 1] - P.sep_off[k])) != 0;
     if (bad) { set_err("device allocation failed"); return DPGO_ERR; }
     stat = d_small.p; keepd = stat + 4 * (size_t)(na + 1); outd = keepd + nout;
@@ -675,6 +748,19 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     HIPC(hipMemcpyAsync(D.tab.p, rob.data(), sizeof(CovBlock) * na, hipMemcpyHostToDevice, s));
     HIPC(hipMemsetAsync(stat, 0, sizeof(double) * small, s));
     if (d_all) HIPC(hipMemsetAsync(d_D.p, 0, sizeof(double) * d_all, s));
+    if (app) {
+      for (int k = 0; k < na; ++k) {
+        const int *poses = d_int.p + ipose_off[k];
+        const int ni = rob[k].ld, K = rob[k].K;
+        aitem[k] = {D.M.p, d_aV.p, d_aX.p, poses, poses, ni, 6 * N, 6 * N, ni, cols, ni};
+        aitem[na + k] = {d_W[k].p, d_aV.p, d_tmp.p, poses, nullptr, ni, 6 * N, K, K, cols, ni};
+        aitem[2 * na + k] = {d_W[k].p, d_xS.p + soff[k], d_aX.p, nullptr, poses, ni, nS, 6 * N, ni, cols, K};
+      }
+      aitem[3 * na] = {D.M.p, d_rS.p, d_xS.p, nullptr, nullptr, nS, nS, nS, nS, cols, nS};
+      HIPC(hipMemcpyAsync(d_app.p, aitem.data(), sizeof(ApplyItem) * aitem.size(), hipMemcpyHostToDevice, s));
+      HIPC(hipMemsetAsync(d_aX.p, 0, sizeof(double) * 6 * (size_t)N * cols, s));
+      if (app->rhs(d_T.p, N, d_aV.p, s)) return DPGO_ERR;
+    }
     MARK(-1);
     for (int k = 0; k < na; ++k) D.assemble(2 * na + k, d_D.p + doff[k], rob[k].K);
     D.assemble(3 * na, d_X.p, 6);
@@ -682,9 +768,15 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     MARK(0);
     for (int k : byid) {
       const int ni = rob[k].ld;
-      if (ni == 0) continue;
+      const int *pub = app ? d_pub.p + P.sep_off[k] : nullptr;
+      if (ni == 0) {  // (a robot with no interior pose: r_a = v_{S_a})
+        if (app) launch_apply_rows_sub(s, d_aV.p, (size_t)6 * N, pub, nullptr, d_rS.p + soff[k], (size_t)nS, nullptr, rob[k].K, cols);
+        continue;
+      }
+      const SchurApply ap{d_app.p + k, d_app.p + na + k, aitem.data() + k, aitem.data() + na + k, d_aV.p, (size_t)6 * N, (size_t)nS, pub,
+                          d_tmp.p, d_rS.p + soff[k], cols, app, &app_marks};
       const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_D.p + doff[k], rob[k].K, keep_list[k], keepd,
-                                     stat + 4 * k);
+                                     stat + 4 * k, app ? &ap : nullptr);
       if (f < 0) return DPGO_ERR;
       if (f > 0) {
         fcode = XF_PIVOT; frobot = t->ag[k]->id; frow = f - 1;
@@ -697,6 +789,14 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     if (d_all) HIPC(hipMemcpyAsync(hD.data(), d_D.p, sizeof(double) * d_all, hipMemcpyDeviceToHost, s));
     if (!xb.empty()) HIPC(hipMemcpyAsync(hX.data(), d_X.p, sizeof(double) * hX.size(), hipMemcpyDeviceToHost, s));
     HIPC(hipMemcpyAsync(hstat.data(), stat, sizeof(double) * hstat.size(), hipMemcpyDeviceToHost, s));
+    if (app) {  // the r_a of the robots here, K_a x cols each, in id order: this participant's part of allgather C
+      HIPC(hipGetLastError());
+      h_ra.resize(rlen);
+      for (int k : byid)
+        if (rob[k].K > 0)
+          HIPC(hipMemcpy2DAsync(h_ra.data() + roff[k], sizeof(double) * rob[k].K, d_rS.p + soff[k], sizeof(double) * nS, sizeof(double) * rob[k].K,
+                                cols, hipMemcpyDeviceToHost, s));
+    }
     HIPC(hipStreamSynchronize(s));
     return DPGO_OK;
   };
@@ -825,6 +925,14 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     rowoff[r] = clen[q];
     clen[q] += 36 * (size_t)gs[rows[r].robot];
   }
+  const size_t rows_max = *std::max_element(clen.begin(), clen.end());  // (the pair blocks and the rows: what hrows stages)
+  // Sigma applied to vectors: behind them every robot's r_a, K_a x cols, from its holder in id order
+  std::vector<size_t> rat(nr, 0);
+  for (int i = 0; app && i < nr; ++i) {
+    const int q = x.robot_holder[i];
+    rat[i] = clen[q];
+    clen[q] += (size_t)6 * gs[i] * cols;
+  }
   const size_t cmax = *std::max_element(clen.begin(), clen.end());
   std::vector<double> hout, hrows;
   std::vector<double> sstat(4, 0.0);
@@ -855,7 +963,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     HIPC(hipMemcpyAsync(hout.data(), outd, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
     if (nS > 0) HIPC(hipMemcpyAsync(sstat.data(), stat + 4 * na, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
     // the rows W_a[i,:] this participant holds, 6 x 6 s_a column-major each
-    hrows.assign(cmax, 0.0);
+    hrows.assign(rows_max, 0.0);
     for (size_t r = 0; r < rows.size(); ++r) {
       if (x.robot_holder[rows[r].robot] != x.rank) continue;
       const int lk = t->id2local.at(rows[r].robot);
@@ -876,6 +984,11 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     for (size_t r = 0; r < rows.size(); ++r)
       if (x.robot_holder[rows[r].robot] == x.rank)
         std::memcpy(gcv.data() + rowoff[r], hrows.data() + rowoff[r], sizeof(double) * 36 * (size_t)gs[rows[r].robot]);
+    for (int k : byid) {  // (app: robot a's r_a from its place in h_ra to its place in the record)
+      const int id = t->ag[k]->id;
+      const size_t len = (size_t)6 * gs[id] * cols;
+      if (app && len > 0) std::memcpy(gcv.data() + rat[id], h_ra.data() + roff[k], sizeof(double) * len);
+    }
   }
   if (x.gather(gcv, gall)) return x.fail();
   if (sfail > 0) {  // (deterministic: the same on every participant, and behind the allgather that would have told of a failure)
@@ -920,6 +1033,42 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     return DPGO_OK;
   };
   if (!x.bad && phase3()) x.fail_local(g_err);
+  // ---- Sigma applied to vectors, behind the separator's inverse (D.M = Sigma_SS).  r_S from the gathered r_a, the same bytes
+  // on every participant; x_S = Sigma_SS r_S, the whole of it, here; x_a = u_a - W_a x_S[S_a] and X[S_a] = x_S[S_a] for the
+  // robots here
+  auto phase_apply = [&]() -> int {
+    if (nS > 0) {
+      std::vector<double> hrS((size_t)nS * cols);
+      for (int i = 0; i < nr; ++i) {
+        const size_t w = (size_t)6 * gs[i];
+        const double *src = gall.data() + (size_t)x.robot_holder[i] * cmax + rat[i];
+        for (int c = 0; c < cols && w > 0; ++c)
+          std::memcpy(hrS.data() + (size_t)c * nS + (size_t)6 * gsoff[i], src + (size_t)c * w, sizeof(double) * w);
+      }
+      HIPC(hipMemcpyAsync(d_rS.p, hrS.data(), sizeof(double) * hrS.size(), hipMemcpyHostToDevice, s));
+      MARK(-1);
+      launch_apply_gemm(s, false, d_app.p + 3 * na, aitem.data() + 3 * na, 1, false);
+      for (int k : byid) {
+        launch_apply_gemm(s, false, d_app.p + 2 * na + k, aitem.data() + 2 * na + k, 1, true);
+        launch_apply_rows_sub(s, d_xS.p + soff[k], (size_t)nS, nullptr, nullptr, d_aX.p, (size_t)6 * N, d_pub.p + P.sep_off[k], rob[k].K, cols);
+        app->flops += apply_flops(aitem.data() + 2 * na + k, 1);
+      }
+      HIPC(hipGetLastError());
+      MARK(-1);
+      app_marks.push_back(marks.ev.size() - 1);
+      app->flops += apply_flops(aitem.data() + 3 * na, 1);
+      HIPC(hipStreamSynchronize(s));  // (hrS has been read)
+    }
+    app->X = d_aX.p;
+    if (app->taken(N, s)) return DPGO_ERR;
+    HIPC(hipStreamSynchronize(s));
+    for (size_t k : app_marks) {
+      float v = 0.f;
+      if (hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) == hipSuccess) app->ms_products += v;
+    }
+    return DPGO_OK;
+  };
+  if (app && !x.bad && phase_apply()) x.fail_local(g_err);
   // ---- the step behind the blocks (the gate, the audit).  Allgather D: per endpoint of the records, sorted by global pose,
   // 12 doubles of T and the 36 of its diagonal block from the participant that holds it, zeros from everyone else (pose 0's
   // block is zero with its holder too).  Then every participant holds the compact tables and runs all records itself.
@@ -970,7 +1119,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
                  "%s: rank %d of %d, n %lld, separator %d, largest interior here %d, assemble %.3f ms, factorisations "
                  "%.3f ms, products %.3f ms, separator inverse %.3f ms, extract %.3f ms, %lld allgathers, %lld exchanges\n",
                  what, x.rank, world, 6 * (NG - 1), nS, 6 * P.max_int, ms[0], ms[1], ms[2], ms[3], ms[4], x.n_allgather, x.n_exchange);
-  if (epi) return DPGO_OK;  // (the blocks stay here: the epilogue's outputs are the call's)
+  if (epi || app) return DPGO_OK;  // (the blocks stay here: the epilogue's outputs, or X, are the call's)
   std::memcpy(cov_diag, hout.data(), sizeof(double) * 36 * (size_t)N);
   if (num_pairs > 0) std::memcpy(cov_pairs, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
   return DPGO_OK;

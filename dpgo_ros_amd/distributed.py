@@ -695,3 +695,38 @@ def audit(backend_or_team, dist, owner_of_robot, measurements=None, **kw):
         return None
     team, tr, own = p
     return team.audit(measurements, transport=tr, owner_of_robot=own, **kw)
+
+
+def covariance_apply(backend_or_team, dist, owner_of_robot, V, T=None, gather=False):
+    """Team.covariance_apply of an estimate split across ranks (one team per rank): V holds this rank's rows, [6 N_loc, m] in
+    team order (or [6 N_loc]: one column), the same m on every rank; T this rank's poses (None: the rounding across).
+    (Covariance, X) with this rank's rows of X = Sigma V; with gather=True X of the whole problem instead, [6 N, m] in global
+    pose order (robots by id) and identical on every rank: one allgather of the local rows behind one of their lengths, the
+    way certify_and_round gathers the diagonal blocks.  A V or T of the wrong shape raises ValueError on this rank before the
+    library is called: the other ranks then wait in the agreement record until the transport gives up, as for the other
+    calls across ranks.  None on a rank that owns no robot."""
+    p = _participants(backend_or_team, dist, owner_of_robot)
+    if p is None:
+        return None
+    team, tr, own = p
+    res, X = team.covariance_apply(V, T=T, transport=tr, owner_of_robot=own)
+    if not gather:
+        return res, X
+    # every rank's rows robot by robot, padded to one length, then placed by robot id
+    m = X.shape[1]
+    ids = list(team.ids)
+    head = np.array([len(ids)] + ids + [team.agents[i].n for i in ids], dtype=np.float64)
+    rows = np.ascontiguousarray(X).reshape(-1)  # (row-major: a robot's 6 n rows of m entries are one run)
+    sizes = tr.allgather(np.array([head.size + rows.size], dtype=np.float64)).astype(int)
+    mine = np.zeros(int(sizes.max()))
+    mine[:head.size], mine[head.size:head.size + rows.size] = head, rows
+    allr = tr.allgather(mine).reshape(tr.world, mine.size)
+    blocks = {}
+    for q in range(tr.world):
+        k = int(allr[q, 0])
+        rid, rn = allr[q, 1:1 + k].astype(int), allr[q, 1 + k:1 + 2 * k].astype(int)
+        o = 1 + 2 * k
+        for i, n in zip(rid, rn):
+            blocks[int(i)] = allr[q, o:o + 6 * n * m].reshape(6 * n, m)
+            o += 6 * n * m
+    return res, np.concatenate([blocks[i] for i in sorted(blocks)], axis=0)

@@ -578,7 +578,7 @@ int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method /* DPGO_
  * read), with the bytes named; an entry of V outside pose 0's rows that is not finite.  The refusals of the chosen
  * covariance path (T outside SE(3), a weighted graph not joined to pose 0, its bytes with the apply's beside them, a
  * non-positive pivot) carry over in their own words.  A refused call leaves X untouched and *res all zero.  *res: the path's
- * record.  Changes no solver state.  One team only: all robots local and INITIALIZED. */
+ * record.  Changes no solver state.  One team: all robots local and INITIALIZED (a split team: the call below). */
 int dpgo_team_covariance_apply(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block /* NESTED only */,
                                int num_cols, const double *V, double *X, dpgo_covariance_t *res);
 /* dpgo_team_linear_update on that solve: the same arguments, outputs and refusals, but the covariance path is asked for the
@@ -814,6 +814,37 @@ int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_transport_t *
                                         int num, const dpgo_measurement_t *meas, double min_redundancy, double *xi /* 6 num */,
                                         double *xi_loo /* 6 num */, double *d2 /* num */, double *rho /* num */, double *pmin /* num */,
                                         double *sigma_loo /* 36 num or NULL */, dpgo_covariance_t *res);
+/* dpgo_team_covariance_apply over a team split across participants, on the path of dpgo_team_marginal_covariances_across,
+ * whose fixed pose, global numbering and robot-wise sets it has; there is no method: the Schur path is the only one.  Every
+ * participant calls.
+ *   T              this team's poses in team order, 12 N_loc doubles.
+ *   V, X           6 N_loc x num_cols, column-major with leading dimension 6 N_loc; rows 6 p .. 6 p + 5 belong to team pose p.
+ *                  On the participant that holds robot 0 the rows of V of the problem's pose 0 are not read and those of X
+ *                  are zero bits.  num_cols is the same on every participant.
+ * For the robots a held here, in id order, with I_a the interior and S_a the public poses, v_a = V[I_a]:
+ *     u_a = C_a v_a (while C_a is live in the robot's step),  r_a = v_{S_a} - W_a^T v_a (no interior pose: r_a = v_{S_a});
+ *     r_S = the r_a of every robot of the problem at the robot's place in the global separator (gathered);
+ *     x_S = Sigma_SS r_S (on every participant, from identical bytes),  x_a = u_a - W_a x_S[S_a],  X[I_a] = x_a,  X[S_a] = x_S[S_a].
+ * The products are the tiles of dpgo_team_covariance_apply with their row maps; one more kernel forms r_a out of V into the
+ * robot's rows of r_S and copies x_S[S_a] into X.  No floating-point atomics.  The r_a ride in the record of the path's third
+ * allgather (the owned pair blocks, empty here): the call makes exactly the transport calls of
+ * dpgo_team_marginal_covariances_across with zero pairs.  Every row of X is the same bits whatever the split, one participant
+ * that holds every robot included, and two calls give the same bytes.  It is not bitwise DPGO_GATE_NESTED of the single
+ * team's call: the interior inverses take another route.
+ * Bytes on the device beside what the path needs for zero pairs: 8 num_cols (12 N_loc + 12 |S| + max_a K_a) (V and X; r_S and
+ * x_S on the separator of the whole problem; the temporary W_a^T v_a, K_a = 6 |S_a| over the robots here) + 64 (3 robots + 1)
+ * of product records + 4 per public pose here of row maps.  A request above the free memory is refused before V and X are
+ * allocated, with the bytes named; the other participants read "rank q: the Schur path does not fit its device".  V and X
+ * alone above the free memory are decided before V is read.
+ * Refused with DPGO_ERR and a message that begins "covariance_apply_across:", before any device work: a NULL among t, tr,
+ * owner_rank_of_robot, T, V, X, res; num_cols <= 0; an entry of V outside pose 0's rows that is not finite (the row, team pose
+ * and column named).  Such a refusal travels in the agreement record: its participant reads its own words, the others "rank
+ * q: invalid arguments"; a num_cols that differs is refused on all of them, naming "num_cols".  The refusals of
+ * dpgo_team_marginal_covariances_across (T outside SE(3), a pivot, memory, measurement sets that differ) carry over in their
+ * own words.  A refused call leaves X untouched and *res all zero on every participant, and the transport usable.  *res: the
+ * path's record, identical on every participant.  Changes no solver state. */
+int dpgo_team_covariance_apply_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
+                                      const double *T, int num_cols, const double *V, double *X, dpgo_covariance_t *res);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
