@@ -139,7 +139,8 @@ dpgo_covariance_nested_plan dpgo_team_covariance_nested_plan dpgo_team_marginal_
 dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consistency dpgo_max_clique
 dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal
 dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across
-dpgo_team_covariance_apply dpgo_team_linear_update_solved dpgo_team_refine dpgo_team_covariance_apply_across""".split()
+dpgo_team_covariance_apply dpgo_team_linear_update_solved dpgo_team_refine dpgo_team_covariance_apply_across
+dpgo_team_refine_across""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1184,7 +1185,8 @@ class Team:
              "covariance_apply")
         return res, X
 
-    def refine(self, T=None, method=None, max_block=None, max_iters=10, grad_tol=1e-8, armijo=1e-4, ladder=8):
+    def refine(self, T=None, method=None, max_block=None, max_iters=10, grad_tol=1e-8, armijo=1e-4, ladder=8, transport=None,
+               owner_of_robot=None):
         """T refined to a critical point of the SE(3) cost by Newton steps on Sigma: what covariances, the gates,
         audit, select_closures, linear_update, linear_removal and covariance_apply assume of their T.  Every iteration forms the
         gradient of g(xi) = f(T [+] xi) (the perturbation of covariances, pose 0 fixed), the cost and |g|_inf on the device,
@@ -1196,12 +1198,22 @@ class Team:
         "indefinite" (a later iterate lost positive definiteness: T is the last good one) | "no_descent" (no step length
         passed), iterations, f0, f, grad_inf0, grad_inf, history=dict(f, grad_inf: iterations + 1 entries; alpha, decrement =
         g^T Sigma g, pivot_min: one entry per path that ran, alpha NaN where no step was taken), covariance: the last path's
-        record).  A T that meets grad_tol comes back bit for bit with iterations 0.  Two calls give the same bytes.  One team
-        only.  Changes no solver state."""
+        record).  A T that meets grad_tol comes back bit for bit with iterations 0.  Two calls give the same bytes.  Changes no
+        solver state.
+        With a transport (a team split across participants, owner_of_robot as for covariances; DESIGN.md 5n "Across teams"):
+        the Schur path across is the only one (method None or "schur"; anything else, or a max_block, raises ValueError before
+        any transport call).  T is this team's poses in team order (None: the rounding across) and so is the T returned; the
+        fixed pose is the problem's pose 0, robot 0's first.  max_iters, grad_tol, armijo and ladder must be the same on every
+        participant.  The cost and g^T X are summed robot by robot and the robots' totals in id order, so every pose, the
+        history and the scalars are the same bits whatever the split, and identical on every participant; they are not bitwise
+        the single team's.  A ValueError (T's size) is raised on this participant alone before the library is called: check
+        shapes before a collective call."""
         if method not in (None, "dense", "schur", "nested"):
             raise ValueError("refine: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
         N = int(sum(self.agents[i].n for i in self.ids))
-        if T is None:
+        if transport is not None:
+            T = self._across_args("refine", T, method, max_block, transport, owner_of_robot)
+        elif T is None:
             T = self.round()[1]
         T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
         if T.size != 12 * N:
@@ -1209,8 +1221,15 @@ class Team:
         code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         rows = max(int(max_iters), 0) + 1
         T_out, hist, out, res = np.zeros(12 * N), np.zeros((rows, 5)), Refine(), Covariance()
-        _chk(lib().dpgo_team_refine(self.h, _d(T), code, int(max_block or 0), int(max_iters), C.c_double(grad_tol),
-                                    C.c_double(armijo), int(ladder), _d(T_out), _d(hist), C.byref(out), C.byref(res)), "refine")
+        if transport is not None:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_refine_across(self.h, C.byref(transport.struct), _d(own), _d(T), int(max_iters),
+                                               C.c_double(grad_tol), C.c_double(armijo), int(ladder), _d(T_out), _d(hist),
+                                               C.byref(out), C.byref(res)), "refine_across")
+        else:
+            _chk(lib().dpgo_team_refine(self.h, _d(T), code, int(max_block or 0), int(max_iters), C.c_double(grad_tol),
+                                        C.c_double(armijo), int(ladder), _d(T_out), _d(hist), C.byref(out), C.byref(res)),
+                 "refine")
         k = out.iterations
         ran = int(np.count_nonzero(~np.isnan(hist[:, 3])))
         return dict(T=T_out, status=REFINE_STATUS[out.status], iterations=k, f0=out.f0, f=out.f, grad_inf0=out.grad_inf0,

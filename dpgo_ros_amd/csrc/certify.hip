@@ -342,8 +342,8 @@ void jacobi_eig(int n, std::vector<double> A, std::vector<double> &w, std::vecto
 }
 
 void launch_cert_apply3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *V, double *out,
-                        const double *lam) {
-  k_cert_apply<3><<<dim3(spmm_grid(3, max_n), na), 64, 0, s>>>(agents, off, V, 3, out, 3, lam, nullptr, nullptr);
+                        const double *lam, const double *halo, const int *hoff) {
+  k_cert_apply<3><<<dim3(spmm_grid(3, max_n), na), 64, 0, s>>>(agents, off, V, 3, out, 3, lam, halo, hoff);
 }
 
 void launch_cert_lambda3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *X,

@@ -152,8 +152,9 @@ int check_team_local(dpgo_team_t *t, const char *what);
 // the rank-3 forms of the certificate's kernels for a trajectory T in the iterate layout (3 x 4N, ld 3; covariance.hip):
 // out = T Q (lam null) or T S, one team;  Lambda_i = Sym(R_i^T E_i,rot) into lam (9 per pose), gmax: na x ceil(max_n / 256)
 // doubles of scratch (the Gershgorin sums k_cert_lambda leaves)
+// across teams: halo ([(4 slot + c) 3 + b], Across::halo_of at k = 3) and hoff (Across::d_hoff), the remote neighbours' poses
 void launch_cert_apply3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *V, double *out,
-                        const double *lam);
+                        const double *lam, const double *halo = nullptr, const int *hoff = nullptr);
 void launch_cert_lambda3(hipStream_t s, const AgentDev *agents, const int *off, int na, int max_n, const double *X,
                          const double *E, double *lam, double *gmax);
 
@@ -187,9 +188,24 @@ struct CovEpilogue {
 // epilogue: the pointer stays valid as long as the staged blocks do.  Pose 0's rows of X are zero bits.
 // Across teams (covariance_schur_across, which has no CovEpilogue) N is this participant's N_loc and pose 0 the problem's, the
 // agreement record carries num_cols, and the path calls taken() once X is set, before its closing status word: taken() queues
-// on `stream` whatever reads X; the path drains the stream.  argerr: this participant's own refusal, which the others learn from
+// on `stream` whatever reads X; the path drains the stream.  Before taken() the path fills `view` (CovAcrossView): what a step
+// that moves T along X needs of the poses behind this participant's own -- it costs no launch and no transport call, and an app
+// that ignores it changes nothing.  argerr: this participant's own refusal, which the others learn from
 // the agreement record; memerr: V and X alone exceed the device (V was then not read), told as the path's memory refusal.
+// What covariance_schur_across holds when it calls CovApply::taken(): T with its halo on the device (N poses of this
+// participant in team order, then halo_slots poses, slot hoffs[k] + s the pose np[s] of local robot k; the slots of remote
+// neighbours are filled, the others are not read by anyone), x_S = Sigma_SS r_S of the WHOLE problem (6 |S| x num_cols, leading
+// dimension nS: after allgather B every participant knows every robot's public frames, so x_S is whole everywhere), and for
+// every halo slot the separator pose whose rows 6 q .. 6 q + 5 of x_S are the slot's rows of X (-1: the problem's fixed pose,
+// whose rows are zero, or a slot of a neighbour that lives here).  All device pointers are ordered on the path's stream and live
+// until the path has drained it behind taken().
+struct CovAcrossView {
+  const double *Td = nullptr, *xS = nullptr;
+  int N = 0, halo_slots = 0, nS = 0;
+  std::vector<int> halo_sep;
+};
 struct CovApply {
+  CovAcrossView view;
   int num_cols = 0;
   double *X = nullptr;
   double ms_products = 0.0, flops = 0.0;  // the apply's own products, for the caller's DPGO_TIMING line

@@ -1060,6 +1060,16 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
       HIPC(hipStreamSynchronize(s));  // (hrS has been read)
     }
     app->X = d_aX.p;
+    {  // what a step along X needs of the poses behind this participant's own (CovAcrossView): host tables, no launch
+      CovAcrossView &v = app->view;
+      v.Td = d_T.p; v.N = N; v.halo_slots = halo_slots; v.xS = nS > 0 ? d_xS.p : nullptr; v.nS = nS;
+      v.halo_sep.assign(halo_slots, -1);
+      for (int k = 0; k < na; ++k)
+        for (size_t q = 0; q < t->ag[k]->np.size(); ++q) {
+          const int b = t->ag[k]->np[q].first, f = t->ag[k]->np[q].second;
+          if (b >= 0 && b < nr && !t->id2local.count(b)) v.halo_sep[hoffs[k] + q] = sep_index(b, f);
+        }
+    }
     if (app->taken(N, s)) return DPGO_ERR;
     HIPC(hipStreamSynchronize(s));
     for (size_t k : app_marks) {

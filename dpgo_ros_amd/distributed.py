@@ -604,14 +604,16 @@ class TorchTransport(_Transport):
 
 
 def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8, max_iters=1000, block=0,
-                      refine_translations=True, certify_kw=None, covariances=False, pairs=None):
+                      refine_translations=True, certify_kw=None, covariances=False, pairs=None, refine=False):
     """The certificate and the SE-Sync rounding of an iterate split across ranks (one team per rank), with global results on
     every rank that owns a robot: dict(T = the rounded poses of all robots in global order (robots by id), certificate,
     rounding, f_relaxed, f_rounded, gap_rel as in capi.solve_certified).  Every rank of the world calls (ranks that own no
     robot are left out through a sub-group, whose creation is collective) and gets None back when it owns none.
     covariances=True adds covariances=(Covariance, diag[N, 6, 6] of all poses in global order[, cross[len(pairs), 6, 6]]):
     Team.covariances of the split team at T (pairs: global pose indices, the same list on every rank), the diagonal blocks
-    gathered the way T is."""
+    gathered the way T is.  refine=True refines the rounded T to a critical point on SE(3) across the ranks (Team.refine with
+    the transport, at its defaults) and adds refine=its dict (T: this rank's poses); T and the covariances are then taken at
+    the refined T, while rounding and f_rounded stay those of the rounded point."""
     owners = sorted(set(int(o) for o in owner_of_robot))
     group = None
     if dist.get_world_size() != len(owners):
@@ -624,6 +626,10 @@ def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8,
     cert, _ = team.certify(eta=eta, tol=tol, max_iters=max_iters, block=block, transport=tr, owner_of_robot=own,
                            **(certify_kw or {}))
     rd, T = team.round(refine_translations=refine_translations, transport=tr, owner_of_robot=own)
+    rf = None
+    if refine:
+        rf = team.refine(T, transport=tr, owner_of_robot=own)
+        T = rf["T"]
     # every rank's poses, padded to one length, then placed by robot id
     ids = list(team.ids)
     head = np.array([len(ids)] + ids + [team.agents[i].n for i in ids], dtype=np.float64)
@@ -643,6 +649,8 @@ def certify_and_round(backend_or_team, dist, owner_of_robot, eta=1e-6, tol=1e-8,
     Tg = np.concatenate([blocks[i] for i in sorted(blocks)])
     gap = (rd.f_rounded - rd.f_relaxed) / rd.f_relaxed if cert.certified == 1 else None
     out = dict(T=Tg, certificate=cert, rounding=rd, f_relaxed=rd.f_relaxed, f_rounded=rd.f_rounded, gap_rel=gap)
+    if refine:
+        out["refine"] = rf
     if covariances:
         cres, diag, cross = team.covariances(T, pairs, transport=tr, owner_of_robot=own)
         # (T holds 12 doubles per pose, a diagonal block 36: the same record, three times as long at most)
@@ -730,3 +738,36 @@ def covariance_apply(backend_or_team, dist, owner_of_robot, V, T=None, gather=Fa
             blocks[int(i)] = allr[q, o:o + 6 * n * m].reshape(6 * n, m)
             o += 6 * n * m
     return res, np.concatenate([blocks[i] for i in sorted(blocks)], axis=0)
+
+
+def refine(backend_or_team, dist, owner_of_robot, T=None, gather=False, **kw):
+    """Team.refine of an estimate split across ranks (one team per rank): T this rank's poses in team order (None: the rounding
+    across); kw: max_iters, grad_tol, armijo, ladder, the same on every rank.  The dict of Team.refine with T this rank's
+    refined poses; status, iterations, history and the scalars are identical on every rank.  With gather=True T is that of the
+    whole problem instead, 12 doubles per pose in global pose order (robots by id) and identical on every rank: one allgather of
+    the local poses behind one of their lengths, the way covariance_apply gathers its rows.  A T of the wrong size raises
+    ValueError on this rank before the library is called: the other ranks then wait in the agreement record until the
+    transport gives up, as for the other calls across ranks.  None on a rank that owns no robot."""
+    p = _participants(backend_or_team, dist, owner_of_robot)
+    if p is None:
+        return None
+    team, tr, own = p
+    out = team.refine(T, transport=tr, owner_of_robot=own, **kw)
+    if not gather:
+        return out
+    ids = list(team.ids)
+    head = np.array([len(ids)] + ids + [team.agents[i].n for i in ids], dtype=np.float64)
+    sizes = tr.allgather(np.array([head.size + out["T"].size], dtype=np.float64)).astype(int)
+    mine = np.zeros(int(sizes.max()))
+    mine[:head.size], mine[head.size:head.size + out["T"].size] = head, out["T"]
+    allr = tr.allgather(mine).reshape(tr.world, mine.size)
+    blocks = {}
+    for q in range(tr.world):
+        k = int(allr[q, 0])
+        rid, rn = allr[q, 1:1 + k].astype(int), allr[q, 1 + k:1 + 2 * k].astype(int)
+        o = 1 + 2 * k
+        for i, n in zip(rid, rn):
+            blocks[int(i)] = allr[q, o:o + 12 * n]
+            o += 12 * n
+    out["T"] = np.concatenate([blocks[i] for i in sorted(blocks)])
+    return out

@@ -845,6 +845,38 @@ int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_transport_t *
  * path's record, identical on every participant.  Changes no solver state. */
 int dpgo_team_covariance_apply_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
                                       const double *T, int num_cols, const double *V, double *X, dpgo_covariance_t *res);
+/* ---- dpgo_team_refine over a team split across participants (csrc/refine.hip; DESIGN.md 5n, "Across teams") ----
+ * Collective: every participant calls it with its own team and the same owner table, max_iters, grad_tol, armijo and ladder.
+ * T, T_out: this participant's 12 N_loc doubles in team order.  history, *out, *res and the status codes are those of
+ * dpgo_team_refine and are identical on every participant.  There is no method: a split team has the Schur path alone.
+ * The fixed pose is the PROBLEM's pose 0, robot 0's first: on a participant that does not hold robot 0 every local pose moves.
+ * Per iterate: E = T Q from the across operator at K = 3 (one exchange of the T halo), the gradient on the local poses, and the
+ * cost summed ROBOT BY ROBOT -- a measurement belongs to its own robot, a shared one to the lower robot id, whose copy owns the
+ * weight; a robot's terms are summed in the order of its own list, 256 to a workgroup, the workgroups in index order -- so a
+ * robot's total depends on nothing but the robot.  The totals are allgathered and added on the host in robot order from 0;
+ * |g|_inf is the largest of the participants' (a NaN wins).  The step is X = Sigma g from dpgo_team_covariance_apply_across'
+ * path with one column; the rows of X of the remote end points of this participant's shared measurements are read out of
+ * x_S = Sigma_SS r_S, which is whole on every participant, so the trial trajectories need no further exchange.  The ladder's
+ * costs and g^T X are summed by robot in the same way; the first l with
+ *   f_l <= f - armijo 2^-l g^T X + eps_f,   eps_f = (24 + max_a ceil(E_a / 256) + R) 2^-53 f
+ * is taken (R robots in the problem, E_a the measurements robot a owns), by every participant from the same bits.
+ * Transport calls for k steps: the two agreement allgathers and the closing one; per evaluated iterate (k + 1 of them) one
+ * exchange and one allgather; per step the calls of dpgo_team_marginal_covariances_across with zero pairs and one allgather.
+ * For a given problem and T every pose of T_out, every entry of history and every scalar are the same bits whatever the split,
+ * one participant that holds every robot included; two calls give the same bytes.  It is not bitwise dpgo_team_refine of the
+ * joined team (the step comes from the Schur path's sets, the sums run by robot).  A T that meets grad_tol comes back bit for bit
+ * with iterations = 0 and no path run.
+ * Refused with DPGO_ERR and a message that begins "refine_across:": a NULL argument; max_iters < 0; ladder outside [1, 32];
+ * grad_tol not positive; armijo outside (0, 1); a pose of T outside SE(3).  Such a refusal travels in the agreement record: its
+ * participant reads its own words, the others "rank q: invalid arguments"; a max_iters, ladder, grad_tol or armijo that differs
+ * is refused on all of them ("the participants disagree on ...").  A pivot that is not positive at the input T refuses every
+ * participant with the path's message behind "refine: "; at a later iterate the status is DPGO_REFINE_INDEFINITE everywhere.
+ * The path's other refusals pass through.  A refused call leaves T_out and history untouched and *out, *res zero, and the
+ * transport usable.  Bytes on the device beside the path's, with H the halo poses here: 8 x 12 (N_loc + H) (ladder + 1) +
+ * 8 x 6 (2 N_loc + H) + 8 x 12 N_loc + 128 per measurement owned here.  No floating-point atomics.  Changes no solver state. */
+int dpgo_team_refine_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot, const double *T,
+                            int max_iters, double grad_tol, double armijo, int ladder, double *T_out /* 12 N_loc */,
+                            double *history /* 5 (max_iters + 1) */, dpgo_refine_t *out, dpgo_covariance_t *res);
 /* the synchronous schedule with the leader's decisions (src/PGOAgentROS.cpp:129-220): iterate; after every iteration
  * in which the leader optimized: stop if shouldTerminate() (:208), else an UPDATE_WEIGHT round if
  * shouldUpdateMeasurementWeights() (:210), else pass the token (:213).  Returns the number of iterations executed
