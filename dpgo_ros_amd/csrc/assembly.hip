@@ -3,6 +3,7 @@
 // SURVEY 8a rows 'PoseGraph data matrices').
 #include <mutex>
 #include "team_internal.h"
+#include "step_front.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -399,6 +400,7 @@ int finalize_agent(dpgo_team *t, Agent &a, double *scratch) {
   }
   pub_ptr.push_back((int)se.size());
   a.npub = (int)pub_pose.size();
+  a.pub_pose_host = pub_pose; a.pub_ptr_host = pub_ptr;
   pose_eptr.assign(n + 1, 0);
   for (const auto &d : se) pose_eptr[d.lpose + 1] += 1;
   for (int j = 0; j < n; ++j) pose_eptr[j + 1] += pose_eptr[j];
@@ -738,6 +740,7 @@ int sync_descs_noflush(dpgo_team *t) {
       for (size_t q = 0; q < a->np.size(); ++q)
         if (t->peers.count(a->np[q].first)) { a->np_has[0][q] = 1; a->np_has[1][q] = 1; }
   if (!t->descs_dirty) return 0;
+  t->desc_gen += 1;
   // direct pointers from every shared edge to the neighbour's pose (buffers of re-assembled agents may have moved)
   for (auto &a : t->ag) {
     if (a->se_host.empty() || !a->d_se.p) continue;
@@ -762,12 +765,6 @@ int sync_descs_noflush(dpgo_team *t) {
     }
     if (a->d_se.upload(a->se_host, t->stream)) { set_err("shared-edge upload failed"); return DPGO_ERR; }
     a->dev.se = a->d_se.p;
-    {
-      std::vector<double> packed(16 * a->se_host.size());
-      for (size_t e = 0; e < a->se_host.size(); ++e) std::memcpy(&packed[16 * e], a->se_host[e].coef, 16 * sizeof(double));
-      if (a->d_fe_coef.upload(packed, t->stream)) { set_err("shared-edge upload failed"); return DPGO_ERR; }
-      a->dev.fe_coef = a->d_fe_coef.p;
-    }
     // (carried one-launch iteration: the same pointers as 16-bit codes in the descriptor)
     a->dev.fe_code_ok = (int)a->se_host.size() <= FE_MAX_EDGES && !t->isolated;
     for (int q = 0; q < FE_MAX_EDGES / 2; ++q) a->dev.fe_code[q] = 0;
@@ -778,6 +775,34 @@ int sync_descs_noflush(dpgo_team *t) {
         break;
       }
       a->dev.fe_code[e >> 1] |= (unsigned)(d.src_frame | (d.src_agent_local << 12)) << (16 * (e & 1));
+    }
+    {
+      // the packed coefficients and, behind them at a fixed offset, the front table of the deep-carried launches
+      // (step_front.h): ONE image, built from what those launches would otherwise resolve themselves -- the codes above, the
+      // bases and pose counts launch_step_fd passes (FeBases), the public-pose tables, the chunk order -- and uploaded whole
+      // on every descriptor sync: after a weight update (new coefficients), new measurements (new codes and tables), a rank
+      // change or a re-allocated work vector of ANY agent (new addresses).  An agent the table cannot stand for uploads its
+      // coefficients alone and keeps a stale front_gen: its team does not take the deep-carried form (fe_deep_m0).
+      const size_t ns = a->se_host.size();
+      const bool fits = a->dev.fe_code_ok && ns <= (size_t)FD_FRONT_EDGES;
+      std::vector<double> &img = a->fe_image;
+      img.assign(fits ? FD_FRONT_IMAGE_DOUBLES : 16 * ns, 0.0);
+      for (size_t e = 0; e < ns; ++e) std::memcpy(&img[16 * e], a->se_host[e].coef, 16 * sizeof(double));
+      bool current = false;
+      if (fits && (int)a->pub_pose_host.size() == a->npub && (int)a->pub_ptr_host.size() == a->npub + 1) {
+        const double *ybase[LOOKAHEAD_MAX_AGENTS] = {};
+        int npose[LOOKAHEAD_MAX_AGENTS] = {};
+        const int na = (int)std::min<size_t>(t->ag.size(), LOOKAHEAD_MAX_AGENTS);
+        for (int k = 0; k < na; ++k) { ybase[k] = t->ag[k]->dev.buf[B_Y]; npose[k] = t->ag[k]->n; }
+        FdFront ft;
+        current = fd_front_build(ft, t->prm.r, a->n, (int)ns, a->dev.fe_code, na, ybase, npose, B_ALT, a->npub, a->pub_pose_host.data(),
+                                 a->pub_ptr_host.data(), a->dev.fe_ord);
+        if (current) std::memcpy(&img[FD_FRONT_OFF_DOUBLES], &ft, sizeof ft);
+      }
+      if (a->d_fe_coef.upload(img, t->stream)) { set_err("shared-edge upload failed"); return DPGO_ERR; }
+      a->dev.fe_coef = a->d_fe_coef.p;
+      // (captured launches hold this pointer in their head: the graphs are dropped below, graph_valid, whether it moved or not)
+      a->front_gen = current ? t->desc_gen : 0;
     }
   }
   std::vector<AgentDev> descs;

@@ -44,12 +44,20 @@
 // behind it, everything else in one struct (FdArgs: the descriptor, what the launch needs of the next two agents, ...).  The
 // head is delivered in SGPRs at wave launch (the object is built with -amdgpu-kernarg-preload-count=14; where the firmware
 // does not preload, a prologue the compiler emits fetches the same dwords), FdArgs sits in memory nobody has touched.  So
-// every role forms its FIRST requests from the head alone -- the streamers the carried rows; the chain waves W / X, their
-// quarter of the last chunks, the operands of the tail; wave 6 its quarter; wave 7 the coefficients and its quarter -- and
+// every role forms its FIRST requests from the head alone -- the streamers the carried rows; the chain waves their public
+// pose's record, W / X, their quarter of the last chunks, the operands of the tail; wave 6 the addresses of its edges'
+// neighbour poses, its quarter and, through the addresses, the poses; wave 7 the coefficients and its quarter -- and
 // only then calls fd_args_behind_requests: one word of every line of FdArgs touched, all in flight at once, and no load of
 // the struct can be moved above that point (where the wait for it would stand in front of those requests: the kernel's one
 // barrier, whose LDS write shares the scalar loads' counter, waited for the arguments in every wave).  Nothing in front of
 // the barrier reads memory: the workgroup's place in the grid follows from the head too (profiles/r21_step_head.md).
+// What a role LOOKS UP before it can ask for data -- where the neighbour pose of each shared edge lives (wave 6), which
+// pose, which edges and which place in the chunk order a lane's public pose has (the chain waves) -- does not change from
+// launch to launch, so it is not resolved in the launch: the host forms it where it builds the descriptor (assembly.hip) and
+// keeps it in a FRONT TABLE behind the packed coefficients, at a fixed offset of the allocation the head's fe_coef points at
+// (step_front.h).  Those reads are the roles' first instructions; the descriptor's own copies (fe_code, FeBases, pub_pose,
+// pub_ptr) serve k_step_fe, k_precond and the evaluations.  A team whose table is not the one built from the descriptors as
+// last published (Agent::front_gen against dpgo_team::desc_gen) does not take this form (fe_deep_m0).
 // Where a launch's 12.6 us went in round 6 (profiles/r06_deep_carry.md): 2.8 until everything is requested (134 KB per CU in front of
 // the stream -- every workgroup finishes ALL public poses itself, the price of no exchange inside the launch), 1.0 until the
 // edges' operands have landed, 1.9 gradient of the public poses, 0.9 product over the last chunks, 0.5 reduction, 3.2 tail,
@@ -57,6 +65,12 @@
 // of it: the streamers are done 3 us before the tail.  With the head the launch takes 11.3 us dispatch to dispatch
 // (12.5 without, same session): the first requests of every role moved forward by 0.1-0.2 us only -- a data trip remains --,
 // most of the gain is in front of the first instruction and behind the last (r21_step_head.md: stamps of both builds).
+// With the front table (profiles/r26_step_front.md; trace build, us from wave 4's first instruction, parent -> table): wave 6
+// requests the neighbour poses at 1.2-1.4 (2.6) and hands them over at 2.1-2.2 (3.1-3.2); the chain waves count in at 2.4-2.6
+// (2.8-3.2), the stream is released at 2.6-2.8 (3.3-3.4); E, seen by the chain, 3.4-3.7 (3.7-3.8) -- it is wave 7's hand-off
+// of the coefficients (3.3-3.6), which stands behind its count-in, and moving it in front (three placements) measured slower;
+// D 4.9-5.4 (5.7-5.8); tail end, median over the workgroups, 10.64 (10.80); streamers' end 8.55 (8.63): the stream still lands
+// under the chain.  Product builds: 11.43 us dispatch to dispatch against 11.58 for the parent in the same sessions.
 // Same arithmetic on the same operands in the same order as k_step_fe / the two-launch sequence: the iterates are BITWISE
 // theirs (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).  The Nesterov scalars (nest_ahead), the books
 // (step_books), the look-ahead map (lookahead_map) and the step of the two poses (step_two_poses) are the text of
@@ -66,9 +80,12 @@
 // 2-4 % more instructions and 0.14 us per launch, profiles/r19_nesterov_step.md.)
 #include "kernel_common.h"
 #include "step_head.h"
+#include "step_front.h"
 #include <algorithm>
 
 namespace dpgo {
+
+static_assert(FD_FRONT_EDGES == FE_MAX_EDGES && FD_FRONT_AGENTS == LOOKAHEAD_MAX_AGENTS, "step_front.h repeats these limits");
 
 // ---- device helpers of k_step_fd: hand-offs between the waves of a workgroup through counters in LDS, the chunk-ordered
 // layout, the staging of the shared edges' operands, the product over the last chunks
@@ -132,8 +149,9 @@ __device__ __forceinline__ int fd_pos_off(const unsigned char *ord, int pose) {
 
 // The operands of the shared edges go to LDS, [edge][neighbour pose 4r | 16 coefficients].
 //   * wave 6, neighbour poses: one lane per edge (edges l, 64 + l, 128 + l), 2r loads of 16 bytes each.  Where the neighbour
-//     lives comes from the edge's 16-bit code (frame | agent << 12) in the descriptor -- scalar registers and a select
-//     chain, no descriptor round trip (k_step_fe).  (Measured and dropped, round 6: 64 consecutive 16-byte parts per load --
+//     lives is an address the host formed once (step_front.h: xaddr[parity][edge], behind the coefficients) -- three 8-byte
+//     loads per lane, the wave's first instructions; k_step_fe forms it in every launch from the edge's 16-bit code in the
+//     descriptor and the agents' bases, as this kernel did until r26.  (Measured and dropped, round 6: 64 consecutive 16-byte parts per load --
 //     a quarter of the cache-line requests -- with the address handed from the edge's lane by ds_bpermute: the wave reached
 //     the request hand-off 1.5 us LATER; and with the codes looked up per part: scalar loads inside every trip, 4 us later.)
 //   * wave 7, coefficients: the packed copy [edge][16] (AgentDev::fe_coef) read straight through, 1 KB per load -- 100
@@ -144,47 +162,27 @@ struct FdXn {
   double2 v[3][2 * R];
 };
 
+// the front table's reads (step_front.h): ordinary vector loads, indexed by lane
+__device__ __forceinline__ const double *fd_front_ld_xaddr(const FdFront *ft, int parity, int slot) {
+  typedef const double *Ptr;
+  return *(const __attribute__((address_space(1))) Ptr *)&ft->xaddr[parity][slot];
+}
+
+__device__ __forceinline__ FdFrontPub fd_front_ld_pub(const FdFront *ft, int q) {
+  typedef int v4i_t __attribute__((ext_vector_type(4)));
+  const v4i_t v = *(const __attribute__((address_space(1))) v4i_t *)&ft->pub[q];
+  return FdFrontPub{v.x, v.y, v.z, v.w};
+}
+
 template <int R>
-__device__ __forceinline__ void fd_xn_request(const AgentDev &ag, const FeBases &fb, int parity, int ln, FdXn<R> &xr) {
-  // the agents' bases and pose counts as scalar VALUES in front of the selects.  (Left as expressions of the arguments the
-  // compiler selects the ADDRESS instead and fetches the base with a vector load from the argument segment, the count under a
-  // branch on the parity: the wait for either is a wait for EVERYTHING the wave has requested -- its quarter of the last
-  // chunks included, and once per slot.  Read off the ISA.)
-  const double *ybs[LOOKAHEAD_MAX_AGENTS];
-  int yns[LOOKAHEAD_MAX_AGENTS];
-#pragma unroll
-  for (int k = 0; k < LOOKAHEAD_MAX_AGENTS; ++k) { ybs[k] = fb.ybase[k]; yns[k] = fb.npose[k]; }
-  static_assert(LOOKAHEAD_MAX_AGENTS == 8, "one operand below per agent");
-  // (all sixteen in ONE statement: one wait for the scalar loads, not one per value)
-  asm volatile("" : "+s"(ybs[0]), "+s"(ybs[1]), "+s"(ybs[2]), "+s"(ybs[3]), "+s"(ybs[4]), "+s"(ybs[5]), "+s"(ybs[6]), "+s"(ybs[7]),
-               "+s"(yns[0]), "+s"(yns[1]), "+s"(yns[2]), "+s"(yns[3]), "+s"(yns[4]), "+s"(yns[5]), "+s"(yns[6]), "+s"(yns[7]));
+__device__ __forceinline__ void fd_xn_request(const double *const (&xa)[3], FdXn<R> &xr) {
+  // (every slot, edges or not: loads under a wave-uniform `if` leave the compiler without a count of what is in flight behind
+  // the join, and the wait in front of the LDS writes becomes a wait for EVERYTHING the wave has requested; the table's slots
+  // beyond the last edge hold the address of a pose that exists)
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    {  // (every slot, edges or not: loads under a wave-uniform `if` leave the compiler without a count of what is in flight
-       // behind the join, and the wait in front of the LDS writes becomes a wait for EVERYTHING the wave has requested)
-      // word ln >> 1 of the slot's 32: a binary tree of selects on the bits of the index -- five lane masks in scalar
-      // registers where a chain of 32 compares held 32 pairs, more than the wave has beside the descriptor's words
-      unsigned wt[32];
 #pragma unroll
-      for (int k = 0; k < 32; ++k) wt[k] = ag.fe_code[(32 * q + k < FE_MAX_EDGES / 2) ? 32 * q + k : FE_MAX_EDGES / 2 - 1];
-#pragma unroll
-      for (int bit = 0; bit < 5; ++bit) {
-        const bool up = ((ln >> 1) >> bit) & 1;
-#pragma unroll
-        for (int k = 0; k < (16 >> bit); ++k) wt[k] = up ? wt[2 * k + 1] : wt[2 * k];
-      }
-      const unsigned wsel = wt[0];
-      // (lanes beyond the last edge read the pose of an edge that exists: words beyond the last edge hold zeros = agent 0, frame 0)
-      const unsigned code = (ln & 1) ? (wsel >> 16) : (wsel & 0xffffu);
-      const int sa = (int)(code >> 12), sf = (int)(code & 0xfffu);
-      const double *yb = ybs[0];
-      int yn = yns[0];
-#pragma unroll
-      for (int k = 1; k < LOOKAHEAD_MAX_AGENTS; ++k) { yb = (sa == k) ? ybs[k] : yb; yn = (sa == k) ? yns[k] : yn; }
-      const double *xp = yb + (parity ? (size_t)B_ALT * 4 * R * yn : (size_t)0) + (size_t)sf * 4 * R;
-#pragma unroll
-      for (int k = 0; k < 2 * R; ++k) xr.v[q][k] = ld2(xp + 2 * k);
-    }
+    for (int k = 0; k < 2 * R; ++k) xr.v[q][k] = ld2(xa[q] + 2 * k);
   }
 }
 
@@ -350,6 +348,7 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
   const FdHead hd = {hd_buf0, hd_M, hd_pacc_in, hd_fe_coef, hd_np, hd_sf, hd_ord_lo, hd_ord_hi, nblk_all};
   const int n = fd_head_n(hd.np), N4 = 4 * n, hd_npub = fd_head_npub(hd.np), hd_nshared = fd_head_nshared(hd.sf);
   const int parity = fd_head_parity(hd.sf), flags = fd_head_flags(hd.sf);
+  const FdFront *ft = fd_front_of(hd.fe_coef);  // the front table (step_front.h): behind the coefficients, at a fixed offset
   // the poses live twice (step_fused.hip): this launch reads the copy of its parity and writes the other one
   const double *__restrict__ Xr = fd_head_buf(hd.buf0, R, n, parity ? B_XALT : B_X);
   const double *__restrict__ Yr = fd_head_buf(hd.buf0, R, n, parity ? B_YALT : B_Y);
@@ -490,6 +489,10 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     const int pq = 64 * g + ln;
     const bool pact = pq < npub;
     const int pqc = pact ? pq : 0;
+    // (the lane's public pose -- where its row goes, which edges are its -- from the front table, first: one 16-byte load;
+    // records beyond the last public pose are zeros)
+    const FdFrontPub pr = fd_front_ld_pub(ft, pq);
+    __builtin_amdgcn_sched_barrier(0);
     double w[4 * R], x[4 * R];
     {
       const double *Wc = fd_head_buf(hd.buf0, R, n, B_CARRY_W), *Xc = fd_head_buf(hd.buf0, R, n, B_CARRY_X);
@@ -513,12 +516,11 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
       pre_y = gp(Yr)[own_off];
       pre_p = gp(fd_head_buf(hd.buf0, R, n, B_XPREV))[own_off];
     }
-    // ---- behind them, from FdArgs: which pose and which edges, the rows of W, the Nesterov state
+    // ---- behind them, from FdArgs: the rows of W, the Nesterov state
     const FdArgs &as = fd_args_behind_requests<true>();
     const AgentDev &ag = as.ag;
     const FdNext &nx = as.nx;
-    const int pj = ag.pub_pose[pqc];
-    const int pe0 = ag.pub_ptr[pqc], pe1 = ag.pub_ptr[pqc + (pact ? 1 : 0)];
+    const int pe0 = pr.pe0, pe1 = pr.pe1, vs_off = pr.vs_off;
     // W (wave 5, behind its quarter of the product): the indices of the rows now (wave 4's copies are never used)
     const int npw = (nx.n_e + nblk_all - 1) / nblk_all;  // (<= 2)
     const int wls = ln / (4 * R), we = ln - wls * (4 * R);
@@ -536,7 +538,6 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     FD_STAMP(10);
     fd_signal_requested(&sy[FD_SY_RQ]);
     FD_STAMP(11);
-    const int vs_off = fd_pos_off<R>(ag.fe_ord, pj);  // (where the pose's row goes: looked up while the edges' operands land)
     fd_wait(&sy[FD_SY_E], 2);  // the operands of the shared edges are in LDS
     FD_STAMP(1);
     if (pact) {
@@ -653,13 +654,18 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
   // then the row products of the agent two iterations ahead (6) / the look-ahead of the other agents' poses (7)
   const int h = cwv - 6;
   if (h == 0) {
-    // (its quarter of the last chunks from the head first: the neighbour poses need the edges' codes, 320 B of FdArgs)
+    // (where its three edges' neighbour poses live, from the front table, FIRST: its quarter of the last chunks is requested
+    // while the addresses travel, and the wait in front of the pose loads counts the three address loads alone)
+    const double *xa[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) xa[q] = fd_front_ld_xaddr(ft, parity, 64 * q + ln);
+    __builtin_amdgcn_sched_barrier(0);
     FdCur<R, NC> cu;
     fd_cur_request<R, M0, NC>(hd, N4, bx, nblk, tid - 256, cu);
-    const FdArgs &as = fd_args_behind_requests<true>();
     FdXn<R> er;
-    fd_xn_request<R>(as.ag, as.fb, parity, ln, er);
+    fd_xn_request<R>(xa, er);
     FD_STAMP(9);
+    const FdArgs &as = fd_args_behind_requests<true>();
     FD_STAMP(10);
     fd_signal_requested(&sy[FD_SY_RQ]);
     FD_STAMP(11);

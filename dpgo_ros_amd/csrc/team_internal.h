@@ -244,7 +244,12 @@ struct Agent {
   bool opt_success = false, opt_cached = false;
   double opt_ratio = 1.0, opt_rel_change = 0.0;
   DevBuf<SharedEdgeDev> d_se;
-  DevBuf<double> d_fe_coef;  // the coefficients of the shared edges once more, packed [edge][16] (step_deep.hip reads them with whole-line loads)
+  DevBuf<double> d_fe_coef;  // the coefficients of the shared edges once more, packed [edge][16] (step_deep.hip reads them with whole-line
+                             // loads) and, for agents of <= FE_MAX_EDGES edges, the front table behind them (step_front.h): one image
+  std::vector<double> fe_image;             // its host copy
+  std::vector<int> pub_pose_host, pub_ptr_host;  // the public-pose tables of the last full build (the front table repeats them)
+  unsigned long long front_gen = 0;         // dpgo_team::desc_gen of the descriptor sync that last built and uploaded the front
+                                            // table (0: never, or the last sync could not build it)
   std::vector<SharedEdgeDev> se_host;
   std::vector<int> se_order;          // se_host[e] describes shared[se_order[e]] (sorted by local pose, stable)
   std::vector<dpgo::EdgeDev> edges_host;  // the edge records of the residual / cost kernels (odometry, private, shared)
@@ -284,6 +289,8 @@ struct dpgo_team {
   std::vector<int> sched;
   int iter = 0;
   bool descs_dirty = true;
+  unsigned long long desc_gen = 0;  // counts the descriptor syncs that republished the descriptors (sync_descs): whatever is derived
+                                    // from them and cached elsewhere (Agent::front_gen) is current only if it carries this count
   int max_n = 0, max_npub = 0;
   dpgo::RtrState *h_state = nullptr;  // pinned
   double *h_scal = nullptr;     // pinned [16 x local agents] (fetch_scal uses the first 16)

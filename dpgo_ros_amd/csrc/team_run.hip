@@ -127,6 +127,9 @@ int fe_deep_m0(dpgo_team *t) {
   int min_priv = 32, nblk_all = 0, total = 0;
   for (auto &a : t->ag) {
     if (a->npub < 1 || a->npub > 128 || !a->dev.fe_code_ok || (int)a->se_host.size() > FE_MAX_EDGES) return 0;
+    // (the launches resolve their edges and public poses from the front table, step_front.h: it must be the one built from
+    // the descriptors as they were last published)
+    if (t->desc_gen == 0 || a->front_gen != t->desc_gen) return 0;
     min_priv = std::min(min_priv, a->dev.fe_npriv);
     nblk_all = std::max(nblk_all, (4 * a->n + 7) / 8);
     total += a->n;
