@@ -28,8 +28,9 @@
 // most of them have landed (step_fused.hip), and every s_barrier behind that point waits for it -- the critical chain
 // (gradient of the public poses -> product over the last chunks -> tail) must not meet the streamers again.  So the only
 // s_barrier stands at the kernel's head (it zeroes the counters); every hand-off is a counter in LDS that only the waves
-// concerned wait at -- the first of them (RQ) orders the requests: waves 4-7 count themselves in behind their last load, the
-// streamers release the stream when all four have (everything the chain needs is in the CU's memory queue in front of it):
+// concerned wait at -- the first of them (RQ) orders the requests: waves 4-7 count themselves in behind their last load (and
+// behind no load's DATA: see "the count-in waits for no data" below), the streamers release the stream when all four have
+// (everything the chain needs is in the CU's memory queue in front of it):
 //     waves 0-3  streamers: the carried gradient of c's last chunks -> LDS (C); then the whole P part on their own (N: their
 //                own hand-off; they start their product behind F, the chain's -- the two share the LDS)
 //     waves 4-5  the chain: one public pose per lane (G_j from LDS, projection; rows -> LDS: D) -> their quarters of the
@@ -71,6 +72,23 @@
 // of the coefficients (3.3-3.6), which stands behind its count-in, and moving it in front (three placements) measured slower;
 // D 4.9-5.4 (5.7-5.8); tail end, median over the workgroups, 10.64 (10.80); streamers' end 8.55 (8.63): the stream still lands
 // under the chain.  Product builds: 11.43 us dispatch to dispatch against 11.58 for the parent in the same sessions.
+// THE COUNT-IN WAITS FOR NO DATA (r27, profiles/r27_count_in.md; held on the assembly by tests/test_step_count_in_build.py).
+// vmcnt retires in order: a wait for ANY load of a wave in front of its count-in is a wait for everything it requested before
+// that load, the loads of M from HBM among them, and the count-in then stands behind the data, not behind the requests.  The
+// parent had such waits in three places, read off its assembly (k = loads issued, vmcnt(n) blocks when n < k; <5, 24>):
+//   * the chain waves and wave 7 brought the Nesterov state's `iter` to a scalar register in front of the count-in: vmcnt(1)
+//     after 47 loads, vmcnt(20) after 57.  Now fd_nest_request asks for the state in front of the count-in and leaves it in
+//     vector registers; fd_nest_state consumes it where it is first used, behind the role's product (directly behind the
+//     count-in the same wait stood in front of wave 7's hand-off E, and measured slower than the parent);
+//   * wave 7 fetched ybase / npose of its lane's agent with vector loads from the argument segment: vmcnt(2) after 37 loads
+//     in front of its first look-ahead address.  Now it selects VALUES among the eight it holds in scalar registers;
+//   * the chain waves stalled twice while issuing, on registers of load halves nobody reads (the `pose` word of the front
+//     table's record, the translation half of a pair of the point): vmcnt(16) after 17, vmcnt(8) after 25.  Now they request
+//     12 bytes of the record and the rotation block of the point only.
+// Wave 6 keeps its three counted waits, one in front of the pose loads of each address.  No instance has a flat_ access (one
+// is enough for the compiler to turn every counted wait into vmcnt(0)).  Trace build, r27 (parent in the same session): the
+// chain waves count in at 2.0-2.2 (2.4-2.8), wave 7 at 2.3-2.4 (2.5-2.8), the stream is released at 2.5-2.6 (2.6-3.0), E is
+// seen at 3.4-3.5 (3.4-3.8).  Product builds: 11.13-11.15 us dispatch to dispatch against 11.43-11.44 for the parent.
 // Same arithmetic on the same operands in the same order as k_step_fe / the two-launch sequence: the iterates are BITWISE
 // theirs (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).  The Nesterov scalars (nest_ahead), the books
 // (step_books), the look-ahead map (lookahead_map) and the step of the two poses (step_two_poses) are the text of
@@ -118,11 +136,52 @@ __device__ __forceinline__ void fd_signal(int *cnt) {
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// the roles that count themselves in at FD_SY_RQ.  Each leaves two comment-only markers in the assembly -- "fd_role_entry k" in
+// front of its first request, "fd_count_in k" in front of its count -- which tests/test_step_count_in_build.py walks between
+enum { FD_ROLE_CHAIN = 4, FD_ROLE_POSES = 6, FD_ROLE_COEF = 7 };
+
+template <int ROLE>
+__device__ __forceinline__ void fd_role_entry() {
+  asm volatile("; fd_role_entry %0" ::"n"(ROLE));
+}
+
+// The Nesterov state of the stepped agent is REQUESTED in front of the count-in and CONSUMED behind it.  Read as a struct it
+// is one wave-uniform load whose `iter` the compiler brings to a scalar register at once -- in front of the count-in, behind
+// a wait for the load and, since vmcnt retires in order, for everything the wave requested before it (the loads of M from
+// HBM among them): the count-in stood behind the data.  So: loaded through a lane-opaque zero offset, the words stay in
+// vector registers until fd_nest_state, which the roles call where they first use the state: behind their product.
+// (Requesting it behind the count-in is not the same: the load would queue behind the stream.)
+struct FdNestReq {
+  double gamma, alpha;
+  int iter;
+};
+
+__device__ __forceinline__ FdNestReq fd_nest_request(const NestState *src) {
+  static_assert(offsetof(NestState, gamma) == 0 && offsetof(NestState, alpha) == 8 && offsetof(NestState, iter) == 16, "the words below");
+  int z = 0;
+  asm volatile("" : "+v"(z));
+  const __attribute__((address_space(1))) char *p = (const __attribute__((address_space(1))) char *)src + z;
+  FdNestReq rq;
+  // (word by word: a word nobody reads behind the count-in is then not requested at all -- the dead half of a wider load is
+  // a register the compiler reuses while the load is in flight, behind a wait for it)
+  rq.gamma = *(const __attribute__((address_space(1))) double *)p;
+  rq.alpha = *(const __attribute__((address_space(1))) double *)(p + 8);
+  rq.iter = *(const __attribute__((address_space(1))) int *)(p + 16);
+  return rq;
+}
+
+__device__ __forceinline__ NestState fd_nest_state(const FdNestReq &rq) {
+  NestState ns;
+  ns.gamma = rq.gamma; ns.alpha = rq.alpha; ns.iter = __builtin_amdgcn_readfirstlane(rq.iter); ns.pad = 0;
+  return ns;
+}
+
 // "everything this wave needs is in the CU's memory queue": counted behind the wave's last request (the compiler may move
 // neither the requests below it nor the count above them)
+template <int ROLE>
 __device__ __forceinline__ void fd_signal_requested(int *cnt) {
   __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
+  asm volatile("; fd_count_in %0" ::"n"(ROLE) : "memory");
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   asm volatile("" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
@@ -168,10 +227,17 @@ __device__ __forceinline__ const double *fd_front_ld_xaddr(const FdFront *ft, in
   return *(const __attribute__((address_space(1))) Ptr *)&ft->xaddr[parity][slot];
 }
 
-__device__ __forceinline__ FdFrontPub fd_front_ld_pub(const FdFront *ft, int q) {
-  typedef int v4i_t __attribute__((ext_vector_type(4)));
-  const v4i_t v = *(const __attribute__((address_space(1))) v4i_t *)&ft->pub[q];
-  return FdFrontPub{v.x, v.y, v.z, v.w};
+// (the record without its first word: the chain waves use {vs_off, pe0, pe1} only, and a word of a load that nobody reads is a
+// register the compiler reuses while the load is in flight -- behind a wait for it, in the middle of the wave's requests)
+struct FdFrontPubTail {
+  int vs_off, pe0, pe1;
+};
+
+__device__ __forceinline__ FdFrontPubTail fd_front_ld_pub_tail(const FdFront *ft, int q) {
+  static_assert(offsetof(FdFrontPub, vs_off) == 4 && offsetof(FdFrontPub, pe0) == 8 && offsetof(FdFrontPub, pe1) == 12, "12 bytes behind pose");
+  typedef int v3i_t __attribute__((ext_vector_type(3), aligned(4)));
+  const v3i_t v = *(const __attribute__((address_space(1))) v3i_t *)&ft->pub[q].vs_off;
+  return FdFrontPubTail{v.x, v.y, v.z};
 }
 
 template <int R>
@@ -484,23 +550,32 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     // ================================================================ the chain: gradient of the public poses, product over the
     // last chunks, step of the workgroup's poses
     const int g = cwv - 4;
+    fd_role_entry<FD_ROLE_CHAIN>();
     // ---- from the head: W / X of the public poses, this wave's quarter of the last chunks, the operands of the tail
     const int npub = hd_npub;
     const int pq = 64 * g + ln;
     const bool pact = pq < npub;
     const int pqc = pact ? pq : 0;
-    // (the lane's public pose -- where its row goes, which edges are its -- from the front table, first: one 16-byte load;
+    // (the lane's public pose -- where its row goes, which edges are its -- from the front table, first: one 12-byte load;
     // records beyond the last public pose are zeros)
-    const FdFrontPub pr = fd_front_ld_pub(ft, pq);
+    const FdFrontPubTail pr = fd_front_ld_pub_tail(ft, pq);
     __builtin_amdgcn_sched_barrier(0);
-    double w[4 * R], x[4 * R];
+    // (of the point only the rotation block is read, tangent_inplace: its 3r entries are requested, nothing of the translation
+    // column -- a pair that straddles the two as 8 bytes, see fd_front_ld_pub_tail)
+    double w[4 * R], x[3 * R];
     {
       const double *Wc = fd_head_buf(hd.buf0, R, n, B_CARRY_W), *Xc = fd_head_buf(hd.buf0, R, n, B_CARRY_X);
 #pragma unroll
       for (int i = 0; i < 2 * R; ++i) {
         // ([entry pair][public pose][2]: one 16-byte load per pair, a wave's 64 lanes one contiguous KB -- half the requests)
-        const double2 tw = ld2(Wc + ((size_t)i * npub + pqc) * 2), tx = ld2(Xc + ((size_t)i * npub + pqc) * 2);
-        w[2 * i] = tw.x; w[2 * i + 1] = tw.y; x[2 * i] = tx.x; x[2 * i + 1] = tx.y;
+        const double2 tw = ld2(Wc + ((size_t)i * npub + pqc) * 2);
+        w[2 * i] = tw.x; w[2 * i + 1] = tw.y;
+        if (2 * i + 1 < 3 * R) {
+          const double2 tx = ld2(Xc + ((size_t)i * npub + pqc) * 2);
+          x[2 * i] = tx.x; x[2 * i + 1] = tx.y;
+        } else if (2 * i < 3 * R) {
+          x[2 * i] = gp(Xc)[((size_t)i * npub + pqc) * 2];
+        }
       }
     }
     FD_STAMP(14);
@@ -533,10 +608,10 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     for (int u = 0; u < 8; ++u) ii[u] = gp(nx.soa_col_e)[((size_t)wtile * wdn + min(u, wdn - 1)) * 64 + wpl];
     const int qi = gp(nx.pub_index_e)[pwc];
     const int sel = as.sel, next_sel = as.next_sel, num_robots = as.num_robots, restart_interval = as.restart_interval;
-    const NestState ns = as.nest_src[sel];
+    const FdNestReq nrq = fd_nest_request(as.nest_src + sel);
     __builtin_amdgcn_s_setprio(3);  // (the chain's instructions go first: the streamers' product shares the LDS with it)
     FD_STAMP(10);
-    fd_signal_requested(&sy[FD_SY_RQ]);
+    fd_signal_requested<FD_ROLE_CHAIN>(&sy[FD_SY_RQ]);
     FD_STAMP(11);
     fd_wait(&sy[FD_SY_E], 2);  // the operands of the shared edges are in LDS
     FD_STAMP(1);
@@ -631,6 +706,9 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     }
     FD_STAMP(6);
     WSYNC();
+    // (the state is brought to scalar registers HERE, where it is first used: the wait for it is a wait for everything the wave
+    // has requested, and directly behind the count-in it stood in front of the chain's first phase)
+    const NestState ns = fd_nest_state(nrq);
     const NestAhead nn = nest_ahead(ns, num_robots, restart_interval);
     const bool ahead_opt = next_sel == sel;
     const bool stats = in && (flags & FD_STATS) != 0, lastat = in && (flags & FD_LASTAT) != 0;
@@ -656,6 +734,7 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
   if (h == 0) {
     // (where its three edges' neighbour poses live, from the front table, FIRST: its quarter of the last chunks is requested
     // while the addresses travel, and the wait in front of the pose loads counts the three address loads alone)
+    fd_role_entry<FD_ROLE_POSES>();
     const double *xa[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) xa[q] = fd_front_ld_xaddr(ft, parity, 64 * q + ln);
@@ -667,7 +746,7 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     FD_STAMP(9);
     const FdArgs &as = fd_args_behind_requests<true>();
     FD_STAMP(10);
-    fd_signal_requested(&sy[FD_SY_RQ]);
+    fd_signal_requested<FD_ROLE_POSES>(&sy[FD_SY_RQ]);
     FD_STAMP(11);
     __builtin_amdgcn_s_setprio(3);
     fd_xn_to_lds<R>(hd_nshared, ln, er, Es);
@@ -686,6 +765,7 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
   // ---- wave 7: look-ahead Nesterov step of iteration k+1 for this workgroup's share of the OTHER agents' poses (one lane
   // per pose, k_step_fe's second wave), every address from the launch's arguments
   {
+    fd_role_entry<FD_ROLE_COEF>();
     FdCf er;
     fd_cf_request(hd.fe_coef, hd_nshared, ln, er);
     FD_STAMP(9);
@@ -716,14 +796,26 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
 #pragma unroll
     for (int k = 0; k < LOOKAHEAD_MAX_AGENTS; ++k) if (k == sel) self_lo = pre[k];
     const int gq = lact ? (q < self_lo ? q : q + n) : 0;
-    int a = 0, lo = 0, na_ = fb.npose[0];
-    const double *ya = fb.ybase[0];
+    // (the lane's agent: its Y array and pose count are VALUES selected among the eight the wave holds in scalar registers.
+    // Left as a choice among fb's fields the compiler selects the field's ADDRESS per lane and fetches the two with vector
+    // loads from the argument segment -- a dependent trip, queued behind the coefficients and M, in front of the wave's first
+    // look-ahead address.  The address is an integer while it is chosen and a global pointer again behind it: the accesses
+    // below stay global_ ones -- one flat access in the kernel and the compiler's counted waits become waits for everything)
+    unsigned long long yb[LOOKAHEAD_MAX_AGENTS];
+    int nb[LOOKAHEAD_MAX_AGENTS];
+#pragma unroll
+    for (int k = 0; k < LOOKAHEAD_MAX_AGENTS; ++k) {
+      yb[k] = (unsigned long long)fb.ybase[k]; nb[k] = fb.npose[k];
+      asm volatile("" : "+s"(yb[k]), "+s"(nb[k]));
+    }
+    int a = 0, lo = 0, na_ = nb[0];
+    unsigned long long yau = yb[0];
 #pragma unroll
     for (int k = 1; k < LOOKAHEAD_MAX_AGENTS; ++k)
-      if (k < num_agents && gq >= pre[k]) { a = k; lo = pre[k]; ya = fb.ybase[k]; na_ = fb.npose[k]; }
+      if (k < num_agents && gq >= pre[k]) { a = k; lo = pre[k]; yau = yb[k]; na_ = nb[k]; }
     // (the work vectors of an agent are one allocation, NBUF x (4r n): everything from its Y array)
     const size_t vlen = (size_t)4 * R * na_;
-    double *yp = const_cast<double *>(ya);
+    double *yp = (double *)(__attribute__((address_space(1))) double *)yau;
     double *xa = yp - (size_t)(B_Y - B_X) * vlen, *va = yp + (size_t)(B_V - B_Y) * vlen;
     const size_t da = (size_t)B_ALT * vlen;
     const double *xr = parity ? xa + da : xa, *yr = parity ? yp + da : yp;
@@ -737,9 +829,9 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
       const double2 tx = ld2(xr + o + 2 * i), tv = ld2(va + o + 2 * i);
       la_x[2 * i] = tx.x; la_x[2 * i + 1] = tx.y; la_v[2 * i] = tv.x; la_v[2 * i + 1] = tv.y;
     }
-    const NestState ns = as.nest_src[sel];
+    const FdNestReq nrq = fd_nest_request(as.nest_src + sel);
     FD_STAMP(10);
-    fd_signal_requested(&sy[FD_SY_RQ]);
+    fd_signal_requested<FD_ROLE_COEF>(&sy[FD_SY_RQ]);
     FD_STAMP(11);
     __builtin_amdgcn_s_setprio(3);
 #if !DPGO_FD_E_EARLY
@@ -751,6 +843,9 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     fd_cur_product<R, M0, NC>(cu, vs, red, tid - 256);
     fd_signal(&sy[FD_SY_F]);
     __builtin_amdgcn_s_setprio(0);
+    // (the state: consumed here, behind the product -- directly behind the count-in the wait for it, which is a wait for all the
+    // wave has requested, stood in front of the coefficients' hand-off E)
+    const NestState ns = fd_nest_state(nrq);
     const NestAhead nn = nest_ahead(ns, num_robots, restart_interval);
     if (lact) {
       const bool st = in, lastat = in && (flags & FD_LASTAT) != 0;
