@@ -1553,6 +1553,21 @@ class Team:
         return dict(candidates=cand, gain=gain, gain_cond=gc, rank=rank, selected=selected, num_selected=n,
                     gain_total=float(gt.value), logdet_joint=float(lj.value), covariance=res)
 
+    def _linear_arguments(self, name, T, method, pairs):
+        """what linear_update and linear_removal (`name`) marshal alike: (T flat and checked against the team's N poses, the
+        rounded estimate when None; the method code; pairs as int32[P, 2]; the outputs T', delta, cov_diag and cov_pairs)"""
+        if method not in (None, "dense", "schur", "nested"):
+            raise ValueError("%s: method must be \"dense\", \"schur\" or \"nested\", not %r" % (name, method))
+        N = int(sum(self.agents[i].n for i in self.ids))
+        if T is None:
+            T = self.round()[1]
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+        if T.size != 12 * N:
+            raise ValueError("%s: T holds %d doubles, the team's %d poses need %d" % (name, T.size, N, 12 * N))
+        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
+        return T, code, pr, (np.zeros(12 * N), np.zeros((N, 6)), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6)))
+
     def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None, columns="blocks"):
         """The estimate and its covariances updated to first order for a set of new closures, without a re-solve (DESIGN.md
         5j): the information-filter update of the whole trajectory.  closures, T, method and max_block as in gate_jointly, whose
@@ -1580,21 +1595,11 @@ class Team:
         agree to round-off, and two calls of either route give the same bytes."""
         if columns not in ("blocks", "solve"):
             raise ValueError("linear_update: columns must be \"blocks\" or \"solve\", not %r" % (columns,))
-        if method not in (None, "dense", "schur", "nested"):
-            raise ValueError("linear_update: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
-        N = int(sum(self.agents[i].n for i in self.ids))
-        if T is None:
-            T = self.round()[1]
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
-        if T.size != 12 * N:
-            raise ValueError("linear_update: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        T, code, pr, (Tn, dx, diag, cross) = self._linear_arguments("linear_update", T, method, pairs)
         cand = np.ascontiguousarray(closures, dtype=MEAS_DTYPE).reshape(-1)
         K = len(cand)
-        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
         res = Covariance()
-        Tn, dx, diag, cross = np.zeros(12 * N), np.zeros((N, 6)), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
         xi, xp, sc = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(3)
-        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         p = lambda a: _d(a) if K else None
         call = lib().dpgo_team_linear_update_solved if columns == "solve" else lib().dpgo_team_linear_update
         _chk(call(self.h, _d(T), code, int(max_block or 0), K, p(cand), len(pr), _d(pr) if len(pr) else None,
@@ -1639,22 +1644,12 @@ class Team:
         pivot_min is not above min_redundancy (a bridge: the record is named), a non-positive pivot of N, or a pivot_min_joint
         not above min_redundancy (the records together leave no redundancy: a cut).  One team only.  Changes no solver state,
         the team's weights included."""
-        if method not in (None, "dense", "schur", "nested"):
-            raise ValueError("linear_removal: method must be \"dense\", \"schur\" or \"nested\", not %r" % (method,))
-        N = int(sum(self.agents[i].n for i in self.ids))
-        if T is None:
-            T = self.round()[1]
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
-        if T.size != 12 * N:
-            raise ValueError("linear_removal: T holds %d doubles, the team's %d poses need %d" % (T.size, N, 12 * N))
+        T, code, pr, (Tn, dx, diag, cross) = self._linear_arguments("linear_removal", T, method, pairs)
         meas = np.ascontiguousarray(measurements, dtype=MEAS_DTYPE).reshape(-1)
         K = len(meas)
         nw = np.zeros(K) if new_weight is None else np.ascontiguousarray(np.broadcast_to(np.asarray(new_weight, dtype=np.float64), (K,)))
-        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
         res = Covariance()
-        Tn, dx, diag, cross = np.zeros(12 * N), np.zeros((N, 6)), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6))
         xi, xl, pm, sc = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(K), np.zeros(4)
-        code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         p = lambda a: _d(a) if K else None
         _chk(lib().dpgo_team_linear_removal(self.h, _d(T), code, int(max_block or 0), K, p(meas), p(nw), C.c_double(min_redundancy),
                                             len(pr), _d(pr) if len(pr) else None, _d(Tn), _d(dx), _d(diag),

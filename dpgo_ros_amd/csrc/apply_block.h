@@ -1,6 +1,6 @@
 // apply_block.h -- the right-hand side V = A^T of the first-order update on the solve: what
 // k_apply_rhs_closures (linear_update.hip) writes for one closure.  In the idiom of linear_update_block.h, whose Jacobians it
-// takes (gate_jacobians, as k_upd_b does): statically indexed 6 x 6 arrays, compiled for the device and for the host, so the
+// takes (gate_jacobians, as k_lin_b does): statically indexed 6 x 6 arrays, compiled for the device and for the host, so the
 // same text is checked on a machine without a GPU (tests/test_apply_host.py).
 //
 // A is the joint gate's (gate_joint.hip): row block k holds J_i^k at the columns of pose i_k and J_j^k at those of pose j_k.

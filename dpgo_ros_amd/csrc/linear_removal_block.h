@@ -1,6 +1,6 @@
 // linear_removal_block.h -- the block arithmetic of the first-order removal or down-weighting of measurements that are in the
-// graph: what k_rem_b, k_rem_n, k_rem_z and k_rem_finish (linear_removal.hip) do with the staged covariance
-// blocks, with B~ and with U~.  In the idiom of linear_update_block.h, whose primitives it uses: statically indexed 6 x 6
+// graph: what k_lin_b<true>, k_lin_finish<true> (linear_frame.h), k_rem_n and k_rem_z (linear_removal.hip) do
+// with the staged covariance blocks, with B~ and with U~.  In the idiom of linear_update_block.h, whose primitives it uses: statically indexed 6 x 6
 // arrays, compiled for the device and for the host, so the same text is checked on a machine without a GPU
 // (tests/test_linear_removal_host.py).
 //
@@ -79,17 +79,6 @@ DPGO_HD double rem_pivot_min(const double S[6][6]) {
 DPGO_HD void rem_whiten(const double x[6], double s_rot, double s_trn, double xt[6]) {
 #pragma unroll
   for (int a = 0; a < 6; ++a) xt[a] = rem_s(a, s_rot, s_trn) * x[a];
-}
-
-// Sigma'_pp (bitwise symmetric) = Sigma_pp (36 doubles, row-major) + the 21 sums of upd_accumulate, and dx = +(B~_p z~)
-DPGO_HD void rem_close_pose(const double *Spp, const double acc[UPD_SUMS], double Sn[6][6], double dx[6]) {
-  int q = 0;
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int c = a; c < 6; ++c, ++q) Sn[a][c] = Sn[c][a] = GATE_LD(Spp, 6 * a + c) + acc[q];
-#pragma unroll
-  for (int a = 0; a < 6; ++a) dx[a] = acc[UPD_TRI + a];
 }
 
 // log det R_k = log det Sigma_meas,k - 6 log dw_k

@@ -1,6 +1,6 @@
 // linear_update_block.h -- the block arithmetic of the first-order update of a trajectory and its covariances for a set of
-// new closures: what k_upd_b, k_upd_m and k_upd_finish (linear_update.hip) do with the staged covariance blocks,
-// with B and with U.  In the idiom of gate_block.h and gate_joint_block.h, whose primitives it uses: statically indexed 6 x 6
+// new closures: what k_lin_b, k_lin_finish (linear_frame.h) and k_upd_m (linear_update.hip) do with the staged
+// covariance blocks, with B and with U.  In the idiom of gate_block.h and gate_joint_block.h, whose primitives it uses: statically indexed 6 x 6
 // arrays, compiled for the device and for the host, so the same text is checked on a machine without a GPU
 // (tests/test_linear_update_host.py).
 //
@@ -87,15 +87,20 @@ DPGO_HD void upd_accumulate_pair(const double u[6], const double b[6], double ac
     for (int c = 0; c < 6; ++c) acc[6 * a + c] = __builtin_fma(u[a], b[c], acc[6 * a + c]);
 }
 
-// Sigma'_pp (36 doubles, row-major, bitwise symmetric) from Sigma_pp (36, row-major) and the 21 sums, and dx = -(B_p z)
-DPGO_HD void upd_close_pose(const double *Spp, const double acc[UPD_SUMS], double Sn[6][6], double dx[6]) {
+// Sigma'_pp (36 doubles, row-major, bitwise symmetric) from Sigma_pp (36, row-major) and the 21 sums, and dx from the 6.  The
+// update: Sigma_pp - the sums, dx = -(B_p z); Add, the removal (linear_removal_block.h): Sigma_pp + the sums, dx = +(B~_p z~)
+template <bool Add>
+DPGO_HD void lin_close_pose(const double *Spp, const double acc[UPD_SUMS], double Sn[6][6], double dx[6]) {
   int q = 0;
 #pragma unroll
   for (int a = 0; a < 6; ++a)
 #pragma unroll
-    for (int c = a; c < 6; ++c, ++q) Sn[a][c] = Sn[c][a] = GATE_LD(Spp, 6 * a + c) - acc[q];
+    for (int c = a; c < 6; ++c, ++q) {
+      const double S = GATE_LD(Spp, 6 * a + c);
+      Sn[a][c] = Sn[c][a] = Add ? S + acc[q] : S - acc[q];
+    }
 #pragma unroll
-  for (int a = 0; a < 6; ++a) dx[a] = -acc[UPD_TRI + a];
+  for (int a = 0; a < 6; ++a) dx[a] = Add ? acc[UPD_TRI + a] : -acc[UPD_TRI + a];
 }
 
 // E = Exp(phi) by Rodrigues, I + a [phi]x + b [phi]x^2 with a = sin(th) / th and b = (1 - cos th) / th^2 formed without

@@ -1,8 +1,9 @@
-"""the bit comparison of profiles/r18_closure_frame.md: every output of the five calls behind the covariance paths (Team.gate /
-relative_covariances, Team.audit, Team.gate_jointly, Team.linear_update, capi.pairwise_consistency) under the inputs of their own
-GPU tests -- the three methods, both orders of the joint gate, the update with and without pairs, duplicated records, candidates
-at pose 0, the K = 65 ballot-tile edge.  The Python entry points are wrapped, the five test files run in this process, and each
-call leaves one line: its name and a SHA-256 per output array, the Covariance records without their times.  One process per
+"""the bit comparison of profiles/r18_closure_frame.md and r28_linear_frame.md: every output of the six calls behind the
+covariance paths (Team.gate / relative_covariances, Team.audit, Team.gate_jointly, Team.linear_update, Team.linear_removal,
+capi.pairwise_consistency) under the inputs of their own GPU tests -- the three methods, both orders of the joint gate, the update
+with and without pairs and on both routes (columns="blocks" and "solve"), the removal at full and fractional weight, duplicated
+records, candidates at pose 0, the K = 65 ballot-tile edge.  The Python entry points are wrapped, the seven test files run in this
+process, and each call leaves one line: its name and a SHA-256 per output array, the Covariance records without their times.  One process per
 library (DPGO_HIP_LIB names the other one); two dumps are compared line by line.
 usage: python profiles/experiments/closure_bits.py OUT.json            run the tests, write the dump
        python profiles/experiments/closure_bits.py A.json B.json       -> calls, arrays, arrays that differ"""
@@ -13,7 +14,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-TESTS = ["test_gpu_gate.py", "test_gpu_gate_joint.py", "test_gpu_audit.py", "test_gpu_linear_update.py", "test_gpu_consistency.py"]
+TESTS = ["test_gpu_gate.py", "test_gpu_gate_joint.py", "test_gpu_audit.py", "test_gpu_linear_update.py", "test_gpu_consistency.py",
+         "test_gpu_linear_removal.py", "test_gpu_linear_update_solved.py"]
 TIMES = ("seconds",)  # the fields of a Covariance record that are measured, not computed
 
 
@@ -71,6 +73,7 @@ capi.Team._gate_call = record("gate_candidates", capi.Team._gate_call)
 capi.Team.audit = record("audit_measurements", capi.Team.audit)
 capi.Team.gate_jointly = record("gate_candidates_jointly", capi.Team.gate_jointly)
 capi.Team.linear_update = record("linear_update", capi.Team.linear_update)
+capi.Team.linear_removal = record("linear_removal", capi.Team.linear_removal)
 capi.pairwise_consistency = record("pairwise_consistency", capi.pairwise_consistency)
 
 rc = pytest.main(["-q", "-x", "-p", "no:cacheprovider"] + [os.path.join(ROOT, "tests", f) for f in TESTS])

@@ -1,6 +1,6 @@
-"""The refusals that the five calls behind the covariance paths share (csrc/closure_frame.h): gate_candidates,
-pairwise_consistency, audit_measurements, gate_candidates_jointly and linear_update word them from the call's name and the
-noun of its records, and each is written out here in full.  tinyGrid3D over 2 robots at the chordal T; three records of which
+"""The refusals that the six calls behind the covariance paths share (csrc/closure_frame.h): gate_candidates,
+pairwise_consistency, audit_measurements, gate_candidates_jointly, linear_update and linear_removal word them from the call's
+name and the noun of its records, and each is written out here in full.  tinyGrid3D over 2 robots at the chordal T; three records of which
 the one at index 1 is malformed, so that the index in the message is exercised.  For every entry point and record: the error
 code, the whole message, and every output still at its sentinel.  Nothing runs on the device but the team's construction and
 the gate's relative-covariance query, which reads the endpoints alone and so takes the records with malformed measurement
@@ -16,6 +16,7 @@ from tests.test_gpu_consistency import fresh_outputs, raw_call
 from tests.test_gpu_covariance_nested import team_of
 from tests.test_gpu_gate import raw_gate
 from tests.test_gpu_gate_joint import raw_joint
+from tests.test_gpu_linear_removal import raw_removal
 from tests.test_gpu_linear_update import raw_update
 from tests.util import DATA
 
@@ -27,10 +28,11 @@ CALLS = {  # entry point: (the call's name, the noun of its records)
     "audit": ("audit_measurements", "record"),
     "joint": ("gate_candidates_jointly", "candidate"),
     "update": ("linear_update", "closure"),
+    "removal": ("linear_removal", "record"),
 }
 ENDPOINT_CASES = ("robot", "pose", "self")
 FIELD_CASES = ("kappa", "tau", "scaled", "reflected", "inf")
-CASES = ENDPOINT_CASES + FIELD_CASES + ("weight",)
+CASES = ENDPOINT_CASES + FIELD_CASES + ("weight", "unweighted")
 FILL = 7.25
 
 
@@ -83,9 +85,12 @@ def malformed(t, entry, case):
     if case == "inf":
         rec["t"][1][2] = np.inf
         return rec, "the measurement of %s 1 is not in SE(3) (|R R^T - I| = 0, det R = 1)" % noun
-    assert case == "weight"
-    rec["weight"][1] = -1.0
-    return rec, "%s 1 has weight = -1: it must be finite and not negative" % noun
+    if case == "weight":
+        rec["weight"][1] = -1.0
+        return rec, "%s 1 has weight = -1: it must be finite and not negative" % noun
+    assert case == "unweighted"
+    rec["weight"][1] = 0.0
+    return rec, "%s 1 has weight = 0: a record must be in the graph at a positive weight" % noun
 
 
 def call(entry, t, T, n, rec):
@@ -114,15 +119,22 @@ def call(entry, t, T, n, rec):
     else:
         pairs = np.array([(1, 2)], dtype=np.int32)
         outs = [np.full(12 * n, FILL), np.full((n, 6), FILL), np.full((n, 6, 6), FILL), np.full((1, 6, 6), FILL), np.full((K, 6), FILL),
-                np.full((K, 6), FILL), np.full(3, FILL)]
-        rc = raw_update(t, T, capi.GATE_DENSE, 0, rec, pairs, outs, res)
+                np.full((K, 6), FILL)]
+        if entry == "update":
+            outs += [np.full(3, FILL)]
+            rc = raw_update(t, T, capi.GATE_DENSE, 0, rec, pairs, outs, res)
+        else:  # (new_weight null: every record goes to weight 0)
+            outs += [np.full(K, FILL), np.full(4, FILL)]
+            rc = raw_removal(t, T, capi.GATE_DENSE, 0, rec, None, 1e-6, pairs, outs, res)
     untouched = [bool((a == (7 if a.dtype == np.int32 else FILL)).all()) for a in outs] + [res.n == 5]
     return rc, capi.lib().dpgo_last_error().decode(), untouched
 
 
 def applies(entry, case):
     if case == "weight":
-        return entry == "audit"  # (the audit alone reads the weight)
+        return entry in ("audit", "removal")  # (the two that read the weight)
+    if case == "unweighted":
+        return entry == "removal"  # (the audit takes a record at weight 0; the removal has no weight to take out of it)
     if case == "self":
         return entry != "consistency"  # (its two endpoints lie in different teams: no pose is joined to itself)
     return True

@@ -140,7 +140,7 @@ int main(int argc, char **argv) {
     double acc[UPD_SUMS] = {0.0};
     for (size_t c = 0; c < n; ++c) upd_accumulate(&U[c * ld + 6 * p], &B[c * ld + 6 * p], z[c], acc);
     double Sn[6][6], d[6], Rp[3][3], tp[3], Rn[3][3], tn[3];
-    rem_close_pose(diag + 36 * p, acc, Sn, d);
+    lin_close_pose<true>(diag + 36 * p, acc, Sn, d);
     gate_load_pose(T, p, Rp, tp);
     upd_retract(Rp, tp, d, Rn, tn);
     upd_store_pose(Rn, tn, &Tn[12 * p]);
