@@ -31,23 +31,25 @@
 // concerned wait at -- the first of them (RQ) orders the requests: waves 4-7 count themselves in behind their last load (and
 // behind no load's DATA: see "the count-in waits for no data" below), the streamers release the stream when all four have
 // (everything the chain needs is in the CU's memory queue in front of it):
-//     waves 0-3  streamers: the carried gradient of c's last chunks -> LDS (C); then the whole P part on their own (N: their
-//                own hand-off; they start their product behind F, the chain's -- the two share the LDS)
+//     waves 0-3  streamers: coefficients of the shared edges -> LDS (E: four of its five counts), the carried gradient of c's
+//                last chunks -> LDS (C); then the whole P part on their own (N: their own hand-off, signalled with the
+//                stream still in flight; they start their product behind F, the chain's -- the two share the LDS -- and
+//                follow the chunks as they land)
 //     waves 4-5  the chain: one public pose per lane (G_j from LDS, projection; rows -> LDS: D) -> their quarters of the
 //                product over the last chunks (F) -> wave 4: reduction, step of the two poses on 16 lanes each
 //                (step_two_poses); wave 5: W
-//     wave 6     neighbour poses of the shared edges -> LDS (E); its quarter of the product behind D (F); the books
-//     wave 7     coefficients of the shared edges -> LDS (E); its quarter of the product (F); look-ahead of the other
-//                agents' poses + Y
+//     wave 6     neighbour poses of the shared edges -> LDS (E: the fifth count); its quarter of the product behind D (F);
+//                the books
+//     wave 7     its quarter of the product (F); look-ahead of the other agents' poses + Y
 //   Waves 4-7 run at raised priority while they are on the chain.
 // The launch's arguments are a HEAD of thirteen plain dwords (step_head.h: the agent's first work vector, M, the partial
 // sums, the packed coefficients, n | npub, nshared | parity | flags, the ids of the last chunks, the workgroup count) and,
 // behind it, everything else in one struct (FdArgs: the descriptor, what the launch needs of the next two agents, ...).  The
 // head is delivered in SGPRs at wave launch (the object is built with -amdgpu-kernarg-preload-count=14; where the firmware
 // does not preload, a prologue the compiler emits fetches the same dwords), FdArgs sits in memory nobody has touched.  So
-// every role forms its FIRST requests from the head alone -- the streamers the carried rows; the chain waves their public
-// pose's record, W / X, their quarter of the last chunks, the operands of the tail; wave 6 the addresses of its edges'
-// neighbour poses, its quarter and, through the addresses, the poses; wave 7 the coefficients and its quarter -- and
+// every role forms its FIRST requests from the head alone -- the streamers the coefficients and the carried rows; the chain
+// waves their public pose's record, W / X, their quarter of the last chunks, the operands of the tail; wave 6 the addresses
+// of its edges' neighbour poses, its quarter and, through the addresses, the poses; wave 7 its quarter -- and
 // only then calls fd_args_behind_requests: one word of every line of FdArgs touched, all in flight at once, and no load of
 // the struct can be moved above that point (where the wait for it would stand in front of those requests: the kernel's one
 // barrier, whose LDS write shares the scalar loads' counter, waited for the arguments in every wave).  Nothing in front of
@@ -89,6 +91,30 @@
 // is enough for the compiler to turn every counted wait into vmcnt(0)).  Trace build, r27 (parent in the same session): the
 // chain waves count in at 2.0-2.2 (2.4-2.8), wave 7 at 2.3-2.4 (2.5-2.8), the stream is released at 2.5-2.6 (2.6-3.0), E is
 // seen at 3.4-3.5 (3.4-3.8).  Product builds: 11.13-11.15 us dispatch to dispatch against 11.43-11.44 for the parent.
+// THE STREAMERS HAND THE COEFFICIENTS OVER, AND FOLLOW THEIR STREAM CHUNK BY CHUNK (r29, profiles/r29_coef_handoff.md; held on
+// the assembly by tests/test_step_coef_handoff_build.py).  The chain held all it needed from about 2.2 us and waited until
+// 3.4 for E: wave 7 requested the packed coefficients first but handed them over behind its other 35 requests and its
+// count-in, in 20 guarded LDS writes.  The streamers are idle there.  They now request the coefficients as their first
+// loads -- five per lane over the 1280 parts, clamped to the last part --, the carried rows behind them, write the
+// coefficients behind counted waits that leave the carried rows in flight, and count at E (five counts: wave 6 and the
+// four of them); a lane beyond the last part writes the clamped part to its own place, so the stretch has no branch.  Wave
+// 7 goes from its count-in straight to D.  Trace build (parent in the same session): E seen at 2.3-2.6 (3.4-3.5), D 3.9-4.3
+// (5.0-5.3), tail end, median over the workgroups, 9.47 (10.40) -- and the PRODUCT build did not separate: 11.10-11.16 us
+// dispatch to dispatch against 11.13-11.16 in five sessions.  The wave ends of a build that stores nothing else showed the
+// streamers leaving WITH the tail wave (0.5-1.8 us before it in the parent): the stream had become as long a path as the
+// chain.  What held it, read off the assembly: one load of the next agent's carried rows scheduled in among the 24 loads of
+// M and one sunk into its guarded write -- vmcnt(4) and vmcnt(0) in front of the hand-off N, a wait for the whole stream, and
+// a product that began behind the last chunk's data.  Now those rows are requested in front of the first load of M
+// (sched_barrier) and written unguarded (clamped index): the writes leave the 24 loads in flight and the product waits
+// chunk by chunk, vmcnt(23) ... (0), from F on -- which the first change had moved a microsecond forward.  The streamers
+// leave 1.0 us earlier (7.4-8.5 against 8.4-9.8), the tail wave decides the launch again.  Product builds, both changes,
+// four sessions with the parent interleaved: 10.71-10.77 us dispatch to dispatch against 11.14-11.16 (-0.39 ... -0.45 us),
+// bench value 0.01113-0.01121 ms against 0.01156-0.01161 (-3.2 ... -3.9 %); every reading below every reading of the parent
+// in all four, for both figures.  r26's second condition (medians apart by more than three times the parent's spread) is
+// reached for the kernel in three sessions of the four and for the value in two: a gain by that definition in two
+// sessions for both figures, not in the other two.  The first change alone is no gain in any session.
+// The chain sees E 0.1 us behind its own count-in, the last of the four: it is not idle for wave 6, whose 30 guarded
+// writes were therefore left as they are.
 // Same arithmetic on the same operands in the same order as k_step_fe / the two-launch sequence: the iterates are BITWISE
 // theirs (tests/test_gpu_fused_step.py, profiles/experiments/fe_fuzz.py).  The Nesterov scalars (nest_ahead), the books
 // (step_books), the look-ahead map (lookahead_map) and the step of the two poses (step_two_poses) are the text of
@@ -109,19 +135,16 @@ static_assert(FD_FRONT_EDGES == FE_MAX_EDGES && FD_FRONT_AGENTS == LOOKAHEAD_MAX
 // layout, the staging of the shared edges' operands, the product over the last chunks
 constexpr int FD_KC = 2048;
 // build switches of the experiments recorded in profiles/r06_deep_carry.md (every one measured SLOWER than the defaults but
-// the last; a fifth, 16-byte loads per lane of the next agent's slab requested in front of the request hand-off, is gone):
+// the last; two more are gone: 16-byte loads per lane of the next agent's slab requested in front of the request hand-off,
+// and wave 7 handing the coefficients over before it requested its look-ahead operands -- the streamers hand them over now):
 // DPGO_FD_GC_LATE -- the carried rows of the current agent requested behind it; DPGO_FD_PACC_WT -- partial sums stored
-// write-through; DPGO_FD_E_EARLY -- wave 7 hands the coefficients over before it requests its look-ahead operands;
-// DPGO_FD_KA_PREFETCH (default on) -- one word of every line of the launch's argument struct touched as soon as the requests
-// formed from the head are out (fd_args_behind_requests)
+// write-through; DPGO_FD_KA_PREFETCH (default on) -- one word of every line of the launch's argument struct touched as soon
+// as the requests formed from the head are out (fd_args_behind_requests)
 #ifndef DPGO_FD_GC_LATE
 #define DPGO_FD_GC_LATE 0
 #endif
 #ifndef DPGO_FD_PACC_WT
 #define DPGO_FD_PACC_WT 0
-#endif
-#ifndef DPGO_FD_E_EARLY
-#define DPGO_FD_E_EARLY 0
 #endif
 #ifndef DPGO_FD_KA_PREFETCH
 #define DPGO_FD_KA_PREFETCH 1
@@ -138,11 +161,21 @@ __device__ __forceinline__ void fd_signal(int *cnt) {
 
 // the roles that count themselves in at FD_SY_RQ.  Each leaves two comment-only markers in the assembly -- "fd_role_entry k" in
 // front of its first request, "fd_count_in k" in front of its count -- which tests/test_step_count_in_build.py walks between
-enum { FD_ROLE_CHAIN = 4, FD_ROLE_POSES = 6, FD_ROLE_COEF = 7 };
+// (FD_ROLE_COEF is wave 7: it handed the coefficients over until r29 and keeps the number the tests know it by.  The
+// streamers do not count in at FD_SY_RQ -- they wait for it; their markers are "fd_role_entry 0" and, in front of the count of
+// their hand-off E, "fd_e_count 0": tests/test_step_coef_handoff_build.py)
+enum { FD_ROLE_STREAM = 0, FD_ROLE_CHAIN = 4, FD_ROLE_POSES = 6, FD_ROLE_COEF = 7 };
 
 template <int ROLE>
 __device__ __forceinline__ void fd_role_entry() {
   asm volatile("; fd_role_entry %0" ::"n"(ROLE));
+}
+
+// the streamers' hand-off of the coefficients: fd_signal with the marker in front of the count
+__device__ __forceinline__ void fd_signal_coef(int *cnt) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  asm volatile("; fd_e_count %0" ::"n"(FD_ROLE_STREAM) : "memory");
+  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // The Nesterov state of the stepped agent is REQUESTED in front of the count-in and CONSUMED behind it.  Read as a struct it
@@ -213,9 +246,10 @@ __device__ __forceinline__ int fd_pos_off(const unsigned char *ord, int pose) {
 //     descriptor and the agents' bases, as this kernel did until r26.  (Measured and dropped, round 6: 64 consecutive 16-byte parts per load --
 //     a quarter of the cache-line requests -- with the address handed from the edge's lane by ds_bpermute: the wave reached
 //     the request hand-off 1.5 us LATER; and with the codes looked up per part: scalar loads inside every trip, 4 us later.)
-//   * wave 7, coefficients: the packed copy [edge][16] (AgentDev::fe_coef) read straight through, 1 KB per load -- 100
-//     cache-line requests where one lane per edge asked for 800 (the kernel's first microseconds are a count of such
-//     requests: ~4400 per CU in front of the stream, and a CU's texture path takes about one a cycle).
+//   * the streamers, coefficients: the packed copy [edge][16] (AgentDev::fe_coef) read straight through, 1 KB per wave and
+//     load -- 100 cache-line requests where one lane per edge asked for 800 (the kernel's first microseconds are a count of
+//     such requests: ~4400 per CU in front of the stream, and a CU's texture path takes about one a cycle).  Wave 7 did this
+//     until r29, behind its other 35 requests and its count-in: see the head of the file.
 template <int R>
 struct FdXn {
   double2 v[3][2 * R];
@@ -256,7 +290,9 @@ template <int R>
 __device__ __forceinline__ void fd_xn_to_lds(int nshared, int ln, const FdXn<R> &xr, double *Es) {
   constexpr int EPE = 4 * R + 16;
   int nsh = nshared;
-  asm volatile("" : "+v"(nsh));  // (see fd_cf_to_lds)
+  // (held in a register: left as an expression of the descriptor the count was RE-READ from the kernel arguments in front of
+  // every store below, each time behind a wait for the scalar load and the LDS store before it; read off the ISA, round 6)
+  asm volatile("" : "+v"(nsh));
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     if (64 * q < nsh && 64 * q + ln < nsh) {
@@ -267,30 +303,36 @@ __device__ __forceinline__ void fd_xn_to_lds(int nshared, int ln, const FdXn<R> 
   }
 }
 
+// The streamers' 256 lanes cover the FE_MAX_EDGES * 8 parts of 16 bytes in five loads per lane (part 256 j + lane: a wave's
+// 64 lanes one contiguous KB), every trip requested whatever the count (see fd_xn_request).  A lane beyond the last part
+// takes the LAST part and, in fd_cf_to_lds, writes it to that part's own place -- the same value to the same address as the
+// lane that owns it: the hand-off has no lane-varying branch and the compiler counts its waits (nshared >= 1 in every team
+// that takes this form: fe_deep_m0).
 struct FdCf {
-  static constexpr int TRIPS = FE_MAX_EDGES * 8 / 64;
+  static constexpr int TRIPS = FE_MAX_EDGES * 8 / 256;
+  static_assert(TRIPS * 256 == FE_MAX_EDGES * 8, "whole trips of the four streamer waves");
   double2 v[TRIPS];
+  int t[TRIPS];  // the (clamped) part of each trip
 };
 
-__device__ __forceinline__ void fd_cf_request(const double *fe_coef, int nshared, int ln, FdCf &cr) {
-  const int nit = nshared * 8;
+__device__ __forceinline__ void fd_cf_request(const double *fe_coef, int nshared, int tid, FdCf &cr) {
+  // (held in a register: left as an expression of the head the count is formed again in front of every store)
+  // (never below part 0, whatever the head says: the allocation behind fe_coef and edge 0's place in LDS always exist)
+  int last = max(nshared * 8 - 1, 0);
+  asm volatile("" : "+v"(last));
 #pragma unroll
-  for (int j = 0; j < FdCf::TRIPS; ++j) cr.v[j] = ld2(fe_coef + 2 * min(64 * j + ln, nit - 1));  // (every trip: see fd_xn_request)
+  for (int j = 0; j < FdCf::TRIPS; ++j) {
+    cr.t[j] = min(256 * j + tid, last);
+    cr.v[j] = ld2(fe_coef + 2 * cr.t[j]);
+  }
 }
 
 template <int R>
-__device__ __forceinline__ void fd_cf_to_lds(int nshared, int ln, const FdCf &cr, double *Es) {
+__device__ __forceinline__ void fd_cf_to_lds(const FdCf &cr, double *Es) {
   constexpr int EPE = 4 * R + 16;
-  // (held in a register: left as an expression of the descriptor the count was RE-READ from the kernel arguments in front of
-  // every one of the 20 stores below, each time behind a wait for the scalar load and the LDS store before it -- 0.9 us
-  // between this wave's last request and the hand-off the chain waits for; read off the ISA, round 6)
-  int nit = nshared * 8;
-  asm volatile("" : "+v"(nit));
 #pragma unroll
-  for (int j = 0; j < FdCf::TRIPS; ++j) {
-    const int t = 64 * j + ln;
-    if (64 * j < nit && t < nit) *reinterpret_cast<double2 *>(Es + (size_t)(t >> 3) * EPE + 4 * R + 2 * (t & 7)) = cr.v[j];
-  }
+  for (int j = 0; j < FdCf::TRIPS; ++j)
+    *reinterpret_cast<double2 *>(Es + (cr.t[j] >> 3) * EPE + 4 * R + 2 * (cr.t[j] & 7)) = cr.v[j];
 }
 
 // the last NC chunks of one column per lane of waves 4-7 (lane l of the four: column group (l >> 5) & 7, k-lane l & 31 -- the
@@ -454,7 +496,10 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
   if (cwv < 4) {
     // ================================================================ streamers
     const int cg = (tid >> 5) & 7, kl = tid & 31;
-    for (int t = N4 * R + tid; t < KC * R; t += 256) vs[t] = 0.0;  // rows beyond the agent's
+    // the coefficients of the shared edges, FIRST: the chain waits for them (E) and for nothing else it does not hold by then
+    fd_role_entry<FD_ROLE_STREAM>();
+    FdCf cf;
+    fd_cf_request(hd.fe_coef, hd_nshared, tid, cf);
     // the rows of this agent's carried gradient that the last NC chunks meet: positions [M0 * 64 R, N4 R)
     constexpr int NGC = ((KC - 64 * M0) * R / 2 + 255) / 256;
     double2 gc[NGC];
@@ -465,8 +510,15 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
       for (int u = 0; u < NGC; ++u) gc[u] = ld2(Gc + min(M0 * 64 * R + 2 * (tid + 256 * u), N4 * R - 2));
     }
 #endif
-    // (FdArgs behind the carried rows' requests.  The streamers touch none of its lines up front -- waves 4-7 do --: the
-    // chain needs these rows only behind its gradient phase, and the stream waits for the request hand-off anyway)
+    // (vmcnt retires in order: the writes below wait for the coefficients alone and leave the carried rows in flight)
+    __builtin_amdgcn_sched_barrier(0);
+    fd_cf_to_lds<R>(cf, Es);
+    fd_signal_coef(&sy[FD_SY_E]);
+    FD_STAMP(8);
+    for (int t = N4 * R + tid; t < KC * R; t += 256) vs[t] = 0.0;  // rows beyond the agent's
+    // (FdArgs behind the hand-off E: its scalar loads share the counter the hand-off's fence waits for.  The streamers touch
+    // none of its lines up front -- waves 4-7 do --: the chain needs the carried rows only behind its gradient phase, and the
+    // stream waits for the request hand-off anyway)
     const FdArgs &as = fd_args_behind_requests<false>();
     const FdNext &nx = as.nx;
     const int cold = 8 * bx + cg;
@@ -499,14 +551,19 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     double2 gn[NGN];
 #pragma unroll
     for (int u = 0; u < NGN; ++u) gn[u] = ld2(nx.Gd + min(2 * (tid + 256 * u), M0 * 64 * R - 2));
+    // (every row of the vector requested in front of the first load of M, and written without a guard -- a lane beyond the
+    // last pair writes the clamped pair to its own place: a row load the scheduler moves in among the loads of M, or sinks
+    // into a guarded write, puts a wait for the WHOLE stream in front of the hand-off N, and the product then starts behind
+    // the last chunk's data where it can follow the chunks as they land: its waits are counted, vmcnt(M0 - 1) ... (0))
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("; fd_stream_entry 0");
 #pragma unroll
     for (int i = 0; i < M0; ++i) mn[i] = ld2_nt(Md + min(2 * kl + 64 * (int)nx.ord_d[i], N4d - 2));
     FD_STAMP(12);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int u = 0; u < NGN; ++u) {
-      const int tt = 2 * (tid + 256 * u);
-      if (tt < M0 * 64 * R) *reinterpret_cast<double2 *>(&vs[tt]) = gn[u];
-    }
+    for (int u = 0; u < NGN; ++u) *reinterpret_cast<double2 *>(&vs[min(2 * (tid + 256 * u), M0 * 64 * R - 2)]) = gn[u];
+    asm volatile("; fd_n_count 0" ::: "memory");
     fd_signal(&sy[FD_SY_N]);
     fd_wait(&sy[FD_SY_N], 4);
     fd_wait(&sy[FD_SY_F], 4);  // (the chain's product first: the two share the LDS)
@@ -613,7 +670,7 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     FD_STAMP(10);
     fd_signal_requested<FD_ROLE_CHAIN>(&sy[FD_SY_RQ]);
     FD_STAMP(11);
-    fd_wait(&sy[FD_SY_E], 2);  // the operands of the shared edges are in LDS
+    fd_wait(&sy[FD_SY_E], 5);  // the operands of the shared edges are in LDS: wave 6's poses, the four streamers' coefficients
     FD_STAMP(1);
     if (pact) {
       // G_j from LDS: g[c][a] -= x[cp][a] coef[cp + 4c], edge after edge and cp after cp for every entry (g_row_range's order)
@@ -766,24 +823,13 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
   // per pose, k_step_fe's second wave), every address from the launch's arguments
   {
     fd_role_entry<FD_ROLE_COEF>();
-    FdCf er;
-    fd_cf_request(hd.fe_coef, hd_nshared, ln, er);
-    FD_STAMP(9);
     FdCur<R, NC> cu;
     fd_cur_request<R, M0, NC>(hd, N4, bx, nblk, tid - 256, cu);
+    FD_STAMP(9);
     const FdArgs &as = fd_args_behind_requests<true>();
     const FeBases &fb = as.fb;
     const int sel = as.sel, next_sel = as.next_sel, next3_sel = as.next3_sel, num_agents = as.num_agents;
     const int num_robots = as.num_robots, restart_interval = as.restart_interval;
-    // (the coefficients go to LDS as soon as they are here -- the chain waits for them --, the look-ahead operands are
-    // requested behind that)
-#if DPGO_FD_E_EARLY
-    __builtin_amdgcn_sched_barrier(0);
-    fd_cf_to_lds<R>(hd_nshared, ln, er, Es);
-    fd_signal(&sy[FD_SY_E]);
-    FD_STAMP(8);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     int pre[LOOKAHEAD_MAX_AGENTS + 1];
     pre[0] = 0;
 #pragma unroll
@@ -834,11 +880,6 @@ __global__ __launch_bounds__(512) void k_step_fd(double *hd_buf0, const double *
     fd_signal_requested<FD_ROLE_COEF>(&sy[FD_SY_RQ]);
     FD_STAMP(11);
     __builtin_amdgcn_s_setprio(3);
-#if !DPGO_FD_E_EARLY
-    fd_cf_to_lds<R>(hd_nshared, ln, er, Es);
-    fd_signal(&sy[FD_SY_E]);
-    FD_STAMP(8);
-#endif
     fd_wait(&sy[FD_SY_D], 2);  // this wave's quarter of the product over the last chunks
     fd_cur_product<R, M0, NC>(cu, vs, red, tid - 256);
     fd_signal(&sy[FD_SY_F]);
