@@ -140,7 +140,7 @@ dpgo_team_gate_candidates dpgo_team_audit_measurements dpgo_team_pairwise_consis
 dpgo_team_gate_candidates_jointly dpgo_team_linear_update dpgo_team_select_candidates dpgo_team_linear_removal
 dpgo_team_gate_candidates_across dpgo_team_audit_measurements_across
 dpgo_team_covariance_apply dpgo_team_linear_update_solved dpgo_team_refine dpgo_team_covariance_apply_across
-dpgo_team_refine_across""".split()
+dpgo_team_refine_across dpgo_team_linear_update_across""".split()
 
 
 class DpgoError(RuntimeError):
@@ -1568,7 +1568,8 @@ class Team:
         code = {None: GATE_DENSE, "dense": GATE_DENSE, "schur": GATE_SCHUR, "nested": GATE_NESTED}[method]
         return T, code, pr, (np.zeros(12 * N), np.zeros((N, 6)), np.zeros((N, 6, 6)), np.zeros((len(pr), 6, 6)))
 
-    def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None, columns="blocks"):
+    def linear_update(self, closures, T=None, method=None, max_block=None, pairs=None, columns=None, transport=None,
+                      owner_of_robot=None):
         """The estimate and its covariances updated to first order for a set of new closures, without a re-solve (DESIGN.md
         5j): the information-filter update of the whole trajectory.  closures, T, method and max_block as in gate_jointly, whose
         A, R and M = A Sigma A^T + R these are: with B = Sigma A^T, dx = -B M^-1 xi, Sigma' = Sigma - B M^-1 B^T and
@@ -1592,19 +1593,40 @@ class Team:
         its own factors (covariance_apply) and asks it for `pairs` alone: the time no longer grows with the
         blocks extracted.  Under "solve" method is "dense" or "nested" ("schur" raises DpgoError: "nested" with no robot split
         has its sets), and the outputs are NOT bitwise those of "blocks", because the sums of B come in another order; they
-        agree to round-off, and two calls of either route give the same bytes."""
-        if columns not in ("blocks", "solve"):
+        agree to round-off, and two calls of either route give the same bytes.
+        With a transport (a team split across participants, owner_of_robot as for covariances; DESIGN.md 5j "Across teams"):
+        the solve on the Schur path across is the only route (columns None or "solve", method None or "schur"; "blocks", any
+        other method or a max_block raises ValueError before any transport call).  The call is collective: every participant
+        passes the same closures, whose (r1, p1) -> (r2, p2) may name any robot of the problem, and the same pairs, which
+        name poses of the whole problem (robots by id, then poses; pose 0 is robot 0's first).  T (None: the rounding
+        across), and T, delta and cov_diag of the dict, are this team's poses in team order; cov_pairs, xi, xi_post, the
+        scalars and the covariance record are complete and identical on every participant.  Every output is the same bits
+        whatever the split; it is not bitwise the single team's call.  A ValueError (T's size) is raised on this participant
+        alone before the library is called: check shapes before a collective call."""
+        if columns not in (None, "blocks", "solve"):
             raise ValueError("linear_update: columns must be \"blocks\" or \"solve\", not %r" % (columns,))
+        if transport is not None:
+            if columns == "blocks":
+                raise ValueError("linear_update: a team split across participants has the solve alone (columns=\"blocks\" with a "
+                                 "transport)")
+            T = self._across_args("linear_update", T, method, max_block, transport, owner_of_robot)
         T, code, pr, (Tn, dx, diag, cross) = self._linear_arguments("linear_update", T, method, pairs)
         cand = np.ascontiguousarray(closures, dtype=MEAS_DTYPE).reshape(-1)
         K = len(cand)
         res = Covariance()
         xi, xp, sc = np.zeros((K, 6)), np.zeros((K, 6)), np.zeros(3)
         p = lambda a: _d(a) if K else None
-        call = lib().dpgo_team_linear_update_solved if columns == "solve" else lib().dpgo_team_linear_update
-        _chk(call(self.h, _d(T), code, int(max_block or 0), K, p(cand), len(pr), _d(pr) if len(pr) else None,
-                  _d(Tn), _d(dx), _d(diag), _d(cross) if len(pr) else None, _d(xi), _d(xp), _d(sc),
-                  C.byref(res)), "linear_update")
+        if transport is not None:
+            own = _owner_array(owner_of_robot)
+            _chk(lib().dpgo_team_linear_update_across(self.h, C.byref(transport.struct), _d(own), _d(T), K, p(cand), len(pr),
+                                                      _d(pr) if len(pr) else None, _d(Tn), _d(dx), _d(diag),
+                                                      _d(cross) if len(pr) else None, _d(xi), _d(xp), _d(sc), C.byref(res)),
+                 "linear_update_across")
+        else:
+            call = lib().dpgo_team_linear_update_solved if columns == "solve" else lib().dpgo_team_linear_update
+            _chk(call(self.h, _d(T), code, int(max_block or 0), K, p(cand), len(pr), _d(pr) if len(pr) else None,
+                      _d(Tn), _d(dx), _d(diag), _d(cross) if len(pr) else None, _d(xi), _d(xp), _d(sc),
+                      C.byref(res)), "linear_update")
         return dict(T=Tn, delta=dx, cov_diag=diag, cov_pairs=cross, xi=xi, xi_post=xp, d2_joint=float(sc[0]), logdet_M=float(sc[1]),
                     logdet_R=float(sc[2]), information_gain=0.5 * float(sc[1] - sc[2]), covariance=res)
 

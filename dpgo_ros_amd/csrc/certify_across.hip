@@ -314,8 +314,9 @@ int Across::begin(dpgo_team_t *t, const dpgo_transport_t *tr_, const int *owner_
         // (op 4, 5, the gate and the audit: the number of records and the hash of the record list)
         // (op 6, Sigma applied to vectors: the first real field carries num_cols)
         // (op 7, the refinement: flags carries the ladder, the two real fields grad_tol and armijo)
-        const bool recs = op == 4 || op == 5;
-        const char *name = (op == 7 && f == 9) ? "ladder" : (op == 7 && f == 10) ? "grad_tol" : (op == 7 && f == 11) ? "armijo"
+        // (op 8, the update across teams: as 4 and 5; the hash covers the pair list too and the integer field carries num_pairs)
+        const bool recs = op == 4 || op == 5 || op == 8;
+        const char *name = (op == 8 && f == 12) ? "num_pairs" : (op == 7 && f == 9) ? "ladder" : (op == 7 && f == 10) ? "grad_tol" : (op == 7 && f == 11) ? "armijo"
                            : (op == 6 && f == 10) ? "num_cols" : (op == 3 && f == 10) ? "num_pairs" : (op == 3 && f == 11) ? "the pair list"
                            : (recs && f == 10)  ? "the number of records" : (recs && f == 11) ? "the record list" : XA_FIELD[f];
         err = "the participants disagree on " + std::string(name) + " (rank 0 and rank " + std::to_string(q) + ")";

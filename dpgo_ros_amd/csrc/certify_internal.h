@@ -199,19 +199,33 @@ struct CovEpilogue {
 // every halo slot the separator pose whose rows 6 q .. 6 q + 5 of x_S are the slot's rows of X (-1: the problem's fixed pose,
 // whose rows are zero, or a slot of a neighbour that lives here).  All device pointers are ordered on the path's stream and live
 // until the path has drained it behind taken().
+// With pairs beside the app (the first-order update across teams, DESIGN.md 5j "across teams") the view also hands the blocks
+// back: diag, the N diagonal blocks of this participant's poses on the device, and blocks_h, the host image of those N blocks
+// and behind them the num_pairs pair blocks, complete after allgather C (both live as long as Td does).
 struct CovAcrossView {
-  const double *Td = nullptr, *xS = nullptr;
-  int N = 0, halo_slots = 0, nS = 0;
+  const double *Td = nullptr, *xS = nullptr, *diag = nullptr, *blocks_h = nullptr;
+  int N = 0, halo_slots = 0, nS = 0, num_pairs = 0;
   std::vector<int> halo_sep;
 };
+// An app with a record list of its own (op != 0; the update across teams) names itself and fills the agreement record: `op`,
+// the two real fields (agree_num, agree_hash) and the integer one (agree_int) of Across::begin.  The path calls resolve()
+// behind begin, when the global numbering is known -- DPGO_OK, 1: a refusal in msg, the same words on every participant, 2: the
+// transport is dead -- and exchange() behind taken() whether or not this participant still works (x.bad): the app's own
+// allgathers, the same number on every participant, and behind them its device work.  The defaults do nothing: an app
+// without them queues no launch and sends no byte more.
 struct CovApply {
   CovAcrossView view;
   int num_cols = 0;
   double *X = nullptr;
   double ms_products = 0.0, flops = 0.0;  // the apply's own products, for the caller's DPGO_TIMING line
   std::string argerr, memerr;
+  const char *name = nullptr;
+  int op = 0, agree_int = 0;
+  double agree_num = 0.0, agree_hash = 0.0;
   virtual int rhs(const double *Td, int N, double *V, hipStream_t stream) = 0;
   virtual int taken(int /*N*/, hipStream_t /*stream*/) { return DPGO_OK; }
+  virtual int resolve(Across & /*x*/, std::string & /*msg*/) { return DPGO_OK; }
+  virtual int exchange(Across & /*x*/, hipStream_t /*stream*/) { return DPGO_OK; }
   virtual ~CovApply() = default;
 };
 

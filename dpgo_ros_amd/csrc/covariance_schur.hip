@@ -497,7 +497,7 @@ enum { XF_OK = 0, XF_PIVOT = 1, XF_MEMORY = 2, XF_LOCAL = 3 };
 int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
                             const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, AcrossEpilogue *epi,
                             CovApply *app) {
-  const char *what = epi ? epi->name : app ? "covariance_apply_across" : "marginal_covariances_across";
+  const char *what = epi ? epi->name : app ? (app->name ? app->name : "covariance_apply_across") : "marginal_covariances_across";
   if (res) std::memset(res, 0, sizeof *res);
   const int cols = app ? app->num_cols : 0;
   std::string argerr;
@@ -518,9 +518,12 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
   }
   Across x;
   // (op 6, Sigma applied to vectors: the first real field carries num_cols)
-  const double agree_num = epi ? epi->num : app ? (double)cols : (double)num_pairs;
-  const double agree_hash = !argerr.empty() ? 0.0 : epi ? epi->hash : pair_hash(pairs, num_pairs);
-  if (x.begin(t, tr, owner, what, epi ? epi->op : app ? 6 : 3, 3, flags, agree_num, agree_hash, 0, argerr.empty() ? nullptr : argerr.c_str())) {
+  // (op 8, the update across teams: the app's own record -- the number of records, the hash of records and pairs, num_pairs)
+  const bool own = app && app->op;
+  const double agree_num = epi ? epi->num : own ? app->agree_num : app ? (double)cols : (double)num_pairs;
+  const double agree_hash = !argerr.empty() ? 0.0 : epi ? epi->hash : own ? app->agree_hash : pair_hash(pairs, num_pairs);
+  if (x.begin(t, tr, owner, what, epi ? epi->op : own ? app->op : app ? 6 : 3, 3, flags, agree_num, agree_hash, own ? app->agree_int : 0,
+              argerr.empty() ? nullptr : argerr.c_str())) {
     // (a participant whose own records were refused says why in the words of the single team's call)
     if (epi && !epi->argerr.empty()) set_err(std::string(what) + ": " + epi->argerr);
     else if (app && !app->argerr.empty()) set_err(std::string(what) + ": " + app->argerr);
@@ -534,6 +537,12 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     if (epi->resolve(x, msg)) { set_err(std::string(what) + ": " + msg); return DPGO_ERR; }
     pairs = epi->pairs.data();
     num_pairs = (int)(epi->pairs.size() / 2);
+  }
+  if (app) {  // (an app with records of its own: its endpoints, and what it gathers before the path starts)
+    std::string msg;
+    const int rc = app->resolve(x, msg);
+    if (rc == 2) return x.fail();
+    if (rc) { set_err(std::string(what) + ": " + msg); return DPGO_ERR; }
   }
   for (int k = 0; k < 2 * num_pairs; ++k)
     if (pairs[k] < 0 || pairs[k] >= NG) {  // (the same on every participant: nobody goes on)
@@ -1063,6 +1072,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     {  // what a step along X needs of the poses behind this participant's own (CovAcrossView): host tables, no launch
       CovAcrossView &v = app->view;
       v.Td = d_T.p; v.N = N; v.halo_slots = halo_slots; v.xS = nS > 0 ? d_xS.p : nullptr; v.nS = nS;
+      v.diag = outd; v.blocks_h = hout.data(); v.num_pairs = num_pairs;
       v.halo_sep.assign(halo_slots, -1);
       for (int k = 0; k < na; ++k)
         for (size_t q = 0; q < t->ag[k]->np.size(); ++q) {
@@ -1079,6 +1089,7 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     return DPGO_OK;
   };
   if (app && !x.bad && phase_apply()) x.fail_local(g_err);
+  if (app && app->exchange(x, s)) return x.fail();
   // ---- the step behind the blocks (the gate, the audit).  Allgather D: per endpoint of the records, sorted by global pose,
   // 12 doubles of T and the 36 of its diagonal block from the participant that holds it, zeros from everyone else (pose 0's
   // block is zero with its holder too).  Then every participant holds the compact tables and runs all records itself.

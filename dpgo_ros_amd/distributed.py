@@ -771,3 +771,42 @@ def refine(backend_or_team, dist, owner_of_robot, T=None, gather=False, **kw):
             o += 12 * n
     out["T"] = np.concatenate([blocks[i] for i in sorted(blocks)])
     return out
+
+
+def linear_update(backend_or_team, dist, owner_of_robot, closures, T=None, pairs=None, gather=False):
+    """Team.linear_update of an estimate split across ranks (one team per rank; DESIGN.md 5j "Across teams"): the closures, the
+    same list on every rank, may join robots held by different ranks; pairs name poses of the whole problem (robots by id, then
+    poses); T this rank's poses in team order (None: the rounding across).  The dict of Team.linear_update with T, delta and
+    cov_diag this rank's poses; cov_pairs, xi, xi_post, the scalars and the covariance record are identical on every rank.  With
+    gather=True T, delta and cov_diag are those of the whole problem instead, in global pose order (robots by id) and identical
+    on every rank: one allgather of the local poses behind one of their lengths, the way covariance_apply gathers its rows.  A T
+    of the wrong size raises ValueError on this rank before the library is called: the other ranks then wait in the agreement
+    record until the transport gives up, as for the other calls across ranks.  None on a rank that owns no robot."""
+    p = _participants(backend_or_team, dist, owner_of_robot)
+    if p is None:
+        return None
+    team, tr, own = p
+    out = team.linear_update(closures, T=T, pairs=pairs, transport=tr, owner_of_robot=own)
+    if not gather:
+        return out
+    # every rank's poses robot by robot (12 + 6 + 36 doubles per pose), padded to one length, then placed by robot id
+    ids = list(team.ids)
+    head = np.array([len(ids)] + ids + [team.agents[i].n for i in ids], dtype=np.float64)
+    rows = np.concatenate([out["T"].reshape(-1, 12), out["delta"].reshape(-1, 6), out["cov_diag"].reshape(-1, 36)], axis=1).reshape(-1)
+    sizes = tr.allgather(np.array([head.size + rows.size], dtype=np.float64)).astype(int)
+    mine = np.zeros(int(sizes.max()))
+    mine[:head.size], mine[head.size:head.size + rows.size] = head, rows
+    allr = tr.allgather(mine).reshape(tr.world, mine.size)
+    blocks = {}
+    for q in range(tr.world):
+        k = int(allr[q, 0])
+        rid, rn = allr[q, 1:1 + k].astype(int), allr[q, 1 + k:1 + 2 * k].astype(int)
+        o = 1 + 2 * k
+        for i, n in zip(rid, rn):
+            blocks[int(i)] = allr[q, o:o + 54 * n].reshape(n, 54)
+            o += 54 * n
+    whole = np.concatenate([blocks[i] for i in sorted(blocks)], axis=0)
+    out["T"] = np.ascontiguousarray(whole[:, :12]).reshape(-1)
+    out["delta"] = np.ascontiguousarray(whole[:, 12:18])
+    out["cov_diag"] = np.ascontiguousarray(whole[:, 18:]).reshape(-1, 6, 6)
+    return out

@@ -545,7 +545,8 @@ int dpgo_team_gate_candidates_jointly(dpgo_team_t *t, const double *T, int metho
  * index outside [0, N); the N m pair blocks (288 bytes each), B and U (288 N K bytes each) and the three matrices of order 6 K
  * that do not fit the free device memory, or more than INT32_MAX pair blocks, with the bytes named; a non-positive pivot in M,
  * with the pivot block named.  Every refusal of the chosen covariance path carries over with its own message; the outputs are
- * then untouched and *res all zero.  *res: the path's own record.  Changes no solver state.  There is no call across teams. */
+ * then untouched and *res all zero.  *res: the path's own record.  Changes no solver state.  One team: a split team calls
+ * dpgo_team_linear_update_across. */
 int dpgo_team_linear_update(dpgo_team_t *t, const double *T, int method /* DPGO_GATE_* */, int max_block, int num,
                             const dpgo_measurement_t *closures, int num_pairs, const int *pairs, double *T_new,
                             double *delta /* 6 N */, double *cov_diag /* 36 N */, double *cov_pairs, double *xi, double *xi_post,
@@ -845,6 +846,46 @@ int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_transport_t *
  * path's record, identical on every participant.  Changes no solver state. */
 int dpgo_team_covariance_apply_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
                                       const double *T, int num_cols, const double *V, double *X, dpgo_covariance_t *res);
+/* ---- dpgo_team_linear_update over a team split across participants (csrc/linear_update.hip; DESIGN.md 5j, "Across teams") ----
+ * Collective: every participant calls it with its own team, the same owner table, the same closures and the same pairs.  The
+ * closures' (r1, p1) -> (r2, p2) may name any robot of the problem; `pairs` holds poses of the whole problem in the global
+ * numbering (robots by id, then poses; pose 0 is robot 0's first).  T, T_new, delta (6 N_loc) and cov_diag (36 N_loc) are this
+ * participant's poses in team order; cov_pairs, xi, xi_post, scalars and the scalars of *res are complete and identical on every
+ * participant.  The definitions are dpgo_team_linear_update's: B = Sigma A^T, M = A B + R, G = M^-1, z = G xi, U = B G,
+ * dx = -B z, Sigma' = Sigma - U B^T, T' = T [+] dx, xi_post = R z; the fixed pose is the PROBLEM's pose 0.
+ * With C the distinct poses among the closures' endpoints and the pairs, sorted by global pose:
+ *   allgather E    12 doubles of T per compact pose from its holder, zeros from everyone else: the table T_C, identical bytes
+ *                  everywhere, from which one lane per closure forms J_i, J_j and writes J^T into column block k of V at the rows
+ *                  of the endpoints that are this participant's (pose 0's rows stay zero);
+ *   the path       dpgo_team_marginal_covariances_across with `pairs` and that V: B_loc = Sigma V on this participant's rows, the
+ *                  local diagonal blocks and the pair blocks;
+ *   allgather F    6 x 6 K doubles of B per compact pose from its holder alone, padded to the participant that holds most:
+ *                  B_C (6 C x 6 K);
+ *   order 6 K      M, its inverse and log det, z, the figures and U_C = B_C G on every participant from identical bytes, by the
+ *                  kernels of dpgo_team_linear_update with N := C; U_loc = B_loc G and the reduction over this participant's
+ *                  poses; Sigma'_pq = Sigma_pq - U_p B_q^T on the compact tables.
+ * Transport calls: those of dpgo_team_marginal_covariances_across with the same pairs and two more allgathers (E and F),
+ * whatever K, the pairs and the split; the agreement (num, num_pairs and a hash of the records and the pairs) rides in the
+ * path's own record.  For a given problem, T, closures and pairs every output is the same bits whatever the split, one
+ * participant that holds every robot included, and two calls give the same bytes; no floating-point atomics.  It is not bitwise
+ * the single team's call.
+ * Refused with DPGO_ERR and a message that begins "linear_update_across:".  Decided on the host before any device work and
+ * carried in the agreement record (its participant reads its own words, the others "rank q: invalid arguments"): a NULL among
+ * the required arguments, num <= 0, num_pairs < 0, a closure that joins a pose to itself, kappa or tau not positive and finite,
+ * R~ outside SO(3), and V, X, U (288 N_loc K bytes each), the three matrices of order 6 K and the compact tables (at most
+ * 2 K + 2 num_pairs poses) above the free device memory, with the bytes named, decided before a record is read.  A NULL t or tr
+ * returns at once.  A num or a record or pair list that differs between participants is refused on all of them ("the number of
+ * records", "the record list": the hash covers the pairs, so a num_pairs that differs reads as the latter); an endpoint or a pair pose outside the problem in the same words everywhere.  A
+ * non-positive pivot of M is refused with the pivot block named, the same on every participant.  The refusals of
+ * dpgo_team_marginal_covariances_across (T outside SE(3), a pivot, memory, measurement sets that differ) carry over in their own
+ * words.  A refused call leaves every output untouched and *res all zero on every participant, and the transport usable.
+ * Changes no solver state. */
+int dpgo_team_linear_update_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
+                                   const double *T /* 12 N_loc */, int num, const dpgo_measurement_t *closures, int num_pairs,
+                                   const int *pairs /* GLOBAL poses */, double *T_new /* 12 N_loc */, double *delta /* 6 N_loc */,
+                                   double *cov_diag /* 36 N_loc */, double *cov_pairs /* 36 num_pairs */, double *xi,
+                                   double *xi_post /* 6 num each */, double *scalars /* d2_joint, logdet_M, logdet_R */,
+                                   dpgo_covariance_t *res);
 /* ---- dpgo_team_refine over a team split across participants (csrc/refine.hip; DESIGN.md 5n, "Across teams") ----
  * Collective: every participant calls it with its own team and the same owner table, max_iters, grad_tol, armijo and ladder.
  * T, T_out: this participant's 12 N_loc doubles in team order.  history, *out, *res and the status codes are those of
