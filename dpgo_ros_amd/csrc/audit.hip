@@ -129,7 +129,7 @@ const ClosureCall AUDIT_ACROSS = {"audit_measurements_across", "record"};
 
 // the same step behind the compact tables of the path across teams: every participant runs all K records
 struct AuditAcross : RecordsAcross<AuditRec>, AuditWork {
-  AuditAcross() : RecordsAcross<AuditRec>(&AUDIT_ACROSS, &AuditRec::blk) {}
+  AuditAcross() : RecordsAcross<AuditRec>(&AUDIT_ACROSS, &AuditRec::blk, 5) {}
   int run(const AcrossStage &st) override {
     if (!inside(st)) { set_err("a record lies outside the staged blocks"); return DPGO_ERR; }
     if (AuditWork::alloc(rec.size(), "audit_measurements_across") || ev.create()) return DPGO_ERR;
@@ -192,7 +192,6 @@ extern "C" int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_tr
   const ClosureCall &A = AUDIT_ACROSS;
   if (res) std::memset(res, 0, sizeof *res);
   AuditAcross epi;
-  epi.op = 5;
   epi.min_redundancy = min_redundancy;
   epi.want_sigma = sigma_loo != nullptr;
   // ---- the refusals of the audit itself, in the single team's order and words: decided here, told to everyone by the
@@ -229,17 +228,17 @@ extern "C" int dpgo_team_audit_measurements_across(dpgo_team_t *t, const dpgo_tr
       h.add(m.r1); h.add(m.p1); h.add(m.r2); h.add(m.p2);
       h.add(c.m, sizeof(double) * 15);
     }
-    epi.num = num;
-    epi.hash = h.value();
+    epi.agree_num = num;
+    epi.agree_hash = h.value();
   }
-  if (const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, T, DPGO_COV_SCHUR, 0, nullptr, nullptr, nullptr, res, &epi)) {
-    if (res) std::memset(res, 0, sizeof *res);
-    return rc;
-  }
+  SchurAcrossArgs a(t, tr, owner_rank_of_robot, T);
+  a.res = res;
+  a.step = &epi;
+  if (const int rc = covariance_schur_across(a)) return rc;  // (res is then all zero)
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr, "audit_measurements_across: %d records on %zu pair blocks and %zu endpoints, audit kernel %.3f ms\n", num,
-                 epi.pairs.size() / 2, epi.endpoints.size(), epi.ev.ms());
+                 epi.pairs.size() / 2, epi.ends.size(), epi.ev.ms());
   epi.copy_out((size_t)num, xi, xi_loo, d2, rho, pmin, sigma_loo);
   return DPGO_OK;
 }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "kernel_common.h"
+#include "schur_across_plan.h"
 #include "team_internal.h"
 
 namespace dpgo {
@@ -186,46 +187,11 @@ struct CovEpilogue {
 // CovFrame::begin has T on the device -- rhs() queues on `stream` whatever writes every element of V outside pose 0's rows,
 // which are not read -- forms X = Sigma V from its own factors without a block of Sigma, and sets X before it runs the
 // epilogue: the pointer stays valid as long as the staged blocks do.  Pose 0's rows of X are zero bits.
-// Across teams (covariance_schur_across, which has no CovEpilogue) N is this participant's N_loc and pose 0 the problem's, the
-// agreement record carries num_cols, and the path calls taken() once X is set, before its closing status word: taken() queues
-// on `stream` whatever reads X; the path drains the stream.  Before taken() the path fills `view` (CovAcrossView): what a step
-// that moves T along X needs of the poses behind this participant's own -- it costs no launch and no transport call, and an app
-// that ignores it changes nothing.  argerr: this participant's own refusal, which the others learn from
-// the agreement record; memerr: V and X alone exceed the device (V was then not read), told as the path's memory refusal.
-// What covariance_schur_across holds when it calls CovApply::taken(): T with its halo on the device (N poses of this
-// participant in team order, then halo_slots poses, slot hoffs[k] + s the pose np[s] of local robot k; the slots of remote
-// neighbours are filled, the others are not read by anyone), x_S = Sigma_SS r_S of the WHOLE problem (6 |S| x num_cols, leading
-// dimension nS: after allgather B every participant knows every robot's public frames, so x_S is whole everywhere), and for
-// every halo slot the separator pose whose rows 6 q .. 6 q + 5 of x_S are the slot's rows of X (-1: the problem's fixed pose,
-// whose rows are zero, or a slot of a neighbour that lives here).  All device pointers are ordered on the path's stream and live
-// until the path has drained it behind taken().
-// With pairs beside the app (the first-order update across teams, DESIGN.md 5j "across teams") the view also hands the blocks
-// back: diag, the N diagonal blocks of this participant's poses on the device, and blocks_h, the host image of those N blocks
-// and behind them the num_pairs pair blocks, complete after allgather C (both live as long as Td does).
-struct CovAcrossView {
-  const double *Td = nullptr, *xS = nullptr, *diag = nullptr, *blocks_h = nullptr;
-  int N = 0, halo_slots = 0, nS = 0, num_pairs = 0;
-  std::vector<int> halo_sep;
-};
-// An app with a record list of its own (op != 0; the update across teams) names itself and fills the agreement record: `op`,
-// the two real fields (agree_num, agree_hash) and the integer one (agree_int) of Across::begin.  The path calls resolve()
-// behind begin, when the global numbering is known -- DPGO_OK, 1: a refusal in msg, the same words on every participant, 2: the
-// transport is dead -- and exchange() behind taken() whether or not this participant still works (x.bad): the app's own
-// allgathers, the same number on every participant, and behind them its device work.  The defaults do nothing: an app
-// without them queues no launch and sends no byte more.
 struct CovApply {
-  CovAcrossView view;
   int num_cols = 0;
   double *X = nullptr;
   double ms_products = 0.0, flops = 0.0;  // the apply's own products, for the caller's DPGO_TIMING line
-  std::string argerr, memerr;
-  const char *name = nullptr;
-  int op = 0, agree_int = 0;
-  double agree_num = 0.0, agree_hash = 0.0;
   virtual int rhs(const double *Td, int N, double *V, hipStream_t stream) = 0;
-  virtual int taken(int /*N*/, hipStream_t /*stream*/) { return DPGO_OK; }
-  virtual int resolve(Across & /*x*/, std::string & /*msg*/) { return DPGO_OK; }
-  virtual int exchange(Across & /*x*/, hipStream_t /*stream*/) { return DPGO_OK; }
   virtual ~CovApply() = default;
 };
 
@@ -252,37 +218,98 @@ int launch_cov_logdet(hipStream_t s, const double *A, int n, double *out);
 // fail[1] the team pose of the pivot, fail[2] its row in that factor
 int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, const int *pairs, double *cov_diag, double *cov_pairs,
                             dpgo_covariance_t *res, int *fail, CovEpilogue *epi = nullptr);
-// What the path across teams has on the device of EVERY participant once allgather D has run ("across teams"):
-// compact tables over the E sorted distinct endpoint poses of the records and the P listed pairs -- T (12 per endpoint, the
-// iterate layout), the E diagonal blocks and the P pair blocks (36 doubles each, row-major), all ordered on `stream`.  An index
-// into them takes the place of the team pose of CovStage: the kernels behind a single team's blocks run on them unchanged.
+// ---- the path over a split team (covariance_schur.hip, SchurAcross; DESIGN.md 5e, "across teams")
+//
+// What the path has on the device of EVERY participant once allgather D has run ("across teams"): compact tables
+// over the E sorted distinct endpoint poses of the records and the P listed pairs -- T (12 per endpoint, the iterate layout),
+// the E diagonal blocks and the P pair blocks (36 doubles each, row-major), all ordered on `stream`.  An index into them takes
+// the place of the team pose of CovStage: the kernels behind a single team's blocks run on them unchanged.
 struct AcrossStage {
   const double *Td, *diag, *pairs;
   int E, P;
   hipStream_t stream;
 };
-// The step behind the blocks of covariance_schur_across (gate.hip, audit.hip), in the spirit of CovEpilogue.  The call fills
-// name, op, num, hash and argerr before the path starts: the path hands them to Across::begin (op 4, 5; the two real fields
-// carry num and hash), so that a record list that differs on one participant is refused everywhere.  resolve() runs behind
-// begin, when the global numbering is known: it fills `pairs` (global pose ids, two per pair) and `endpoints` (sorted,
-// distinct), or refuses in words that are the same on every participant.  run() queues its uploads, its kernel and the copies
-// of its per-record outputs on stage.stream and does not synchronise; the path drains the stream and closes the protocol.
-struct AcrossEpilogue {
-  const char *name = "";
-  int op = 0;
-  double num = 0.0, hash = 0.0;
-  std::string argerr;  // this participant's own refusal (the others learn of it from the agreement record)
-  std::vector<int> pairs, endpoints;
-  virtual int resolve(const Across &x, std::string &msg) = 0;
-  virtual int run(const AcrossStage &stage) = 0;
-  virtual ~AcrossEpilogue() = default;
+// What the path holds when it calls AcrossStep::taken(): T with its halo on the device (N poses of this participant in team
+// order, then halo_slots poses, slot hoffs[k] + s the pose np[s] of local robot k; the slots of remote neighbours are filled,
+// the others are not read by anyone), x_S = Sigma_SS r_S of the WHOLE problem (6 |S| x num_cols, leading dimension nS: after
+// allgather B every participant knows every robot's public frames, so x_S is whole everywhere), and for every halo slot the
+// separator pose whose rows 6 q .. 6 q + 5 of x_S are the slot's rows of X (-1: the problem's fixed pose, whose rows are zero,
+// or a slot of a neighbour that lives here).  With pairs beside the columns (the first-order update, DESIGN.md 5j "across
+// teams") the view also hands the blocks back: diag, the N diagonal blocks of this participant's poses on the device, and
+// blocks_h, the host image of those N blocks and behind them the num_pairs pair blocks, complete after allgather C.  All of
+// it is ordered on the path's stream and lives until the path has drained it behind taken(); filling it costs no launch and
+// no transport call.
+struct CovAcrossView {
+  const double *Td = nullptr, *xS = nullptr, *diag = nullptr, *blocks_h = nullptr;
+  int N = 0, halo_slots = 0, nS = 0, num_pairs = 0;
+  std::vector<int> halo_sep;
+};
+// The ONE hook of the path: what a public call adds to the marginal covariances across teams.  The call fills the agreement
+// record before the path starts -- name, op, the two real fields (agree_num, agree_hash) and the integer one (agree_int) of
+// Across::begin, so that a record list that differs on one participant is refused everywhere -- with argerr, this participant's
+// own refusal, which the others learn from the record, and memerr: its V and X alone exceed the device (V was then not read),
+// told as the path's memory refusal.  The step as it stands here is the plain call (op 3; the path fills the number and the
+// hash of the caller's pairs).  Every virtual does nothing unless overridden, and then queues no launch and sends no byte:
+//   resolve()    behind begin, when the global numbering is known: DPGO_OK, 2: the transport is dead, anything else: a refusal
+//                in msg, the same words on every participant.  A step with records fills `pairs` (global pose ids, two per
+//                pair), which then take the place of the caller's, and its endpoints;
+//   num_cols(), rhs()   Sigma applied to vectors beside the blocks (DESIGN.md 5m "across teams"; 0: none).  The path allocates V
+//                and X (6 N x num_cols, N this participant's poses, pose 0 the problem's) and calls rhs() once T is on the
+//                device, as CovApply::rhs above;
+//   taken()      once X and `view` are set: queues on `stream` whatever reads X; the path drains the stream;
+//   exchange()   behind taken(), whether or not this participant still works (x.bad): the step's own allgathers, the same
+//                number on every participant, and behind them its device work;
+//   endpoints(), run()   a step behind compact tables (the gate, the audit): the records' endpoints, sorted
+//                and distinct, make allgather D run; run() queues its uploads, its kernel and the copies of its per-record
+//                outputs on stage.stream and does not synchronise; the path drains the stream and closes the protocol.
+struct AcrossStep {
+  const char *name = "marginal_covariances_across";
+  int op = 3, agree_int = 0;
+  double agree_num = 0.0, agree_hash = 0.0;
+  std::string argerr, memerr;
+  std::vector<int> pairs;
+  CovAcrossView view;
+  double *X = nullptr;
+  double ms_products = 0.0, flops = 0.0;  // the apply's own products, for the caller's DPGO_TIMING line
+  virtual int resolve(Across & /*x*/, std::string & /*msg*/) { return DPGO_OK; }
+  virtual int num_cols() const { return 0; }
+  virtual int rhs(const double * /*Td*/, int /*N*/, double * /*V*/, hipStream_t /*stream*/) { return DPGO_OK; }
+  virtual int taken(int /*N*/, hipStream_t /*stream*/) { return DPGO_OK; }
+  virtual int exchange(Across & /*x*/, hipStream_t /*stream*/) { return DPGO_OK; }
+  virtual const std::vector<int> *endpoints() const { return nullptr; }
+  virtual int run(const AcrossStage & /*stage*/) { return DPGO_OK; }
+  virtual ~AcrossStep() = default;
+};
+// Sigma applied to vectors with nothing else (op 6: the first real field carries num_cols, the hash is that of no pairs)
+struct ApplyStep : AcrossStep {
+  int cols;
+  explicit ApplyStep(int num_cols_) : cols(num_cols_) {
+    name = "covariance_apply_across";
+    op = 6;
+    agree_num = num_cols_;
+    agree_hash = RecordHash().value();
+  }
+  int num_cols() const override { return cols; }
 };
 
-// the same over a split team (dpgo_team_marginal_covariances_across; covariance_schur.hip).  epi: the step behind the blocks
-// (num_pairs and pairs are then epi's; cov_diag and cov_pairs are not touched and may be null, only res is filled).  app: Sigma
-// applied to vectors beside the blocks (dpgo_team_covariance_apply_across; no epi, no pairs, cov_diag may be null)
-int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
-                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res,
-                            AcrossEpilogue *epi = nullptr, CovApply *app = nullptr);
+// The call over a split team (dpgo_team_marginal_covariances_across and the five calls that ride on it).  step null: the plain
+// call, which writes the N diagonal blocks of this participant's poses to cov_diag and the listed pairs to cov_pairs.  With a
+// step the blocks stay with the path (cov_diag and cov_pairs are not touched and may be null) and only res is filled.  res is
+// all zero unless the call returns DPGO_OK.
+struct SchurAcrossArgs {
+  dpgo_team_t *t;
+  const dpgo_transport_t *tr;
+  const int *owner;  // the owner table: the rank that holds each robot
+  const double *T;
+  SchurAcrossArgs(dpgo_team_t *team, const dpgo_transport_t *transport, const int *owner_rank_of_robot, const double *T_)
+      : t(team), tr(transport), owner(owner_rank_of_robot), T(T_) {}
+  int flags = DPGO_COV_SCHUR;
+  int num_pairs = 0;
+  const int *pairs = nullptr;
+  double *cov_diag = nullptr, *cov_pairs = nullptr;
+  dpgo_covariance_t *res = nullptr;
+  AcrossStep *step = nullptr;
+};
+int covariance_schur_across(const SchurAcrossArgs &a);
 
 }  // namespace dpgo_cert

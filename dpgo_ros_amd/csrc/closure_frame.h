@@ -196,34 +196,26 @@ inline std::vector<int> rank_endpoints(std::vector<GateRec> &recs) {
   return poses;
 }
 
-// ---- across teams (the gate and the audit)
+// ---- across teams (the gate and the audit): the AcrossStep of a call with records
 
-// FNV-1a over the bytes of what every participant must pass alike, as a double that an allgather carries exactly
-struct RecordHash {
-  unsigned long long h = 1469598103934665603ull;
-  void add(const void *p, size_t bytes) {
-    const unsigned char *b = (const unsigned char *)p;
-    for (size_t k = 0; k < bytes; ++k) { h ^= b[k]; h *= 1099511628211ull; }
-  }
-  void add(int v) { add(&v, sizeof v); }
-  void add(double v) { add(&v, sizeof v); }
-  double value() const { return (double)(h & ((1ull << 52) - 1)); }
-};
+// (RecordHash, the hash of what every participant must pass alike: schur_across_plan.h)
 
 // The frame of a per-record call over a split team: the records as the caller passed them, their device form (Rec: GateRec
 // or AuditRec, whose words i, j and *blk the kernel reads as indices into the staged tables), and the hook's resolve().  The
 // records' endpoints become global poses, the pair list is FirstUsePairs over them (the single team's rule), and i, j are
 // rewritten to the ranks of the two poses among the sorted distinct endpoints: the compact tables of AcrossStage.
 template <class Rec>
-struct RecordsAcross : AcrossEpilogue {
+struct RecordsAcross : AcrossStep {
   const ClosureCall *call;
   int Rec::*blk;
   const dpgo_measurement_t *meas = nullptr;
   std::vector<Rec> rec;
+  std::vector<int> ends;  // the records' endpoints: global poses, sorted, distinct
   Events ev;
-  RecordsAcross(const ClosureCall *c, int Rec::*b) : call(c), blk(b), ev(2) { name = c->name; }
+  RecordsAcross(const ClosureCall *c, int Rec::*b, int op_) : call(c), blk(b), ev(2) { name = c->name; op = op_; }
+  const std::vector<int> *endpoints() const override { return &ends; }
 
-  int resolve(const Across &x, std::string &msg) override {
+  int resolve(Across &x, std::string &msg) override {
     FirstUsePairs fp;
     for (size_t k = 0; k < rec.size(); ++k) {
       const dpgo_measurement_t &m = meas[k];
@@ -231,14 +223,14 @@ struct RecordsAcross : AcrossEpilogue {
       if (call->global_endpoint(x, (int)k, m.r1, m.p1, &g[0], msg) || call->global_endpoint(x, (int)k, m.r2, m.p2, &g[1], msg)) return DPGO_ERR;
       rec[k].i = g[0]; rec[k].j = g[1];
       rec[k].*blk = fp.block(g[0], g[1]);
-      endpoints.push_back(g[0]); endpoints.push_back(g[1]);
+      ends.push_back(g[0]); ends.push_back(g[1]);
     }
     pairs = fp.pairs;
-    std::sort(endpoints.begin(), endpoints.end());
-    endpoints.erase(std::unique(endpoints.begin(), endpoints.end()), endpoints.end());
+    std::sort(ends.begin(), ends.end());
+    ends.erase(std::unique(ends.begin(), ends.end()), ends.end());
     for (Rec &c : rec) {
-      c.i = (int)(std::lower_bound(endpoints.begin(), endpoints.end(), c.i) - endpoints.begin());
-      c.j = (int)(std::lower_bound(endpoints.begin(), endpoints.end(), c.j) - endpoints.begin());
+      c.i = (int)(std::lower_bound(ends.begin(), ends.end(), c.i) - ends.begin());
+      c.j = (int)(std::lower_bound(ends.begin(), ends.end(), c.j) - ends.begin());
     }
     return DPGO_OK;
   }

@@ -400,5 +400,8 @@ extern "C" int dpgo_team_marginal_covariances(dpgo_team_t *t, const double *T, i
 extern "C" int dpgo_team_marginal_covariances_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner_rank_of_robot,
                                                      const double *T, int flags, int num_pairs, const int *pairs, double *cov_diag,
                                                      double *cov_pairs, dpgo_covariance_t *res) {
-  return covariance_schur_across(t, tr, owner_rank_of_robot, T, flags, num_pairs, pairs, cov_diag, cov_pairs, res);
+  SchurAcrossArgs a(t, tr, owner_rank_of_robot, T);
+  a.flags = flags;
+  a.num_pairs = num_pairs; a.pairs = pairs; a.cov_diag = cov_diag; a.cov_pairs = cov_pairs; a.res = res;
+  return covariance_schur_across(a);
 }

@@ -4,8 +4,8 @@
 // The path (covariance_nested.hip, covariance.hip) is handed a CovApply (certify_internal.h): it allocates V and X, has the
 // hook write V once T is on the device, queues the products below between its own launches, and sets X before its epilogue
 // runs.  Here the hook copies the caller's V to the device and the epilogue copies X back.
-// Across teams (dpgo_team_covariance_apply_across; DESIGN.md 5m, "across teams") the path is covariance_schur_across with the
-// same hook: its robots' steps queue u_a, W_a^T v_a and r_a, the r_a of every robot travel in its allgather C, and every
+// Across teams (dpgo_team_covariance_apply_across; DESIGN.md 5m, "across teams") the path is covariance_schur_across with an
+// ApplyStep, the path's AcrossStep with columns, that writes V the same way: its robots' steps queue u_a, W_a^T v_a and r_a, the r_a of every robot travel in its allgather C, and every
 // participant forms x_S = Sigma_SS r_S itself.
 // No floating-point atomics; every element's sum runs over k in index order: two calls give the same bytes.
 #include <chrono>
@@ -125,11 +125,17 @@ const ClosureCall APPLY_ACROSS = {"covariance_apply_across", "column"};
 
 // the hook across teams: V is the caller's, X comes back into a host image that reaches the caller only when every
 // participant has closed the call
-struct ApplyAcross : ApplyHost {
+struct ApplyAcross : ApplyStep {
+  const double *V_host = nullptr;
   std::vector<double> X_image;
   bool ran = false;
+  explicit ApplyAcross(int num_cols_) : ApplyStep(num_cols_) {}
+  int rhs(const double *, int N, double *V, hipStream_t stream) override {
+    HIPC(hipMemcpyAsync(V, V_host, sizeof(double) * 6 * (size_t)N * cols, hipMemcpyHostToDevice, stream));
+    return DPGO_OK;
+  }
   int taken(int N, hipStream_t stream) override {
-    X_image.resize((size_t)6 * N * num_cols);
+    X_image.resize((size_t)6 * N * cols);
     HIPC(hipMemcpyAsync(X_image.data(), X, sizeof(double) * X_image.size(), hipMemcpyDeviceToHost, stream));
     ran = true;
     return DPGO_OK;
@@ -167,8 +173,7 @@ extern "C" int dpgo_team_covariance_apply_across(dpgo_team_t *t, const dpgo_tran
   const auto t_begin = std::chrono::steady_clock::now();
   if (res) std::memset(res, 0, sizeof *res);
   if (!t || !tr) return A.refuse("null argument");  // (nobody to tell)
-  ApplyAcross app;
-  app.num_cols = num_cols;
+  ApplyAcross app(num_cols);
   app.V_host = V;
   int N = 0;
   long long zero = -1;  // the team pose of the problem's pose 0, robot 0's first, when robot 0 lives here
@@ -201,10 +206,10 @@ extern "C" int dpgo_team_covariance_apply_across(dpgo_team_t *t, const dpgo_tran
     return DPGO_OK;
   };
   if (refusal()) app.argerr = A.refused();
-  if (const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, T, DPGO_COV_SCHUR, 0, nullptr, nullptr, nullptr, res, nullptr, &app)) {
-    if (res) std::memset(res, 0, sizeof *res);
-    return rc;
-  }
+  SchurAcrossArgs a(t, tr, owner_rank_of_robot, T);
+  a.res = res;
+  a.step = &app;
+  if (const int rc = covariance_schur_across(a)) return rc;  // (res is then all zero)
   // (a problem of the anchor alone: nothing is free, the path staged nothing)
   if (app.ran) std::memcpy(X, app.X_image.data(), sizeof(double) * app.X_image.size());
   else std::memset(X, 0, sizeof(double) * ld * (size_t)num_cols);
@@ -245,20 +250,10 @@ extern "C" int dpgo_team_covariance_apply(dpgo_team_t *t, const double *T, int m
       return APPLY.refuse(buf);
     }
   }
-  for (int c = 0; c < num_cols; ++c) {
-    // (a column at a time by the exponent bits, which the compiler vectorises; the search for the entry only when there is one)
-    const double *col = V + (size_t)c * ld;
-    unsigned long long any = 0;
-    for (size_t r = 6; r < ld; ++r) {
-      unsigned long long b;
-      std::memcpy(&b, col + r, sizeof b);
-      any |= (unsigned long long)((b & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
-    }
-    if (!any) continue;
-    for (size_t r = 6; r < ld; ++r)
-      if (!std::isfinite(col[r]))
-        return APPLY.refuse("V is not finite at row " + std::to_string(r) + " (pose " + std::to_string(r / 6) + ") of column " + std::to_string(c));
-  }
+  size_t row = 0;
+  int column = 0;
+  if (first_not_finite(V, ld, num_cols, 0, &row, &column))
+    return APPLY.refuse("V is not finite at row " + std::to_string(row) + " (pose " + std::to_string(row / 6) + ") of column " + std::to_string(column));
   ApplyHost app;
   app.num_cols = num_cols;
   app.V_host = V;

@@ -26,14 +26,7 @@ struct CovBlock {
 };
 static_assert(sizeof(CovBlock) == 56, "the byte formulas of include/dpgo_hip.h count 56 bytes");
 
-// a list entry of the extraction: output block blk, set b (or -1), two indices, one flag
-struct CovBlk {
-  int blk, b, i, j, f, pad_;
-};
-// a pair of interior poses of two sets: output block, set and interior index of the left pose, then of the right one
-struct CovCross {
-  int blk, ba, li, bb, lj, pad_;
-};
+// (the list entries of the extraction, CovBlk and CovCross, are plain host structs: schur_across_plan.h)
 
 // row r of the separator's matrices for column k of a set's W: pose nb[k / 6], component k mod 6
 __device__ __forceinline__ size_t cov_row(const int *__restrict__ nb, int k) { return (size_t)6 * gp(nb)[k / 6] + (size_t)(k % 6); }

@@ -120,14 +120,7 @@ void launch_cov_assemble_map(hipStream_t s, const AgentDev *agents, const CovIte
 // the upper triangle of the n x n column-major A from its lower one (k_schur_mirror)
 void launch_schur_mirror(hipStream_t s, double *A, int n);
 
-// who is public, who is interior among a team's poses; the fixed pose (team index `zero`, -1: not in this
-// team) belongs to neither set
-struct SchurPartition {
-  int na = 0, N = 0, nS = 0, max_int = 0;
-  std::vector<int> offs, robot_of, pos, sep, sep_off;  // pos: index inside the pose's own set; sep: team pose of separator index
-  std::vector<char> pub;
-  std::vector<std::vector<int>> interior;              // team poses of robot a's interior, in order
-};
+// who is public, who is interior among a team's poses (SchurPartition, schur_across_plan.h)
 void schur_partition(dpgo_team_t *t, int zero, SchurPartition &P);
 
 // the work lists of the assembly: raw stored blocks, sorted by (list, block column, block row) and merged where they name

@@ -221,7 +221,7 @@ struct SchurApply {
   const int *pub;
   double *tmp, *r;
   int cols;
-  CovApply *app;
+  double *flops;              // the step's count of the apply's own products
   std::vector<size_t> *ends;  // the marks that END an interval of the apply's own launches
 };
 
@@ -261,7 +261,7 @@ static int schur_robot_step(SchurDev &D, SchurMarks &marks, int robot_id, int li
     HIPC(hipGetLastError());
     MARK(-1);
     ap->ends->push_back(marks.ev.size() - 1);
-    ap->app->flops += apply_flops(ap->u_h, 1) + apply_flops(ap->t_h, 1);
+    *ap->flops += apply_flops(ap->u_h, 1) + apply_flops(ap->t_h, 1);
   }
   // (keep is never empty: the diagonal blocks)
   HIPC(hipMemcpyAsync(D.blk.p, keep.data(), sizeof(CovBlk) * keep.size(), hipMemcpyHostToDevice, s));
@@ -472,148 +472,204 @@ int covariance_schur_device(dpgo_team_t *t, const double *T, int num_pairs, cons
 //   C  the pair blocks a participant owns (two interior poses of one of its robots; an interior pose of one of its robots
 //      with a public pose) and, for every pair of interior poses of two robots, the two rows W_a[i,:], W_b[j,:] from their
 //      holders;
-// with an AcrossEpilogue (the gate and the audit across teams) also
-//   D  per endpoint of the epilogue's records, sorted by global pose: T and the diagonal block from the pose's holder, zeros
-//      from everyone else -- every participant then runs the epilogue's kernel on compact tables of endpoints and pairs;
+// with an AcrossStep that has endpoints (the gate and the audit across teams) also
+//   D  per endpoint of the step's records, sorted by global pose: T and the diagonal block from the pose's holder, zeros
+//      from everyone else -- every participant then runs the step's kernel on compact tables of endpoints and pairs;
 // and the closing status word.  Every participant builds the same S_c from B, inverts it itself (deterministic: no
 // broadcast) and forms the pairs of two robots itself from the rows of C.  No sum crosses a robot boundary except the
 // host's log det in robot order, so every block, log det and pivot is bitwise the single team's.
+// The layout of every record is SchurAcrossPlan's (schur_across_plan.h, host only); what a public call adds is its AcrossStep
+// (certify_internal.h).  SchurAcross below is one call: run() is the list above.
 namespace {
-
-double pair_hash(const int *pairs, int num_pairs) {
-  unsigned long long h = 1469598103934665603ull;
-  for (int k = 0; k < 2 * num_pairs; ++k)
-    for (int i = 0; i < 4; ++i) {
-      h ^= (unsigned long long)((unsigned)pairs[k] >> (8 * i)) & 0xffull;
-      h *= 1099511628211ull;
-    }
-  return (double)(h & ((1ull << 52) - 1));
-}
 
 enum { XF_OK = 0, XF_PIVOT = 1, XF_MEMORY = 2, XF_LOCAL = 3 };
 
-}  // namespace
-
-int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const int *owner, const double *T, int flags, int num_pairs,
-                            const int *pairs, double *cov_diag, double *cov_pairs, dpgo_covariance_t *res, AcrossEpilogue *epi,
-                            CovApply *app) {
-  const char *what = epi ? epi->name : app ? (app->name ? app->name : "covariance_apply_across") : "marginal_covariances_across";
-  if (res) std::memset(res, 0, sizeof *res);
-  const int cols = app ? app->num_cols : 0;
-  std::string argerr;
-  if (epi && !epi->argerr.empty()) argerr = epi->argerr;
-  else if (app && !app->argerr.empty()) argerr = app->argerr;
-  else if (!T || !res || (!epi && ((!cov_diag && !app) || num_pairs < 0 || (num_pairs > 0 && (!pairs || !cov_pairs))))) argerr = "null argument";
-  else if (flags != DPGO_COV_SCHUR) argerr = "flags must be DPGO_COV_SCHUR";
-  else if (t) {
-    int n = 0;
-    for (auto &a : t->ag) n += a->n;
-    double orth = 0.0, det = 0.0;
-    const int g = se3_defect(T, n, &orth, &det);
-    if (g >= 0) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "pose %d of T (team order) is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", g, orth, det);
-      argerr = buf;
-    }
-  }
+struct SchurAcross {
+  const SchurAcrossArgs &a;
+  AcrossStep &st;
+  const bool plain;  // no step of the caller's: the blocks go to cov_diag and cov_pairs
+  dpgo_team_t *const t;
+  const char *const what;
+  const int *pairs;
+  int num_pairs;
+  const int cols;    // the columns Sigma is applied to (0: none)
+  int rc = DPGO_ERR;  // what the call returns when a step ends it
   Across x;
-  // (op 6, Sigma applied to vectors: the first real field carries num_cols)
-  // (op 8, the update across teams: the app's own record -- the number of records, the hash of records and pairs, num_pairs)
-  const bool own = app && app->op;
-  const double agree_num = epi ? epi->num : own ? app->agree_num : app ? (double)cols : (double)num_pairs;
-  const double agree_hash = !argerr.empty() ? 0.0 : epi ? epi->hash : own ? app->agree_hash : pair_hash(pairs, num_pairs);
-  if (x.begin(t, tr, owner, what, epi ? epi->op : own ? app->op : app ? 6 : 3, 3, flags, agree_num, agree_hash, own ? app->agree_int : 0,
-              argerr.empty() ? nullptr : argerr.c_str())) {
-    // (a participant whose own records were refused says why in the words of the single team's call)
-    if (epi && !epi->argerr.empty()) set_err(std::string(what) + ": " + epi->argerr);
-    else if (app && !app->argerr.empty()) set_err(std::string(what) + ": " + app->argerr);
-    return DPGO_ERR;
-  }
-  // (from here on the participants agree on the owner table, the robots' sizes and the pair list)
-  const int nr = x.num_robots, na = (int)t->ag.size(), world = x.world;
-  const long long NG = x.nglob;
-  if (epi) {  // the records' endpoints in the global numbering: a refusal is the same on every participant
-    std::string msg;
-    if (epi->resolve(x, msg)) { set_err(std::string(what) + ": " + msg); return DPGO_ERR; }
-    pairs = epi->pairs.data();
-    num_pairs = (int)(epi->pairs.size() / 2);
-  }
-  if (app) {  // (an app with records of its own: its endpoints, and what it gathers before the path starts)
-    std::string msg;
-    const int rc = app->resolve(x, msg);
-    if (rc == 2) return x.fail();
-    if (rc) { set_err(std::string(what) + ": " + msg); return DPGO_ERR; }
-  }
-  for (int k = 0; k < 2 * num_pairs; ++k)
-    if (pairs[k] < 0 || pairs[k] >= NG) {  // (the same on every participant: nobody goes on)
-      set_err(std::string(what) + ": pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " +
-              std::to_string(NG) + ")");
-      return DPGO_ERR;
-    }
+  Cert c;
+  hipStream_t s = nullptr;
   SchurPartition P;
-  {
+  SchurAcrossPlan pl;
+  SchurItems L;
+  SchurMarks marks;
+  int nr = 0, na = 0, N = 0, nS = 0;
+  size_t nout = 0;  // the doubles of the N diagonal and the num_pairs pair blocks
+  std::vector<double> gall;
+  // a block of H_SS between two robots in a row this participant holds.  row: local robot and index among its public poses;
+  // column: robot id, frame
+  struct CrossBlk { int lrobot, lrow, crobot, cframe; };
+  std::vector<CrossBlk> xb;
+  std::vector<int> ncross, byid;  // cross blocks per local robot; the local robots in id order
+  // this participant's failure, told in allgather B
+  int fcode = XF_OK, frobot = 0, fpose = 0, frow = 0, sfail = 0;
+  std::string fmsg;
+  // device storage (as the single team's, the separator that of the whole problem)
+  SchurDev D;
+  DevBuf<double> d_S, d_small, d_t, d_T, d_D, d_X, d_rows, d_tab;
+  std::vector<DevBuf<double>> d_W;
+  DevBuf<int> d_int;
+  DevBuf<CovBlk> d_is;
+  DevBuf<CovCross> d_cross;
+  size_t cross_chunk = 0;
+  std::vector<size_t> doff;          // a robot's diagonal block of the separator in d_D
+  std::vector<int> ipose_off, soff;  // a robot's interior poses in d_int; its first row of the global separator
+  const int *iota_d = nullptr;
+  double *stat = nullptr, *keepd = nullptr, *outd = nullptr;
+  std::vector<CovBlock> rob;
+  std::vector<double> hD, hX, hstat, hS, hout, hrows, sstat = std::vector<double>(4, 0.0);
+  // Sigma applied to vectors (DESIGN.md 5m, "across teams").  d_aV, d_aX: 6 N x cols; d_rS, d_xS: r_S and x_S of the whole
+  // problem, 6 |S| x cols; d_tmp: W_a^T v_a of the robot at hand; d_pub: the team poses of this participant's public poses
+  // (P.sep), a robot's row map a window of it.  Records: [0, na) u_a = C_a v_a, [na, 2 na) t_a = W_a^T v_a, [2 na, 3 na)
+  // x_a -= W_a x_S[S_a], 3 na: x_S = Sigma_SS r_S
+  DevBuf<double> d_aV, d_aX, d_rS, d_xS, d_tmp;
+  DevBuf<int> d_pub;
+  DevBuf<ApplyItem> d_app;
+  std::vector<ApplyItem> aitem;
+  std::vector<size_t> app_marks, roff;  // roff: a robot's r_a (K_a x cols) in h_ra, id order
+  std::vector<double> h_ra;             // the r_a of the robots here, back from the device
+
+  SchurAcross(const SchurAcrossArgs &args, AcrossStep &step, bool plain_)
+      : a(args), st(step), plain(plain_), t(args.t), what(step.name), pairs(args.pairs), num_pairs(args.num_pairs), cols(step.num_cols()) {}
+
+  // a step that returns true has ended the call with rc; a participant that failed locally (x.bad) launches nothing more but
+  // makes every transport call of the sequence
+  int run() {
+    if (agree()) return rc;
+    if (lambda_of_T()) return rc;
+    work_lists();
+    if (gather_sizes()) return rc;
+    if (!x.bad && fcode == XF_OK && (storage() || phase1())) { fcode = XF_LOCAL; fmsg = g_err; }
+    if (gather_b()) return rc;
+    pl.classify(P, pairs, num_pairs, cols);
+    if (!x.bad && phase2()) x.fail_local(g_err);
+    if (gather_c()) return rc;
+    if (!x.bad && phase3()) x.fail_local(g_err);
+    if (cols > 0 && !x.bad && apply()) x.fail_local(g_err);
+    if (st.exchange(x, s)) return x.fail();
+    if (st.endpoints() && gather_d()) return rc;
+    return close();
+  }
+
+  // ---- the agreement record, the step's resolve(), the partition; a problem of the fixed pose alone ends here
+  bool agree() {
+    std::string argerr = st.argerr;
+    if (!argerr.empty()) {}
+    else if (!a.T || !a.res || (plain && !a.cov_diag) || num_pairs < 0 || (num_pairs > 0 && (!pairs || !a.cov_pairs))) argerr = "null argument";
+    else if (a.flags != DPGO_COV_SCHUR) argerr = "flags must be DPGO_COV_SCHUR";
+    else if (t) {
+      int n = 0;
+      for (auto &ag : t->ag) n += ag->n;
+      double orth = 0.0, det = 0.0;
+      const int g = se3_defect(a.T, n, &orth, &det);
+      if (g >= 0) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "pose %d of T (team order) is not in SE(3) (|R^T R - I| = %.3g, det R = %.12g)", g, orth, det);
+        argerr = buf;
+      }
+    }
+    if (plain) {  // (op 3: the number of pairs and their hash)
+      st.agree_num = num_pairs;
+      RecordHash h;
+      for (int k = 0; argerr.empty() && k < 2 * num_pairs; ++k) h.add(pairs[k]);
+      st.agree_hash = h.value();
+    }
+    if (x.begin(t, a.tr, a.owner, what, st.op, 3, a.flags, st.agree_num, argerr.empty() ? st.agree_hash : 0.0, st.agree_int,
+                argerr.empty() ? nullptr : argerr.c_str())) {
+      // (a participant whose own records were refused says why in the words of the single team's call)
+      if (!st.argerr.empty()) set_err(std::string(what) + ": " + st.argerr);
+      return true;
+    }
+    // (from here on the participants agree on the owner table, the robots' sizes and the pair list)
+    nr = x.num_robots; na = (int)t->ag.size();
+    {  // the step's records in the global numbering: a refusal is the same on every participant
+      std::string msg;
+      const int r = st.resolve(x, msg);
+      if (r == 2) { rc = x.fail(); return true; }
+      if (r) { set_err(std::string(what) + ": " + msg); return true; }
+      if (st.endpoints()) { pairs = st.pairs.data(); num_pairs = (int)(st.pairs.size() / 2); }
+    }
+    for (int k = 0; k < 2 * num_pairs; ++k)
+      if (pairs[k] < 0 || pairs[k] >= x.nglob) {  // (the same on every participant: nobody goes on)
+        set_err(std::string(what) + ": pair " + std::to_string(k / 2) + " names pose " + std::to_string(pairs[k]) + ", outside [0, " +
+                std::to_string(x.nglob) + ")");
+        return true;
+      }
     int z = -1;  // team pose of the fixed pose, robot 0's first, when robot 0 lives here
     if (t->id2local.count(0)) {
       z = 0;
       for (int k = 0; k < t->id2local.at(0); ++k) z += t->ag[k]->n;
     }
     schur_partition(t, z, P);
+    N = P.N;
+    nout = (size_t)36 * (N + num_pairs);
+    if (x.nglob < 2 && !st.endpoints()) {  // (with records never: a record joins two different poses of the problem)
+      if (plain) {  // (nothing is free; with a step the caller's own outputs are zero)
+        std::memset(a.cov_diag, 0, sizeof(double) * 36 * (size_t)N);
+        if (num_pairs > 0) std::memset(a.cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
+      }
+      rc = x.finish() ? DPGO_ERR : DPGO_OK;
+      return true;
+    }
+    std::vector<int> local_of(nr, -1);
+    for (int i = 0; i < nr; ++i)
+      if (x.robot_holder[i] == x.rank) { local_of[i] = t->id2local.at(i); byid.push_back(local_of[i]); }
+    pl.init(x.rank, x.world, x.robot_holder, x.robot_n, local_of);
+    return false;
   }
-  const int N = P.N;
-  if (NG < 2 && !epi) {  // (with an epilogue never: a record joins two different poses of the problem)
-    if (app) return x.finish() ? DPGO_ERR : DPGO_OK;  // (nothing is free: the caller's X is zero)
-    std::memset(cov_diag, 0, sizeof(double) * 36 * (size_t)N);
-    if (num_pairs > 0) std::memset(cov_pairs, 0, sizeof(double) * 36 * (size_t)num_pairs);
-    return x.finish() ? DPGO_ERR : DPGO_OK;
-  }
-  x.note(hipSetDevice(t->device), __LINE__);
-  hipStream_t s = t->stream;
+
   // ---- Lambda of T from the across operator at K = 3; the T halo stays on the device
-  Cert c;
-  c.t = t;
-  c.x = &x;
-  c.setup(3);
-  CERT_CK(c, hipMemcpyAsync(c.T, T, sizeof(double) * 12 * (size_t)N, hipMemcpyHostToDevice, s));
-  c.apply(3, c.T, 3, c.T2, 3, false);
-  if (!c.halted()) launch_cert_lambda3(s, t->d_agents.p, c.off, na, c.max_n, c.T, c.T2, c.lam, c.gmax);
-  CERT_CK(c, hipGetLastError());
-  if (x.dead) return x.fail();
+  bool lambda_of_T() {
+    x.note(hipSetDevice(t->device), __LINE__);
+    s = t->stream;
+    c.t = t;
+    c.x = &x;
+    c.setup(3);
+    if (!c.halted()) x.note(hipMemcpyAsync(c.T, a.T, sizeof(double) * 12 * (size_t)N, hipMemcpyHostToDevice, s), __LINE__);
+    c.apply(3, c.T, 3, c.T2, 3, false);
+    if (!c.halted()) launch_cert_lambda3(s, t->d_agents.p, c.off, na, c.max_n, c.T, c.T2, c.lam, c.gmax);
+    if (!c.halted()) x.note(hipGetLastError(), __LINE__);
+    if (x.dead) { rc = x.fail(); return true; }
+    return false;
+  }
 
   // ---- the work lists of this participant.  Lists: [0, na) H_II,a, [na, 2 na) B_a, [2 na, 3 na) the diagonal block of H_SS of
   // robot a, 3 na: the blocks of H_SS between two robots in the rows this participant holds, one 6 x 6 slot each
-  std::vector<int> hoffs(na, 0);
-  int halo_slots = 0;
-  for (int k = 0; k < na; ++k) { hoffs[k] = halo_slots; halo_slots += (int)t->ag[k]->np.size(); }
-  struct CrossBlk { int lrobot, lrow, crobot, cframe; };  // row: local robot and index among its public poses; column: robot id, frame
-  std::vector<CrossBlk> xb;
-  std::vector<int> ncross(na, 0);
-  SchurItems L;
-  bool outside = false;
-  {
+  void work_lists() {
+    bool outside = false;
+    ncross.assign(na, 0);
     std::map<std::tuple<int, int, int>, int> slot_of;  // (team pose of the row, column robot, column frame) -> slot
     for (int k = 0; k < na; ++k) {
-      const Agent &a = *t->ag[k];
+      const Agent &ag = *t->ag[k];
       const int so = P.sep_off[k];
-      for (int j = 0; j < a.n; ++j)
-        for (int p = a.rowptr[j]; p < a.rowptr[j + 1]; ++p) {
-          const int bi = P.offs[k] + a.col[p], bj = P.offs[k] + j;
-          if (a.col[p] < 0 || a.col[p] >= a.n) { outside = true; continue; }
-          if (a.id == 0 && (a.col[p] == 0 || j == 0)) continue;  // the fixed pose
+      for (int j = 0; j < ag.n; ++j)
+        for (int p = ag.rowptr[j]; p < ag.rowptr[j + 1]; ++p) {
+          const int bi = P.offs[k] + ag.col[p], bj = P.offs[k] + j;
+          if (ag.col[p] < 0 || ag.col[p] >= ag.n) { outside = true; continue; }
+          if (ag.id == 0 && (ag.col[p] == 0 || j == 0)) continue;  // the fixed pose
           const bool pi = P.pub[bi], pj = P.pub[bj];
           if (pi && pj) { if (bi <= bj) L.add(2 * na + k, bi, bj, k, p, P.pos[bi] - so, P.pos[bj] - so, CD_MIRROR); }
           else if (!pi && !pj) { if (bi <= bj) L.add(k, bi, bj, k, p, P.pos[bi], P.pos[bj], CD_MIRROR); }
           else if (!pi && pj) L.add(na + k, bi, bj, k, p, P.pos[bi], P.pos[bj] - so, bi > bj ? (CD_FLIP | CD_TRANS) : 0);
         }
-      for (size_t e = 0; e < a.se_host.size(); ++e) {
-        const SharedEdgeDev &se = a.se_host[e];
+      for (size_t e = 0; e < ag.se_host.size(); ++e) {
+        const SharedEdgeDev &se = ag.se_host[e];
         const int cr = se.src_robot, cf = se.src_frame;
-        if (cr < 0 || cr >= nr || cf < 0 || cf >= x.robot_n[cr] || se.lpose < 0 || se.lpose >= a.n) { outside = true; continue; }
-        if (cr >= a.id) continue;             // the row-owner rule: the block (row own pose, column the LOWER robot's pose)
+        if (cr < 0 || cr >= nr || cf < 0 || cf >= x.robot_n[cr] || se.lpose < 0 || se.lpose >= ag.n) { outside = true; continue; }
+        if (cr >= ag.id) continue;            // the row-owner rule: the block (row own pose, column the LOWER robot's pose)
         if (cr == 0 && cf == 0) continue;     // the fixed pose
-        if (a.id == 0 && se.lpose == 0) continue;
+        if (ag.id == 0 && se.lpose == 0) continue;
         const int bj = P.offs[k] + se.lpose;
         // the column pose's row of T: its own when the neighbour lives here, else its halo slot behind this team's poses
-        const int bi = se.src_agent_local >= 0 ? P.offs[se.src_agent_local] + cf : N + hoffs[k] + se.slot;
+        const int bi = se.src_agent_local >= 0 ? P.offs[se.src_agent_local] + cf : N + x.hoffs[k] + se.slot;
         const auto key = std::make_tuple(bj, cr, cf);
         auto it = slot_of.find(key);
         if (it == slot_of.end()) {
@@ -624,118 +680,58 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
         L.add(3 * na, bi, bj, k, ~(int)e, 0, it->second, CD_TRANS);
       }
     }
-  }
-  L.finish(3 * na + 1);
-  if (outside) x.fail_local("a stored block lies outside the problem");
-
-  // ---- allgather A: the sizes
-  std::vector<double> ga(1 + 3 * (size_t)nr, 0.0), gall;
-  for (int k = 0; k < na; ++k) {
-    const int id = t->ag[k]->id;
-    ga[1 + 3 * id] = P.sep_off[k + 1] - P.sep_off[k];
-    ga[2 + 3 * id] = (double)P.interior[k].size();
-    ga[3 + 3 * id] = ncross[k];
-  }
-  if (x.gather(ga, gall)) return x.fail();
-  std::vector<int> gs(nr), gi(nr), gc(nr), gsoff(nr + 1, 0);
-  for (int i = 0; i < nr; ++i) {
-    const double *q = gall.data() + (size_t)x.robot_holder[i] * ga.size();
-    gs[i] = (int)q[1 + 3 * i]; gi[i] = (int)q[2 + 3 * i]; gc[i] = (int)q[3 + 3 * i];
-    gsoff[i + 1] = gsoff[i] + gs[i];
-  }
-  const int nSp = gsoff[nr], nS = 6 * nSp;
-  int kmax = 0;
-  for (int i = 0; i < nr; ++i) kmax = std::max(kmax, 6 * gs[i]);
-  auto robot_len = [&](int i) { return (size_t)gs[i] + 36 * (size_t)gs[i] * gs[i] + 4 + (size_t)gc[i] * 39; };
-  constexpr size_t HDR = 6;  // status, failure code, robot, pose, row, spare
-  std::vector<size_t> plen(world, HDR);
-  for (int i = 0; i < nr; ++i) plen[x.robot_holder[i]] += robot_len(i);
-  const size_t pmax = *std::max_element(plen.begin(), plen.end());
-  // the local robots in id order
-  std::vector<int> byid;
-  for (int i = 0; i < nr; ++i)
-    if (x.robot_holder[i] == x.rank) byid.push_back(t->id2local.at(i));
-
-  // ---- the pairs, by case, from what every participant knows so far; the remote poses' sets come with allgather B
-  std::vector<int> grobot((size_t)NG), gframe((size_t)NG);
-  for (int i = 0; i < nr; ++i)
-    for (int f = 0; f < x.robot_n[i]; ++f) { grobot[x.robot_goff[i] + f] = i; gframe[x.robot_goff[i] + f] = f; }
-  auto local_pose = [&](int g) { return P.offs[t->id2local.at(grobot[g])] + gframe[g]; };
-  auto here = [&](int g) { return x.robot_holder[grobot[g]] == x.rank; };
-  // pairs of two interior poses of one local robot must be known before the robot's step (its blocks of C_a are kept)
-  std::vector<std::vector<CovBlk>> keep_list(na), same_list(na);
-  for (int k = 0; k < na; ++k)
-    for (int g : P.interior[k]) keep_list[k].push_back({g, k, P.pos[g], P.pos[g], 0, 0});
-  for (int k = 0; k < num_pairs; ++k) {
-    const int a = pairs[2 * k], b = pairs[2 * k + 1];
-    if (a == 0 || b == 0 || grobot[a] != grobot[b] || !here(a)) continue;
-    const int la = local_pose(a), lb = local_pose(b);
-    if (P.pub[la] || P.pub[lb]) continue;
-    const int lk = t->id2local.at(grobot[a]);
-    keep_list[lk].push_back({N + k, lk, P.pos[la], P.pos[lb], 0, 0});
-    same_list[lk].push_back({N + k, lk, P.pos[la], P.pos[lb], 0, 0});
+    L.finish(3 * na + 1);
+    if (outside) x.fail_local("a stored block lies outside the problem");
   }
 
-  // ---- device storage (as the single team's, the separator that of the whole problem)
-  const int M = std::max(6 * P.max_int, nS);
-  const size_t MM = (size_t)M * M, nout = (size_t)36 * (N + num_pairs);
-  size_t w_max = 0, d_all = 0;
-  std::vector<size_t> doff(na + 1, 0);
-  for (int k = 0; k < na; ++k) {
-    const size_t sk = (size_t)(P.sep_off[k + 1] - P.sep_off[k]);
-    w_max = std::max(w_max, (size_t)36 * P.interior[k].size() * sk);
-    doff[k + 1] = doff[k] + 36 * sk * sk;
+  // ---- allgather A: the sizes.  Behind it every participant knows the separator of the whole problem, and this one its
+  // pairs of two interior poses of one robot (their blocks of C_a are kept in the robot's step) and whether it fits its device
+  bool gather_sizes() {
+    std::vector<double> ga(pl.a_len(), 0.0);
+    for (int k = 0; k < na; ++k) pl.a_put(ga, t->ag[k]->id, P.sep_off[k + 1] - P.sep_off[k], (int)P.interior[k].size(), ncross[k]);
+    if (x.gather(ga, gall)) { rc = x.fail(); return true; }
+    pl.a_take(gall);
+    nS = pl.nS;
+    pl.same_robot_pairs(P, pairs, num_pairs);
+    // (V and X alone beyond the device: the caller has decided it without reading V, and says so in its own words)
+    if (!x.bad && !st.memerr.empty()) { fcode = XF_MEMORY; fmsg = std::string(what) + ": " + st.memerr; }
+    else if (!x.bad && schur_fits(t, P, pl.nSp, pl.kmax, num_pairs, what, fmsg, cols)) { fcode = XF_MEMORY; }
+    return false;
   }
-  d_all = doff[na];
-  int fcode = XF_OK, frobot = 0, fpose = 0, frow = 0;
-  std::string fmsg;
-  // (V and X alone beyond the device: the caller has decided it without reading V, and says so in its own words)
-  if (!x.bad && app && !app->memerr.empty()) { fcode = XF_MEMORY; fmsg = std::string(what) + ": " + app->memerr; }
-  else if (!x.bad && schur_fits(t, P, nSp, kmax, num_pairs, what, fmsg, cols)) { fcode = XF_MEMORY; }
-  SchurDev D;
-  DevBuf<double> d_S, d_small, d_t, d_T, d_D, d_X, d_rows;
-  // Sigma applied to vectors (DESIGN.md 5m, "across teams").  d_aV, d_aX: 6 N x cols; d_rS, d_xS: r_S and x_S of the whole
-  // problem, 6 |S| x cols; d_tmp: W_a^T v_a of the robot at hand; d_pub: the team poses of this participant's public poses
-  // (P.sep), a robot's row map a window of it.  Records: [0, na) u_a = C_a v_a, [na, 2 na) t_a = W_a^T v_a, [2 na, 3 na)
-  // x_a -= W_a x_S[S_a], 3 na: x_S = Sigma_SS r_S
-  DevBuf<double> d_aV, d_aX, d_rS, d_xS, d_tmp;
-  DevBuf<int> d_pub;
-  DevBuf<ApplyItem> d_app;
-  std::vector<ApplyItem> aitem(app ? 3 * (size_t)na + 1 : 0);
-  std::vector<size_t> app_marks, roff(na, 0);  // roff: a robot's r_a (K_a x cols) in this participant's part of allgather C, id order
-  size_t rlen = 0;
-  for (int k : byid) { roff[k] = rlen; rlen += (size_t)6 * gs[t->ag[k]->id] * cols; }
-  std::vector<double> h_ra;  // the r_a of the robots here, back from the device
-  std::vector<DevBuf<double>> d_W(na);
-  DevBuf<int> d_int;
-  DevBuf<CovBlk> d_is;
-  DevBuf<CovCross> d_cross;
-  size_t ncrosspairs = 0;
-  for (int k = 0; k < num_pairs; ++k) ncrosspairs += (pairs[2 * k] && pairs[2 * k + 1] && grobot[pairs[2 * k]] != grobot[pairs[2 * k + 1]]);
-  const size_t cross_chunk = cov_cross_chunk(ncrosspairs, kmax);
-  const size_t small = 4 * (size_t)(na + 1) + 2 * nout;
-  size_t nblk = (size_t)N + num_pairs;
-  SchurMarks marks;
-  // d_int: the team pose of every interior index (robot after robot), then iota = 0, 1, ..., |S| - 1 over the GLOBAL separator
-  std::vector<int> ints, ipose_off(na + 1, 0), soff(na, 0);
-  for (int k = 0; k < na; ++k) {
-    ints.insert(ints.end(), P.interior[k].begin(), P.interior[k].end());
-    ipose_off[k + 1] = (int)ints.size();
-    soff[k] = 6 * gsoff[t->ag[k]->id];
-  }
-  for (int q = 0; q < nSp; ++q) ints.push_back(q);
-  const int *iota_d = nullptr;
-  double *stat = nullptr, *keepd = nullptr, *outd = nullptr;
-  std::vector<CovBlock> rob(na);
-  std::vector<double> hD, hX, hstat;
-  // phase 1 on the device: this participant's robots.  DPGO_ERR: a local failure (message set)
-  auto phase1 = [&]() -> int {
+
+  // ---- device storage, the robots as sets, the records of the apply.  DPGO_ERR: a local failure (message set)
+  int storage() {
+    const int M = std::max(6 * P.max_int, nS);
+    const size_t MM = (size_t)M * M, ncrosspairs = pl.two_robot_pairs(pairs, num_pairs);
+    size_t w_max = 0, rlen = 0;
+    doff.assign(na + 1, 0);
+    for (int k = 0; k < na; ++k) {
+      const size_t sk = (size_t)(P.sep_off[k + 1] - P.sep_off[k]);
+      w_max = std::max(w_max, (size_t)36 * P.interior[k].size() * sk);
+      doff[k + 1] = doff[k] + 36 * sk * sk;
+    }
+    const size_t d_all = doff[na], small = 4 * (size_t)(na + 1) + 2 * nout;
+    cross_chunk = cov_cross_chunk(ncrosspairs, pl.kmax);
+    roff.assign(na, 0);
+    for (int k : byid) { roff[k] = rlen; rlen += (size_t)6 * pl.gs[t->ag[k]->id] * cols; }
+    h_ra.resize(rlen);
+    // d_int: the team pose of every interior index (robot after robot), then iota = 0, 1, ..., |S| - 1 over the GLOBAL separator
+    std::vector<int> ints;
+    ipose_off.assign(na + 1, 0); soff.assign(na, 0);
+    for (int k = 0; k < na; ++k) {
+      ints.insert(ints.end(), P.interior[k].begin(), P.interior[k].end());
+      ipose_off[k + 1] = (int)ints.size();
+      soff[k] = 6 * pl.gsoff[t->ag[k]->id];
+    }
+    for (int q = 0; q < pl.nSp; ++q) ints.push_back(q);
+    d_W.resize(na);
+    aitem.resize(cols > 0 ? 3 * (size_t)na + 1 : 0);
     bool bad = D.A.alloc(MM) || D.Wk.alloc(MM) || D.M.alloc(MM) || d_S.alloc((size_t)nS * nS) || D.B.alloc(w_max) || d_small.alloc(small) ||
                d_int.upload(ints, s) || D.items.upload(L.items, s) || D.src.upload(L.srcs, s) || D.dst.upload(L.dsts, s) ||
-               D.blk.alloc(nblk) || d_is.alloc((size_t)num_pairs) || d_cross.alloc(ncrosspairs) || D.tab.alloc((size_t)na + 2 * ncrosspairs) ||
-               d_t.alloc(cross_chunk * 6 * std::max(kmax, 1)) || d_T.alloc((size_t)12 * (N + halo_slots)) || d_D.alloc(d_all) ||
-               d_X.alloc(36 * xb.size());
-    if (app && !bad) {
+               D.blk.alloc((size_t)N + num_pairs) || d_is.alloc((size_t)num_pairs) || d_cross.alloc(ncrosspairs) ||
+               D.tab.alloc((size_t)na + 2 * ncrosspairs) || d_t.alloc(cross_chunk * 6 * std::max(pl.kmax, 1)) ||
+               d_T.alloc((size_t)12 * (N + x.halo_slots)) || d_D.alloc(d_all) || d_X.alloc(36 * xb.size());
+    if (cols > 0 && !bad) {
       int kloc = 0;
       for (int k = 0; k < na; ++k) kloc = std::max(kloc, 6 * (P.sep_off[k + 1] - P.sep_off[k]));
       const size_t vx = (size_t)6 * N * cols, sx = (size_t)nS * cols;
@@ -746,18 +742,20 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     if (bad) { set_err("device allocation failed"); return DPGO_ERR; }
     stat = d_small.p; keepd = stat + 4 * (size_t)(na + 1); outd = keepd + nout;
     HIPC(hipMemcpyAsync(d_T.p, c.T, sizeof(double) * 12 * (size_t)N, hipMemcpyDeviceToDevice, s));
-    if (halo_slots > 0) HIPC(hipMemcpyAsync(d_T.p + (size_t)12 * N, x.d_halo, sizeof(double) * 12 * (size_t)halo_slots, hipMemcpyDeviceToDevice, s));
+    if (x.halo_slots > 0)
+      HIPC(hipMemcpyAsync(d_T.p + (size_t)12 * N, x.d_halo, sizeof(double) * 12 * (size_t)x.halo_slots, hipMemcpyDeviceToDevice, s));
     D.s = s; D.agents = t->d_agents.p; D.Td = d_T.p; D.lam = c.lam; D.L = &L;
     // the robots as sets (the table is on the device before the first keep launch): nb a window of iota at the robot's place
     // in the global separator
     iota_d = d_int.p + ipose_off[na];
+    rob.resize(na);
     for (int k = 0; k < na; ++k)
-      rob[k] = {d_W[k].p, iota_d + gsoff[t->ag[k]->id], d_int.p + ipose_off[k], D.M.p, nullptr, D.B.p, 6 * (int)P.interior[k].size(),
+      rob[k] = {d_W[k].p, iota_d + pl.gsoff[t->ag[k]->id], d_int.p + ipose_off[k], D.M.p, nullptr, D.B.p, 6 * (int)P.interior[k].size(),
                 6 * (P.sep_off[k + 1] - P.sep_off[k])};
     HIPC(hipMemcpyAsync(D.tab.p, rob.data(), sizeof(CovBlock) * na, hipMemcpyHostToDevice, s));
     HIPC(hipMemsetAsync(stat, 0, sizeof(double) * small, s));
     if (d_all) HIPC(hipMemsetAsync(d_D.p, 0, sizeof(double) * d_all, s));
-    if (app) {
+    if (cols > 0) {
       for (int k = 0; k < na; ++k) {
         const int *poses = d_int.p + ipose_off[k];
         const int ni = rob[k].ld, K = rob[k].K;
@@ -768,24 +766,30 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
       aitem[3 * na] = {D.M.p, d_rS.p, d_xS.p, nullptr, nullptr, nS, nS, nS, nS, cols, nS};
       HIPC(hipMemcpyAsync(d_app.p, aitem.data(), sizeof(ApplyItem) * aitem.size(), hipMemcpyHostToDevice, s));
       HIPC(hipMemsetAsync(d_aX.p, 0, sizeof(double) * 6 * (size_t)N * cols, s));
-      if (app->rhs(d_T.p, N, d_aV.p, s)) return DPGO_ERR;
+      if (st.rhs(d_T.p, N, d_aV.p, s)) return DPGO_ERR;
     }
     MARK(-1);
+    return DPGO_OK;
+  }
+
+  // ---- phase 1 on the device: this participant's robots, one after another.  A pivot that is not positive is this
+  // participant's failure record (fcode), not an error of the phase
+  int phase1() {
     for (int k = 0; k < na; ++k) D.assemble(2 * na + k, d_D.p + doff[k], rob[k].K);
     D.assemble(3 * na, d_X.p, 6);
     HIPC(hipGetLastError());
     MARK(0);
     for (int k : byid) {
       const int ni = rob[k].ld;
-      const int *pub = app ? d_pub.p + P.sep_off[k] : nullptr;
+      const int *pub = cols > 0 ? d_pub.p + P.sep_off[k] : nullptr;
       if (ni == 0) {  // (a robot with no interior pose: r_a = v_{S_a})
-        if (app) launch_apply_rows_sub(s, d_aV.p, (size_t)6 * N, pub, nullptr, d_rS.p + soff[k], (size_t)nS, nullptr, rob[k].K, cols);
+        if (cols > 0) launch_apply_rows_sub(s, d_aV.p, (size_t)6 * N, pub, nullptr, d_rS.p + soff[k], (size_t)nS, nullptr, rob[k].K, cols);
         continue;
       }
       const SchurApply ap{d_app.p + k, d_app.p + na + k, aitem.data() + k, aitem.data() + na + k, d_aV.p, (size_t)6 * N, (size_t)nS, pub,
-                          d_tmp.p, d_rS.p + soff[k], cols, app, &app_marks};
-      const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_D.p + doff[k], rob[k].K, keep_list[k], keepd,
-                                     stat + 4 * k, app ? &ap : nullptr);
+                          d_tmp.p, d_rS.p + soff[k], cols, &st.flops, &app_marks};
+      const int f = schur_robot_step(D, marks, t->ag[k]->id, k, na + k, ni, rob[k].K, d_W[k].p, d_D.p + doff[k], rob[k].K, pl.keep_list[k], keepd,
+                                     stat + 4 * k, cols > 0 ? &ap : nullptr);
       if (f < 0) return DPGO_ERR;
       if (f > 0) {
         fcode = XF_PIVOT; frobot = t->ag[k]->id; frow = f - 1;
@@ -794,13 +798,12 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
         return DPGO_OK;
       }
     }
-    hD.resize(d_all); hX.resize(36 * xb.size()); hstat.resize(4 * (size_t)(na + 1));
-    if (d_all) HIPC(hipMemcpyAsync(hD.data(), d_D.p, sizeof(double) * d_all, hipMemcpyDeviceToHost, s));
+    hD.resize(doff[na]); hX.resize(36 * xb.size()); hstat.resize(4 * (size_t)(na + 1));
+    if (!hD.empty()) HIPC(hipMemcpyAsync(hD.data(), d_D.p, sizeof(double) * hD.size(), hipMemcpyDeviceToHost, s));
     if (!xb.empty()) HIPC(hipMemcpyAsync(hX.data(), d_X.p, sizeof(double) * hX.size(), hipMemcpyDeviceToHost, s));
     HIPC(hipMemcpyAsync(hstat.data(), stat, sizeof(double) * hstat.size(), hipMemcpyDeviceToHost, s));
-    if (app) {  // the r_a of the robots here, K_a x cols each, in id order: this participant's part of allgather C
+    if (cols > 0) {  // the r_a of the robots here, K_a x cols each, in id order: this participant's part of allgather C
       HIPC(hipGetLastError());
-      h_ra.resize(rlen);
       for (int k : byid)
         if (rob[k].K > 0)
           HIPC(hipMemcpy2DAsync(h_ra.data() + roff[k], sizeof(double) * rob[k].K, d_rS.p + soff[k], sizeof(double) * nS, sizeof(double) * rob[k].K,
@@ -808,146 +811,46 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
     }
     HIPC(hipStreamSynchronize(s));
     return DPGO_OK;
-  };
-  if (!x.bad && fcode == XF_OK && phase1()) { fcode = XF_LOCAL; fmsg = g_err; }
+  }
 
-  // ---- allgather B
-  std::vector<double> gb(pmax, 0.0);
-  gb[1] = fcode; gb[2] = frobot; gb[3] = fpose; gb[4] = frow;
-  if (fcode == XF_OK && !x.bad) {
-    size_t o = HDR;
+  // ---- allgather B, the failure of any participant told by all in the same words, and S_c of the whole problem
+  bool gather_b() {
+    std::vector<double> gb(pl.pmax, 0.0);
+    gb[pl.B_CODE] = fcode; gb[pl.B_ROBOT] = frobot; gb[pl.B_POSE] = fpose; gb[pl.B_ROW] = frow;
     for (int k : byid) {
-      const int id = t->ag[k]->id, sk = gs[id];
-      for (int q = 0; q < sk; ++q) gb[o++] = P.sep[P.sep_off[k] + q] - P.offs[k];
-      std::memcpy(gb.data() + o, hD.data() + doff[k], sizeof(double) * 36 * (size_t)sk * sk);
-      o += 36 * (size_t)sk * sk;
-      gb[o] = hstat[4 * k]; gb[o + 1] = hstat[4 * k + 1]; gb[o + 2] = hstat[4 * k + 2]; gb[o + 3] = rob[k].ld > 0 ? 1.0 : 0.0;
-      o += 4;
-      for (size_t b = 0; b < xb.size(); ++b) {
-        if (xb[b].lrobot != k) continue;
-        gb[o] = xb[b].lrow; gb[o + 1] = xb[b].crobot; gb[o + 2] = xb[b].cframe;
-        std::memcpy(gb.data() + o + 3, hX.data() + 36 * b, sizeof(double) * 36);
-        o += 39;
-      }
+      if (fcode != XF_OK || x.bad) break;
+      const double rstat[4] = {hstat[4 * k], hstat[4 * k + 1], hstat[4 * k + 2], rob[k].ld > 0 ? 1.0 : 0.0};
+      std::vector<int> frames;
+      for (int q = P.sep_off[k]; q < P.sep_off[k + 1]; ++q) frames.push_back(P.sep[q] - P.offs[k]);
+      std::vector<SchurAcrossPlan::BCross> cross;
+      for (size_t b = 0; b < xb.size(); ++b)
+        if (xb[b].lrobot == k) cross.push_back({xb[b].lrow, xb[b].crobot, xb[b].cframe, hX.data() + 36 * b});
+      pl.b_pack(gb, t->ag[k]->id, frames.data(), hD.data() + doff[k], rstat, cross);
     }
-  }
-  if (x.gather(gb, gall)) return x.fail();
-  // a failure of any participant, told by all in the same words
-  for (int q = 0; q < world; ++q) {
-    const double *h = gall.data() + (size_t)q * pmax;
-    if (h[1] == XF_OK) continue;
-    std::string m = std::string(what) + ": rank " + std::to_string(q) + ": ";
-    if (h[1] == XF_PIVOT)
-      m = pivot_message(std::string(what) + ": rank " + std::to_string(q), (long long)h[4],
-                        "the interior Hessian of robot " + std::to_string((long long)h[2]), (long long)h[3]);
-    else if (h[1] == XF_MEMORY) m += "the Schur path does not fit its device (its own error names the bytes)";
-    else m += "local failure (its own error names the cause)";
-    if (q == x.rank && !fmsg.empty() && h[1] != XF_PIVOT) m += " [" + fmsg + "]";
-    set_err(m);
-    return DPGO_ERR;
-  }
-  // ---- S_c of the whole problem, the same on every participant
-  std::vector<std::vector<int>> pubf(nr);
-  std::vector<double> rstat(4 * (size_t)nr, 0.0);
-  std::vector<double> hS((size_t)nS * nS, 0.0);
-  std::vector<size_t> rstart(nr, 0);
-  for (int q = 0; q < world; ++q) {
-    size_t o = (size_t)q * pmax + HDR;
-    for (int i = 0; i < nr; ++i) {
-      if (x.robot_holder[i] != q) continue;
-      rstart[i] = o;
-      pubf[i].resize(gs[i]);
-      for (int k = 0; k < gs[i]; ++k) pubf[i][k] = (int)gall[o + k];
-      o += robot_len(i);
+    if (x.gather(gb, gall)) { rc = x.fail(); return true; }
+    for (int q = 0; q < x.world; ++q) {
+      const double *h = pl.b_header(gall, q);
+      if (h[pl.B_CODE] == XF_OK) continue;
+      std::string m = std::string(what) + ": rank " + std::to_string(q) + ": ";
+      if (h[pl.B_CODE] == XF_PIVOT)
+        m = pivot_message(std::string(what) + ": rank " + std::to_string(q), (long long)h[pl.B_ROW],
+                          "the interior Hessian of robot " + std::to_string((long long)h[pl.B_ROBOT]), (long long)h[pl.B_POSE]);
+      else if (h[pl.B_CODE] == XF_MEMORY) m += "the Schur path does not fit its device (its own error names the bytes)";
+      else m += "local failure (its own error names the cause)";
+      if (q == x.rank && !fmsg.empty() && h[pl.B_CODE] != XF_PIVOT) m += " [" + fmsg + "]";
+      set_err(m);
+      return true;
     }
-  }
-  auto sep_index = [&](int robot, int frame) -> int {
-    const auto &v = pubf[robot];
-    const auto it = std::lower_bound(v.begin(), v.end(), frame);
-    return (it != v.end() && *it == frame) ? gsoff[robot] + (int)(it - v.begin()) : -1;
-  };
-  bool torn = false;
-  for (int i = 0; i < nr; ++i) {
-    size_t o = rstart[i] + gs[i];
-    const size_t w = 6 * (size_t)gs[i], so = 6 * (size_t)gsoff[i];
-    for (size_t cc = 0; cc < w; ++cc) std::memcpy(hS.data() + (so + cc) * nS + so, gall.data() + o + cc * w, sizeof(double) * w);
-    o += w * w;
-    for (int k = 0; k < 4; ++k) rstat[4 * i + k] = gall[o + k];
-    o += 4;
-    for (int b = 0; b < gc[i]; ++b, o += 39) {
-      const int row = gsoff[i] + (int)gall[o], col = sep_index((int)gall[o + 1], (int)gall[o + 2]);
-      if (col < 0) { torn = true; continue; }
-      const double *blk = gall.data() + o + 3;  // 6 x 6 column-major: H[row pose, column pose]
-      for (int bb = 0; bb < 6; ++bb)
-        for (int aa = 0; aa < 6; ++aa) {
-          hS[((size_t)6 * col + bb) * nS + (size_t)6 * row + aa] = blk[6 * bb + aa];
-          hS[((size_t)6 * row + aa) * nS + (size_t)6 * col + bb] = blk[6 * bb + aa];
-        }
+    if (!pl.assemble(gall, hS)) {  // (the same on every participant)
+      set_err(std::string(what) + ": a shared edge names a pose its robot does not list as public (the measurement sets differ)");
+      return true;
     }
+    return false;
   }
-  if (torn) {  // (the same on every participant)
-    set_err(std::string(what) + ": a shared edge names a pose its robot does not list as public (the measurement sets differ)");
-    return DPGO_ERR;
-  }
-  // every pose of the problem: its set and its index there
-  std::vector<char> gpub((size_t)NG, 0);
-  std::vector<int> gpos((size_t)NG, 0);
-  for (int i = 0; i < nr; ++i) {
-    for (int k = 0; k < gs[i]; ++k) { gpub[x.robot_goff[i] + pubf[i][k]] = 1; gpos[x.robot_goff[i] + pubf[i][k]] = gsoff[i] + k; }
-    int cnt = 0;
-    for (int f = (i == 0 ? 1 : 0); f < x.robot_n[i]; ++f)
-      if (!gpub[x.robot_goff[i] + f]) gpos[x.robot_goff[i] + f] = cnt++;
-  }
-  // ---- the pair lists.  Owner of a pair: the holder of the (left) interior pose's robot; pairs of two public poses and
-  // of two robots' interiors are formed by everyone
-  std::vector<CovBlk> pub_list, is_list;
-  std::vector<CovCross> cross_list;
-  std::vector<int> pair_owner(num_pairs, -1);  // -1: everyone (or zeros)
-  struct RowReq { int pair, robot, li; };
-  std::vector<RowReq> rows;  // two per pair of two robots, in pair order
-  for (int k = 0; k < na; ++k)
-    for (int q = P.sep_off[k]; q < P.sep_off[k + 1]; ++q) {
-      const int gsx = gsoff[t->ag[k]->id] + (q - P.sep_off[k]);
-      pub_list.push_back({P.sep[q], -1, gsx, gsx, 1, 0});
-    }
-  for (int k = 0; k < num_pairs; ++k) {
-    const int a = pairs[2 * k], b = pairs[2 * k + 1], blk = N + k;
-    if (a == 0 || b == 0) continue;
-    const int ra = grobot[a], rb = grobot[b];
-    if (gpub[a] && gpub[b]) pub_list.push_back({blk, -1, gpos[a], gpos[b], 0, 0});
-    else if (!gpub[a] && !gpub[b]) {
-      if (ra == rb) pair_owner[k] = x.robot_holder[ra];
-      else { rows.push_back({k, ra, gpos[a]}); rows.push_back({k, rb, gpos[b]}); }
-    } else if (!gpub[a]) {
-      pair_owner[k] = x.robot_holder[ra];
-      if (pair_owner[k] == x.rank) is_list.push_back({blk, t->id2local.at(ra), gpos[a], gpos[b], 0, 0});
-    } else {
-      pair_owner[k] = x.robot_holder[rb];
-      if (pair_owner[k] == x.rank) is_list.push_back({blk, t->id2local.at(rb), gpos[b], gpos[a], 1, 0});
-    }
-  }
-  std::vector<size_t> clen(world, 1), rowoff(rows.size(), 0);
-  for (int k = 0; k < num_pairs; ++k)
-    if (pair_owner[k] >= 0) clen[pair_owner[k]] += 36;
-  for (size_t r = 0; r < rows.size(); ++r) {
-    const int q = x.robot_holder[rows[r].robot];
-    rowoff[r] = clen[q];
-    clen[q] += 36 * (size_t)gs[rows[r].robot];
-  }
-  const size_t rows_max = *std::max_element(clen.begin(), clen.end());  // (the pair blocks and the rows: what hrows stages)
-  // Sigma applied to vectors: behind them every robot's r_a, K_a x cols, from its holder in id order
-  std::vector<size_t> rat(nr, 0);
-  for (int i = 0; app && i < nr; ++i) {
-    const int q = x.robot_holder[i];
-    rat[i] = clen[q];
-    clen[q] += (size_t)6 * gs[i] * cols;
-  }
-  const size_t cmax = *std::max_element(clen.begin(), clen.end());
-  std::vector<double> hout, hrows;
-  std::vector<double> sstat(4, 0.0);
-  int sfail = 0;
-  // phase 2 on the device: the separator's inverse and this participant's blocks
-  auto phase2 = [&]() -> int {
+
+  // ---- phase 2 on the device: the separator's inverse and this participant's blocks.  A pivot of the separator that is not
+  // positive is sfail, the same on every participant
+  int phase2() {
     if (nS > 0) {
       HIPC(hipMemcpyAsync(d_S.p, hS.data(), sizeof(double) * hS.size(), hipMemcpyHostToDevice, s));
       launch_schur_mirror(s, d_S.p, nS);
@@ -958,192 +861,187 @@ int covariance_schur_across(dpgo_team_t *t, const dpgo_transport_t *tr, const in
       if (f > 0) { sfail = f; return DPGO_OK; }
       if (launch_cov_logdet(s, d_S.p, nS, stat + 4 * na)) return DPGO_ERR;
       MARK(3);
-      if (schur_listed(D, nS, pub_list, D.blk.p, true, outd)) return DPGO_ERR;
+      if (schur_listed(D, nS, pl.pub_list, D.blk.p, true, outd)) return DPGO_ERR;
       MARK(4);
     }
     for (int k : byid) {
       if (rob[k].ld == 0) continue;
-      if (schur_robot_blocks(D, marks, t->ag[k]->id, k, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)soff[k] * nS + soff[k], nS, same_list[k],
+      if (schur_robot_blocks(D, marks, t->ag[k]->id, k, rob[k].ld, rob[k].K, d_W[k].p, D.M.p + (size_t)soff[k] * nS + soff[k], nS, pl.same_list[k],
                              keepd, outd))
         return DPGO_ERR;
     }
-    if (schur_listed(D, nS, is_list, d_is.p, false, outd)) return DPGO_ERR;
+    if (schur_listed(D, nS, pl.is_list, d_is.p, false, outd)) return DPGO_ERR;
     hout.resize(nout);
     HIPC(hipMemcpyAsync(hout.data(), outd, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
     if (nS > 0) HIPC(hipMemcpyAsync(sstat.data(), stat + 4 * na, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
-    // the rows W_a[i,:] this participant holds, 6 x 6 s_a column-major each
-    hrows.assign(rows_max, 0.0);
-    for (size_t r = 0; r < rows.size(); ++r) {
-      if (x.robot_holder[rows[r].robot] != x.rank) continue;
-      const int lk = t->id2local.at(rows[r].robot);
+    // the rows W_a[i,:] this participant holds, 6 x 6 s_a column-major each, at their places in the record
+    hrows.assign(pl.rows_max, 0.0);
+    for (size_t r = 0; r < pl.rows.size(); ++r) {
+      if (x.robot_holder[pl.rows[r].robot] != x.rank) continue;
+      const int lk = t->id2local.at(pl.rows[r].robot);
       if (rob[lk].K > 0)
-        HIPC(hipMemcpy2DAsync(hrows.data() + rowoff[r], 48, d_W[lk].p + (size_t)6 * rows[r].li, sizeof(double) * rob[lk].ld, 48, rob[lk].K,
+        HIPC(hipMemcpy2DAsync(hrows.data() + pl.rowoff[r], 48, d_W[lk].p + (size_t)6 * pl.rows[r].li, sizeof(double) * rob[lk].ld, 48, rob[lk].K,
                               hipMemcpyDeviceToHost, s));
     }
     HIPC(hipStreamSynchronize(s));
     return DPGO_OK;
-  };
-  if (!x.bad && phase2()) x.fail_local(g_err);
-  // ---- allgather C: the owned pair blocks and the rows
-  std::vector<double> gcv(cmax, 0.0);
-  if (!x.bad && sfail == 0) {
-    size_t o = 1;
-    for (int k = 0; k < num_pairs; ++k)
-      if (pair_owner[k] == x.rank) { std::memcpy(gcv.data() + o, hout.data() + 36 * (size_t)(N + k), sizeof(double) * 36); o += 36; }
-    for (size_t r = 0; r < rows.size(); ++r)
-      if (x.robot_holder[rows[r].robot] == x.rank)
-        std::memcpy(gcv.data() + rowoff[r], hrows.data() + rowoff[r], sizeof(double) * 36 * (size_t)gs[rows[r].robot]);
-    for (int k : byid) {  // (app: robot a's r_a from its place in h_ra to its place in the record)
-      const int id = t->ag[k]->id;
-      const size_t len = (size_t)6 * gs[id] * cols;
-      if (app && len > 0) std::memcpy(gcv.data() + rat[id], h_ra.data() + roff[k], sizeof(double) * len);
+  }
+
+  // ---- allgather C: the owned pair blocks, the rows and the r_a; behind it the separator's pivot, and everyone's pair blocks
+  bool gather_c() {
+    std::vector<double> gcv(pl.cmax, 0.0);
+    if (!x.bad && sfail == 0) {
+      pl.c_pack(gcv, hout.data() + (size_t)36 * N, hrows);
+      for (int k : byid)
+        if (cols > 0) pl.c_pack_ra(gcv, t->ag[k]->id, h_ra.data() + roff[k], cols);
     }
+    if (x.gather(gcv, gall)) { rc = x.fail(); return true; }
+    if (sfail > 0) {  // (deterministic: the same on every participant, and behind the allgather that would have told of a failure)
+      const int sp = (sfail - 1) / 6;
+      int robot = 0;
+      while (robot + 1 < nr && pl.gsoff[robot + 1] <= sp) ++robot;
+      const long long pose = x.robot_goff[robot] + pl.pubf[robot][sp - pl.gsoff[robot]];
+      set_err(pivot_message(what, sfail - 1, "the Schur complement on the public poses", pose));
+      return true;
+    }
+    pl.c_unpack_pairs(gall, hout.data() + (size_t)36 * N);
+    return false;
   }
-  if (x.gather(gcv, gall)) return x.fail();
-  if (sfail > 0) {  // (deterministic: the same on every participant, and behind the allgather that would have told of a failure)
-    const int sp = (sfail - 1) / 6;
-    int robot = 0;
-    while (robot + 1 < nr && gsoff[robot + 1] <= sp) ++robot;
-    const long long pose = x.robot_goff[robot] + pubf[robot][sp - gsoff[robot]];
-    set_err(pivot_message(what, sfail - 1, "the Schur complement on the public poses", pose));
-    return DPGO_ERR;
-  }
-  {
-    std::vector<size_t> o(world, 1);
-    for (int k = 0; k < num_pairs; ++k)
-      if (pair_owner[k] >= 0) {
-        const int q = pair_owner[k];
-        std::memcpy(hout.data() + 36 * (size_t)(N + k), gall.data() + (size_t)q * cmax + o[q], sizeof(double) * 36);
-        o[q] += 36;
-      }
-  }
-  // the pairs of two robots' interiors, from the gathered rows: each row a robot of its own in the table
-  auto phase3 = [&]() -> int {
-    if (rows.empty()) return DPGO_OK;
+
+  // ---- phase 3: the pairs of two robots' interiors, from the gathered rows: each row a robot of its own in the table
+  int phase3() {
+    const size_t nrows = pl.rows.size();
+    if (nrows == 0) return DPGO_OK;
     size_t total = 0;
-    std::vector<size_t> ro(rows.size());
-    for (size_t r = 0; r < rows.size(); ++r) { ro[r] = total; total += 36 * (size_t)gs[rows[r].robot]; }
+    std::vector<size_t> ro(nrows);
+    for (size_t r = 0; r < nrows; ++r) { ro[r] = total; total += pl.row_len(r); }
     if (d_rows.alloc(total)) { set_err("device allocation failed"); return DPGO_ERR; }
     std::vector<double> hr(total);
-    std::vector<CovBlock> prob(rows.size());  // a row as a robot of one pose
-    for (size_t r = 0; r < rows.size(); ++r) {
-      const int q = x.robot_holder[rows[r].robot];
-      std::memcpy(hr.data() + ro[r], gall.data() + (size_t)q * cmax + rowoff[r], sizeof(double) * 36 * (size_t)gs[rows[r].robot]);
-      prob[r] = {d_rows.p + ro[r], iota_d + gsoff[rows[r].robot], nullptr, nullptr, nullptr, nullptr, 6, 6 * gs[rows[r].robot]};
+    std::vector<CovBlock> prob(nrows);  // a row as a robot of one pose
+    std::vector<CovCross> cross_list;
+    for (size_t r = 0; r < nrows; ++r) {
+      std::memcpy(hr.data() + ro[r], pl.c_row(gall, r), sizeof(double) * pl.row_len(r));
+      prob[r] = {d_rows.p + ro[r], iota_d + pl.gsoff[pl.rows[r].robot], nullptr, nullptr, nullptr, nullptr, 6, 6 * pl.gs[pl.rows[r].robot]};
     }
-    for (size_t r = 0; r + 1 < rows.size(); r += 2) cross_list.push_back({N + rows[r].pair, na + (int)r, 0, na + (int)r + 1, 0, 0});
+    for (size_t r = 0; r + 1 < nrows; r += 2) cross_list.push_back({N + pl.rows[r].pair, na + (int)r, 0, na + (int)r + 1, 0, 0});
     HIPC(hipMemcpyAsync(d_rows.p, hr.data(), sizeof(double) * total, hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(D.tab.p + na, prob.data(), sizeof(CovBlock) * prob.size(), hipMemcpyHostToDevice, s));
-    if (schur_cross_pairs(s, D.tab.p, D.M.p, nS, cross_list, d_cross.p, kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
+    if (schur_cross_pairs(s, D.tab.p, D.M.p, nS, cross_list, d_cross.p, pl.kmax, d_t.p, cross_chunk, outd)) return DPGO_ERR;
     std::vector<double> hc(36 * (size_t)num_pairs);
     HIPC(hipMemcpyAsync(hc.data(), outd + 36 * (size_t)N, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     for (const CovCross &e : cross_list) std::memcpy(hout.data() + 36 * (size_t)e.blk, hc.data() + 36 * (size_t)(e.blk - N), sizeof(double) * 36);
     return DPGO_OK;
-  };
-  if (!x.bad && phase3()) x.fail_local(g_err);
+  }
+
   // ---- Sigma applied to vectors, behind the separator's inverse (D.M = Sigma_SS).  r_S from the gathered r_a, the same bytes
   // on every participant; x_S = Sigma_SS r_S, the whole of it, here; x_a = u_a - W_a x_S[S_a] and X[S_a] = x_S[S_a] for the
-  // robots here
-  auto phase_apply = [&]() -> int {
+  // robots here.  Then the step's view and its taken()
+  int apply() {
     if (nS > 0) {
-      std::vector<double> hrS((size_t)nS * cols);
-      for (int i = 0; i < nr; ++i) {
-        const size_t w = (size_t)6 * gs[i];
-        const double *src = gall.data() + (size_t)x.robot_holder[i] * cmax + rat[i];
-        for (int c = 0; c < cols && w > 0; ++c)
-          std::memcpy(hrS.data() + (size_t)c * nS + (size_t)6 * gsoff[i], src + (size_t)c * w, sizeof(double) * w);
-      }
+      std::vector<double> hrS;
+      pl.c_unpack_rs(gall, cols, hrS);
       HIPC(hipMemcpyAsync(d_rS.p, hrS.data(), sizeof(double) * hrS.size(), hipMemcpyHostToDevice, s));
       MARK(-1);
       launch_apply_gemm(s, false, d_app.p + 3 * na, aitem.data() + 3 * na, 1, false);
       for (int k : byid) {
         launch_apply_gemm(s, false, d_app.p + 2 * na + k, aitem.data() + 2 * na + k, 1, true);
         launch_apply_rows_sub(s, d_xS.p + soff[k], (size_t)nS, nullptr, nullptr, d_aX.p, (size_t)6 * N, d_pub.p + P.sep_off[k], rob[k].K, cols);
-        app->flops += apply_flops(aitem.data() + 2 * na + k, 1);
+        st.flops += apply_flops(aitem.data() + 2 * na + k, 1);
       }
       HIPC(hipGetLastError());
       MARK(-1);
       app_marks.push_back(marks.ev.size() - 1);
-      app->flops += apply_flops(aitem.data() + 3 * na, 1);
+      st.flops += apply_flops(aitem.data() + 3 * na, 1);
       HIPC(hipStreamSynchronize(s));  // (hrS has been read)
     }
-    app->X = d_aX.p;
-    {  // what a step along X needs of the poses behind this participant's own (CovAcrossView): host tables, no launch
-      CovAcrossView &v = app->view;
-      v.Td = d_T.p; v.N = N; v.halo_slots = halo_slots; v.xS = nS > 0 ? d_xS.p : nullptr; v.nS = nS;
-      v.diag = outd; v.blocks_h = hout.data(); v.num_pairs = num_pairs;
-      v.halo_sep.assign(halo_slots, -1);
-      for (int k = 0; k < na; ++k)
-        for (size_t q = 0; q < t->ag[k]->np.size(); ++q) {
-          const int b = t->ag[k]->np[q].first, f = t->ag[k]->np[q].second;
-          if (b >= 0 && b < nr && !t->id2local.count(b)) v.halo_sep[hoffs[k] + q] = sep_index(b, f);
-        }
-    }
-    if (app->taken(N, s)) return DPGO_ERR;
+    st.X = d_aX.p;
+    // what a step along X needs of the poses behind this participant's own (CovAcrossView): host tables, no launch
+    CovAcrossView &v = st.view;
+    v.Td = d_T.p; v.N = N; v.halo_slots = x.halo_slots; v.xS = nS > 0 ? d_xS.p : nullptr; v.nS = nS;
+    v.diag = outd; v.blocks_h = hout.data(); v.num_pairs = num_pairs;
+    v.halo_sep.assign(x.halo_slots, -1);
+    for (int k = 0; k < na; ++k)
+      for (size_t q = 0; q < t->ag[k]->np.size(); ++q) {
+        const int b = t->ag[k]->np[q].first, f = t->ag[k]->np[q].second;
+        if (b >= 0 && b < nr && !t->id2local.count(b)) v.halo_sep[x.hoffs[k] + q] = pl.sep_index(b, f);
+      }
+    if (st.taken(N, s)) return DPGO_ERR;
     HIPC(hipStreamSynchronize(s));
     for (size_t k : app_marks) {
-      float v = 0.f;
-      if (hipEventElapsedTime(&v, marks.ev[k - 1], marks.ev[k]) == hipSuccess) app->ms_products += v;
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, marks.ev[k - 1], marks.ev[k]) == hipSuccess) st.ms_products += ms;
     }
     return DPGO_OK;
-  };
-  if (app && !x.bad && phase_apply()) x.fail_local(g_err);
-  if (app && app->exchange(x, s)) return x.fail();
+  }
+
   // ---- the step behind the blocks (the gate, the audit).  Allgather D: per endpoint of the records, sorted by global pose,
   // 12 doubles of T and the 36 of its diagonal block from the participant that holds it, zeros from everyone else (pose 0's
-  // block is zero with its holder too).  Then every participant holds the compact tables and runs all records itself.
-  DevBuf<double> d_tab;
-  auto phase4 = [&](const std::vector<double> &tab, int E) -> int {
-    if (d_tab.alloc(tab.size())) { set_err("device allocation failed"); return DPGO_ERR; }
-    HIPC(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
-    const AcrossStage st{d_tab.p, d_tab.p + (size_t)12 * E, d_tab.p + (size_t)48 * E, E, num_pairs, s};
-    if (epi->run(st)) return DPGO_ERR;
-    HIPC(hipStreamSynchronize(s));
-    return DPGO_OK;
-  };
-  if (epi) {
-    const int E = (int)epi->endpoints.size();
-    std::vector<double> gd(1 + 48 * (size_t)E, 0.0);
-    if (!x.bad)
-      for (int e = 0; e < E; ++e) {
-        const int g = epi->endpoints[e];
-        if (!here(g)) continue;
-        const int lp = local_pose(g);
-        std::memcpy(gd.data() + 1 + 48 * (size_t)e, T + (size_t)12 * lp, sizeof(double) * 12);
-        std::memcpy(gd.data() + 1 + 48 * (size_t)e + 12, hout.data() + (size_t)36 * lp, sizeof(double) * 36);
-      }
-    if (x.gather(gd, gall)) return x.fail();
+  // block is zero with its holder too).  Then every participant holds the compact tables and runs all records itself
+  bool gather_d() {
+    const std::vector<int> &ends = *st.endpoints();
+    const int E = (int)ends.size();
+    HeldRecord rec{48, std::vector<int>(E)};
+    for (int e = 0; e < E; ++e) rec.holder[e] = x.robot_holder[pl.grobot[ends[e]]];
+    std::vector<double> gd(rec.len(), 0.0);
+    for (int e = 0; e < E && !x.bad; ++e) {
+      if (rec.holder[e] != x.rank) continue;
+      const int lp = P.offs[t->id2local.at(pl.grobot[ends[e]])] + pl.gframe[ends[e]];
+      std::memcpy(rec.mine(gd, e), a.T + (size_t)12 * lp, sizeof(double) * 12);
+      std::memcpy(rec.mine(gd, e) + 12, hout.data() + (size_t)36 * lp, sizeof(double) * 36);
+    }
+    if (x.gather(gd, gall)) { rc = x.fail(); return true; }
     // T of the E endpoints, their diagonal blocks, the pair blocks
     std::vector<double> tab((size_t)48 * E + (size_t)36 * num_pairs);
     for (int e = 0; e < E; ++e) {
-      const double *q = gall.data() + (size_t)x.robot_holder[grobot[epi->endpoints[e]]] * gd.size() + 1 + 48 * (size_t)e;
-      std::memcpy(tab.data() + (size_t)12 * e, q, sizeof(double) * 12);
-      std::memcpy(tab.data() + (size_t)12 * E + (size_t)36 * e, q + 12, sizeof(double) * 36);
+      std::memcpy(tab.data() + (size_t)12 * e, rec.from(gall, e), sizeof(double) * 12);
+      std::memcpy(tab.data() + (size_t)12 * E + (size_t)36 * e, rec.from(gall, e) + 12, sizeof(double) * 36);
     }
     std::memcpy(tab.data() + (size_t)48 * E, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
-    if (phase4(tab, E)) x.fail_local(g_err);
+    if (run_records(tab, E)) x.fail_local(g_err);
+    return false;
   }
-  if (x.finish()) return DPGO_ERR;
-  // ---- the results: log det and pivots in robot order, the separator last
-  std::vector<char> counted(nr + 1, 0);
-  for (int i = 0; i < nr; ++i) counted[i] = rstat[4 * i + 3] != 0.0;
-  counted[nr] = nS > 0;
-  rstat.insert(rstat.end(), sstat.begin(), sstat.end());
-  double ms[5];
-  marks.sum(ms);
-  cov_fill_result(res, 6 * (NG - 1), rstat.data(), counted, ms);
-  schur_report(marks);
-  static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
-  if (timing)
-    std::fprintf(stderr,
-                 "%s: rank %d of %d, n %lld, separator %d, largest interior here %d, assemble %.3f ms, factorisations "
-                 "%.3f ms, products %.3f ms, separator inverse %.3f ms, extract %.3f ms, %lld allgathers, %lld exchanges\n",
-                 what, x.rank, world, 6 * (NG - 1), nS, 6 * P.max_int, ms[0], ms[1], ms[2], ms[3], ms[4], x.n_allgather, x.n_exchange);
-  if (epi || app) return DPGO_OK;  // (the blocks stay here: the epilogue's outputs, or X, are the call's)
-  std::memcpy(cov_diag, hout.data(), sizeof(double) * 36 * (size_t)N);
-  if (num_pairs > 0) std::memcpy(cov_pairs, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
-  return DPGO_OK;
+  int run_records(const std::vector<double> &tab, int E) {
+    if (d_tab.alloc(tab.size())) { set_err("device allocation failed"); return DPGO_ERR; }
+    HIPC(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
+    const AcrossStage stage{d_tab.p, d_tab.p + (size_t)12 * E, d_tab.p + (size_t)48 * E, E, num_pairs, s};
+    if (st.run(stage)) return DPGO_ERR;
+    HIPC(hipStreamSynchronize(s));
+    return DPGO_OK;
+  }
+
+  // ---- the closing status word and the results: log det and pivots in robot order, the separator last
+  int close() {
+    if (x.finish()) return DPGO_ERR;
+    std::vector<char> counted(nr + 1, 0);
+    for (int i = 0; i < nr; ++i) counted[i] = pl.rstat[4 * i + 3] != 0.0;
+    counted[nr] = nS > 0;
+    std::vector<double> rstat = pl.rstat;
+    rstat.insert(rstat.end(), sstat.begin(), sstat.end());
+    double ms[5];
+    marks.sum(ms);
+    cov_fill_result(a.res, 6 * (x.nglob - 1), rstat.data(), counted, ms);
+    schur_report(marks);
+    static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
+    if (timing)
+      std::fprintf(stderr,
+                   "%s: rank %d of %d, n %lld, separator %d, largest interior here %d, assemble %.3f ms, factorisations "
+                   "%.3f ms, products %.3f ms, separator inverse %.3f ms, extract %.3f ms, %lld allgathers, %lld exchanges\n",
+                   what, x.rank, x.world, 6 * (x.nglob - 1), nS, 6 * P.max_int, ms[0], ms[1], ms[2], ms[3], ms[4], x.n_allgather, x.n_exchange);
+    if (!plain) return DPGO_OK;  // (the blocks stay here: the step's outputs are the call's)
+    std::memcpy(a.cov_diag, hout.data(), sizeof(double) * 36 * (size_t)N);
+    if (num_pairs > 0) std::memcpy(a.cov_pairs, hout.data() + (size_t)36 * N, sizeof(double) * 36 * (size_t)num_pairs);
+    return DPGO_OK;
+  }
+};
+
+}  // namespace
+
+int covariance_schur_across(const SchurAcrossArgs &a) {
+  if (a.res) std::memset(a.res, 0, sizeof *a.res);
+  AcrossStep plain_step;
+  SchurAcross call(a, a.step ? *a.step : plain_step, !a.step);
+  return call.run();
 }
 #undef MARK
 

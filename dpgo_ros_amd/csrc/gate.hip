@@ -124,7 +124,7 @@ const ClosureCall GATE_ACROSS = {"gate_candidates_across", "candidate"};
 
 // the same step behind the compact tables of the path across teams: every participant runs all K records
 struct GateAcross : RecordsAcross<GateRec>, GateWork {
-  GateAcross() : RecordsAcross<GateRec>(&GATE_ACROSS, &GateRec::w0) {}
+  GateAcross() : RecordsAcross<GateRec>(&GATE_ACROSS, &GateRec::w0, 4) {}
   int run(const AcrossStage &st) override {
     if (!inside(st)) { set_err("a candidate lies outside the staged blocks"); return DPGO_ERR; }
     if (GateWork::alloc(rec.size(), "gate_candidates_across") || ev.create()) return DPGO_ERR;
@@ -184,7 +184,6 @@ extern "C" int dpgo_team_gate_candidates_across(dpgo_team_t *t, const dpgo_trans
   const ClosureCall &G = GATE_ACROSS;
   if (res) std::memset(res, 0, sizeof *res);
   GateAcross epi;
-  epi.op = 4;
   epi.innov = xi != nullptr;
   epi.want_sigma = sigma_rel != nullptr;
   // ---- the refusals of the gate itself, in the single team's order and words: decided here, told to everyone by the
@@ -217,17 +216,17 @@ extern "C" int dpgo_team_gate_candidates_across(dpgo_team_t *t, const dpgo_trans
       pack_measurement(m, c.m);
       h.add(c.m, sizeof c.m);
     }
-    epi.num = num;
-    epi.hash = h.value();
+    epi.agree_num = num;
+    epi.agree_hash = h.value();
   }
-  if (const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, T, DPGO_COV_SCHUR, 0, nullptr, nullptr, nullptr, res, &epi)) {
-    if (res) std::memset(res, 0, sizeof *res);
-    return rc;
-  }
+  SchurAcrossArgs a(t, tr, owner_rank_of_robot, T);
+  a.res = res;
+  a.step = &epi;
+  if (const int rc = covariance_schur_across(a)) return rc;  // (res is then all zero)
   static const bool timing = std::getenv("DPGO_TIMING") != nullptr;
   if (timing)
     std::fprintf(stderr, "gate_candidates_across: %d candidates on %zu pair blocks and %zu endpoints, gate kernel %.3f ms\n", num,
-                 epi.pairs.size() / 2, epi.endpoints.size(), epi.ev.ms());
+                 epi.pairs.size() / 2, epi.ends.size(), epi.ev.ms());
   epi.copy_out((size_t)num, xi, d2, sigma_rel);
   return DPGO_OK;
 }

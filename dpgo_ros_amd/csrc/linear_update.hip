@@ -30,9 +30,9 @@
 // factors, and that X is B.  k_lin_b is skipped; k_upd_m onward runs unchanged on that B.  The sums of B come in another order
 // than on the rectangular set, so the outputs of the two routes agree to round-off, not bitwise.
 //
-// Across teams (dpgo_team_linear_update_across; DESIGN.md 5j, "across teams") the path is covariance_schur_across with the hook
-// and the caller's pairs together.  k_upd_rhs_across writes this participant's rows of V = A^T from a compact table of the
-// endpoint poses that an allgather has made identical everywhere; the hook's X is B_loc.  A second allgather carries the rows
+// Across teams (dpgo_team_linear_update_across; DESIGN.md 5j, "across teams") the path is covariance_schur_across with its
+// AcrossStep (UpdateAcross below) and the caller's pairs together.  k_upd_rhs_across writes this participant's rows of V = A^T from a compact table of the
+// endpoint poses that an allgather has made identical everywhere; the step's X is B_loc.  A second allgather carries the rows
 // of B at the poses the records and the pairs name, every participant runs k_upd_m onward on that compact B_C (N := C), and
 // k_lin_u and k_lin_finish on B_loc for its own poses; k_upd_pairs_across forms the pair blocks from B_C and U_C.
 #include "linear_frame.h"
@@ -237,12 +237,12 @@ int linear_update_call(const LinearArgs &a, double *xi_post, double *scalars, bo
 
 const ClosureCall UPDATE_ACROSS = {"linear_update_across", "closure"};
 
-// The app handed to covariance_schur_across together with the caller's pairs.  resolve(): the records' endpoints and the pairs
+// The step handed to covariance_schur_across together with the caller's pairs.  resolve(): the records' endpoints and the pairs
 // in the global numbering, the compact set of C poses {endpoints} u {pair poses} sorted by global pose, and allgather E, T of
 // those poses from their holders.  rhs(): V = A^T on this participant's rows.  taken(): this participant's rows of B_loc = X at
 // the compact poses it holds, gathered on the device.  exchange(): allgather F carries them, every participant assembles B_C and runs
 // everything of order 6 K on identical bytes, and its own poses on B_loc.
-struct UpdateAcross : CovApply {
+struct UpdateAcross : AcrossStep {
   dpgo_team_t *t = nullptr;
   const double *T_host = nullptr;
   const dpgo_measurement_t *meas = nullptr;
@@ -268,6 +268,7 @@ struct UpdateAcross : CovApply {
   std::string pivot;            // the refusal of a non-positive pivot of M: the same on every participant
   size_t K() const { return (size_t)num; }
   size_t out_doubles() const { return (size_t)54 * N + 36 * (size_t)npairs + 12 * K() + 4; }
+  int num_cols() const override { return argerr.empty() ? 6 * num : 0; }
 
   int resolve(Across &x, std::string &msg) override {
     const ClosureCall &A = UPDATE_ACROSS;
@@ -312,13 +313,13 @@ struct UpdateAcross : CovApply {
     }
     max_held = (size_t)*std::max_element(held.begin(), held.end());
     // ---- allgather E: T of the compact poses, 12 doubles each from its holder, zeros from everyone else
-    std::vector<double> ge(1 + 12 * (size_t)C, 0.0), all;
+    const HeldRecord rec{12, holder};
+    std::vector<double> ge(rec.len(), 0.0), all;
     for (int c = 0; c < C; ++c)
-      if (lpose[c] >= 0) std::memcpy(ge.data() + 1 + 12 * (size_t)c, T_host + (size_t)12 * lpose[c], sizeof(double) * 12);
+      if (lpose[c] >= 0) std::memcpy(rec.mine(ge, c), T_host + (size_t)12 * lpose[c], sizeof(double) * 12);
     if (x.gather(ge, all)) return 2;
     T_C.resize(12 * (size_t)C);
-    for (int c = 0; c < C; ++c)
-      std::memcpy(T_C.data() + 12 * (size_t)c, all.data() + (size_t)holder[c] * ge.size() + 1 + 12 * (size_t)c, sizeof(double) * 12);
+    for (int c = 0; c < C; ++c) std::memcpy(T_C.data() + 12 * (size_t)c, rec.from(all, c), sizeof(double) * 12);
     return DPGO_OK;
   }
 
@@ -435,7 +436,7 @@ extern "C" int dpgo_team_linear_update_across(dpgo_team_t *t, const dpgo_transpo
   if (!t || !tr) return A.refuse("null argument");  // (nobody to tell)
   UpdateAcross app;
   app.name = A.name;
-  app.op = 8;
+  app.op = 8;  // (the step's own record: the number of records, the hash of records and pairs, num_pairs)
   app.t = t;
   app.T_host = T;
   app.meas = closures;
@@ -487,17 +488,16 @@ extern "C" int dpgo_team_linear_update_across(dpgo_team_t *t, const dpgo_transpo
       h.add(v, sizeof(double) * 14);
     }
     for (int k = 0; k < 2 * num_pairs; ++k) h.add(pairs[k]);
-    app.num_cols = 6 * num;
     app.agree_num = num;
     app.agree_hash = h.value();
     app.agree_int = num_pairs;
   }
-  const bool bad_args = !app.argerr.empty();
-  if (const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, T, DPGO_COV_SCHUR, bad_args ? 0 : num_pairs, bad_args ? nullptr : pairs,
-                                             nullptr, cov_pairs, res, nullptr, &app)) {
-    if (res) std::memset(res, 0, sizeof *res);
-    return rc;
-  }
+  SchurAcrossArgs path(t, tr, owner_rank_of_robot, T);
+  if (app.argerr.empty()) { path.num_pairs = num_pairs; path.pairs = pairs; }
+  path.cov_pairs = cov_pairs;
+  path.res = res;
+  path.step = &app;
+  if (const int rc = covariance_schur_across(path)) return rc;  // (res is then all zero)
   if (!app.pivot.empty() || !app.ran) {  // (every participant formed the same M from the same bytes: the same words everywhere)
     std::memset(res, 0, sizeof *res);
     return A.refuse(app.pivot.empty() ? "the covariance path staged no blocks" : app.pivot);

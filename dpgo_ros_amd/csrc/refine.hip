@@ -533,10 +533,11 @@ struct RefineAcrossWs {
 
 // the hook of the step across teams: g into V, and behind X the halo rows of X out of x_S, the trial trajectories over this
 // participant's poses and their halo, and the robots' sums
-struct RefineAcrossStep : CovApply {
+struct RefineAcrossStep : ApplyStep {
   RefineAcrossWs *ws = nullptr;
   Events ev{3};
   bool ran = false;
+  RefineAcrossStep() : ApplyStep(1) {}
   int rhs(const double *, int N, double *V, hipStream_t s) override {
     if (N != ws->N) return REFINE_ACROSS.refuse("the covariance path's poses are not the call's");
     HIPC(hipMemcpyAsync(V, ws->d_g.p, sizeof(double) * 6 * (size_t)N, hipMemcpyDeviceToDevice, s));
@@ -627,7 +628,6 @@ extern "C" int dpgo_team_refine_across(dpgo_team_t *t, const dpgo_transport_t *t
   if (t->id2local.count(0)) ws.fixed = offs[t->id2local.at(0)];
   RefineAcrossStep hook;
   hook.ws = &ws;
-  hook.num_cols = 1;
   if (ws.measurements() || ws.alloc(s) || hook.ev.create()) x.fail_local(g_err);
   // (the driver's halo tables in buffers of its own: every path inside carves its own out of the team's workspace)
   if (!x.bad) x.place(ws.d_xa.p, ws.d_xi.p, s);
@@ -688,7 +688,10 @@ extern "C" int dpgo_team_refine_across(dpgo_team_t *t, const dpgo_transport_t *t
     hook.ran = false;
     dpgo_covariance_t cur;
     const auto t1 = std::chrono::steady_clock::now();
-    const int rc = covariance_schur_across(t, tr, owner_rank_of_robot, Tk.data(), DPGO_COV_SCHUR, 0, nullptr, nullptr, nullptr, &cur, nullptr, &hook);
+    SchurAcrossArgs step(t, tr, owner_rank_of_robot, Tk.data());
+    step.res = &cur;
+    step.step = &hook;
+    const int rc = covariance_schur_across(step);
     if (rc != DPGO_OK) {
       // a pivot that is not positive (the same words on every participant): at the input the call is refused in the path's
       // words, later it stops at the last good T
